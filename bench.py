@@ -15,7 +15,14 @@ region / max-over-ranks time, summed over ranks ("weak" scaling: G games residen
 With N > 1 each rank plays its own shard; the one collective of the path — the all-gather of the
 finished-game records at generation end — is inside the timed region and also reported separately.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the JSON line; nothing else runs on the GPU.
+--dump-outputs DIR then writes what the timed path produced in its last step: the records of the G games
+that step accounts for (game ids (W+K-1)*G .. (W+K)*G-1; slots take ids in order, and a game still in
+play at the end of the timed region is played out, untimed, on the same evaluator) as DIR/<field>.npy,
+float32 / float64, at most 64 MB (a fixed, seeded sample of the games beyond that).  A game depends only
+on the seed, its id and the network, so two builds given the same arguments can be compared array for array.
+
+Extra objects on the JSON line, measured only with --full (each takes runs of its own):
   roofline       dominant kernel(s) of a tick = the PV-net forward (MFMA bound): algorithmic FLOPs per
                  evaluated leaf x leaves per tick / HIP-event time of the forward
   roofline_tree  the search kernels (HBM bound, latency-limited): SURVEY.md §8(d) bytes per sim with the
@@ -218,7 +225,7 @@ def main():
                     help="fused backend: f32x = fp32-grade split-fp16 mode, 3 MFMAs per product (the product default: the reference's "
                          "Net.forward is fp32); f16 = opt-in fp16 MFMA operands")
     ap.add_argument("--companion-steps", type=int, default=2,
-                    help="whole steps timed for the other-precision companion leg after the main run (0 = skip)")
+                    help="--full: whole steps timed for the other-precision companion leg after the main run (0 = skip)")
     ap.add_argument("--check-every", type=int, default=128)
     ap.add_argument("--nodes-per-slot", type=int, default=0, help="node-pool capacity per slot (0 = engine default)")
     ap.add_argument("--max-sims-per-tick", type=int, default=0, help="NN-free playouts a slot may chain per tick (0 = default)")
@@ -232,17 +239,24 @@ def main():
                          "2814 -> 2873 -> 2889 games/s on one box)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline", default="full", choices=["full", "quick", "off"],
-                    help="full = SURVEY 8(d): all cores >= 64 full games + 1 thread 8 games + C1 point (~1.5 min); quick = 1 game per leg")
+                    help="--full: full = SURVEY 8(d): all cores >= 64 full games + 1 thread 8 games + C1 point (~1.5 min); quick = 1 game per leg")
     ap.add_argument("--ref-seconds", type=float, default=10.0,
-                    help="wall-time cap of the torch-fp32 (Net.forward under PyTorch-ROCm) leg that follows the timed run; 0 = skip "
+                    help="--full: wall-time cap of the torch-fp32 (Net.forward under PyTorch-ROCm) leg that follows the timed run; 0 = skip "
                          "both companion legs")
     ap.add_argument("--tick-limit", type=int, default=0,
                     help="profiling aid (rocprofv3 --pmc passes serialise every dispatch): end the timed region after this many ticks "
                          "even if the K steps are not complete; the line then carries tick_limited = true and is NOT a bench result")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: cpu_baseline, the instrumented roofline pass, the "
+                         "other-precision and torch-fp32 companion legs (a plain run only sets up, warms up and times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the finished-game records of the last step as DIR/<name>.npy (rank 0)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N>1 (nccl = RCCL over xGMI; gloo only to rehearse several ranks on one GPU)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N`: this process has not touched the GPU; start the N ranks as a CHILD process
@@ -260,7 +274,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and args.cpu_baseline != "off":
+    if args.full and world == 1 and not args.no_cpu_baseline and args.cpu_baseline != "off":
         # host-core baseline first: child processes, before this process initialises the GPU
         ckpt = None
         if args.weights == "checkpoint":
@@ -406,41 +420,85 @@ def main():
         tot[0] = mx[0]
     dt_all, games_all, sims_all, evals_all, moves_all = [float(x) for x in tot.tolist()]
 
-    # ---- instrumented eager pass: HIP events on the launch stream ------------------------------------
-    n_probe = 24
-    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(n_probe)]
-    pa = eng.progress()
-    for i in range(n_probe):
-        ev[i][0].record()
-        eng.advance(pri, val, obs)
-        ev[i][1].record()
-        evaluator(obs, pri, val)
-        ev[i][2].record()
-    torch.cuda.synchronize(device)
-    pb = eng.progress()
-    t_tree = float(np.median([e[0].elapsed_time(e[1]) for e in ev])) * 1e-3
-    t_net = float(np.median([e[1].elapsed_time(e[2]) for e in ev])) * 1e-3
-    sims_tick = (pb["sims"] - pa["sims"]) / n_probe
-    evals_tick = (pb["evals"] - pa["evals"]) / n_probe
     d_mean = (p1["sum_depth"] - p0["sum_depth"]) / max(1, sims)
     a_sel = (p1["sum_children"] - p0["sum_children"]) / max(1, p1["sum_depth"] - p0["sum_depth"])
-    a_leaf = (p1["nodes_allocated"] - p0["nodes_allocated"]) / max(1, evals)
-    b_sim = tree_bytes_per_sim(d_mean, a_sel, a_leaf, A, H, Wd)
-    f_eval = net_flops_per_eval(H, Wd, A, args.blocks, args.filters)
-    net_tflops = evals_tick * f_eval / t_net / 1e12  # evaluated leaves only: slots without a request hold stale boards
-    e2e_tflops = evals_all / world / dt_all * f_eval / 1e12  # per GPU, over the whole timed region (gaps + tick kernel included)
-    tree_gbs = sims_tick * b_sim / t_tree / 1e9
-    peak = MFMA_PEAK_TFLOPS[args.dtype]
-    # MFMA work actually ISSUED (padding included) against the 2.5 PFLOP/s fp16 pipe: v_mfma_f32_16x16x32_f16 = 16384 FLOP
-    issued_mfma = evaluator.issued_mfma_per_board() if args.net == "fused" else None
-    issued_frac = (issued_mfma * 16384.0 * evals_tick / t_net / 1e12 / MFMA_PEAK_TFLOPS["f16"]) if issued_mfma else None
 
-    # HBM bytes per launch: rocprofv3 PMC counters cannot be collected from inside this process, so they are read from the
-    # committed summary of the profiled command and quoted only when this run IS that workload (pmc_traffic)
-    traffic_net = traffic_tree = None
-    if args.net == "fused":
-        traffic_net, traffic_tree = pmc_traffic(workload_key(game.name, G, S, args.blocks, args.filters, args.net, args.weights,
-                                                             args.precision, args.overlap, tpg))
+    # ---- --dump-outputs: the records of the last timed step's G games (module docstring), before anything else ticks ----
+    def dump_outputs(out_dir):
+        lo, hi = (Wm + K - 1) * G, (Wm + K) * G
+        while True:
+            ex = eng.export()
+            if (ex["game_len"][lo:hi] > 0).all() or eng.games_done() >= n_total:
+                break
+            run_until(min(n_total, eng.games_done() + max(1, G // 4)))  # untimed: play out the step's games still in progress
+        arrays = {"game_id": (np.arange(len(ex["game_len"])), np.float64), "game_len": (ex["game_len"], np.float32),
+                  "game_ret0": (ex["game_ret0"], np.float32), "move": (ex["move"], np.float32),
+                  "n_children": (ex["n_children"], np.float32), "child_action": (ex["child_action"], np.float32),
+                  "child_visits": (ex["child_visits"], np.float32), "value": (ex["value"], np.float64),
+                  "states": (ex["states"].view(np.uint32), np.float64)}  # 64-bit bitboards as exact 32-bit halves
+        per_game = sum(a[0].size * np.dtype(t).itemsize for a, t in arrays.values())
+        ids = np.arange(lo, hi)
+        keep = (64_000_000 - 4096) // per_game  # 64 MB in all, .npy headers included
+        if len(ids) > keep:
+            ids = np.sort(np.random.RandomState(0).choice(ids, keep, replace=False))
+        os.makedirs(out_dir, exist_ok=True)
+        for name, (a, t) in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[ids], dtype=t))
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs)
+
+    extra = {}
+    if args.full:
+        # ---- instrumented eager pass: HIP events on the launch stream ------------------------------------
+        n_probe = 24
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(n_probe)]
+        pa = eng.progress()
+        for i in range(n_probe):
+            ev[i][0].record()
+            eng.advance(pri, val, obs)
+            ev[i][1].record()
+            evaluator(obs, pri, val)
+            ev[i][2].record()
+        torch.cuda.synchronize(device)
+        pb = eng.progress()
+        t_tree = float(np.median([e[0].elapsed_time(e[1]) for e in ev])) * 1e-3
+        t_net = float(np.median([e[1].elapsed_time(e[2]) for e in ev])) * 1e-3
+        sims_tick = (pb["sims"] - pa["sims"]) / n_probe
+        evals_tick = (pb["evals"] - pa["evals"]) / n_probe
+        a_leaf = (p1["nodes_allocated"] - p0["nodes_allocated"]) / max(1, evals)
+        b_sim = tree_bytes_per_sim(d_mean, a_sel, a_leaf, A, H, Wd)
+        f_eval = net_flops_per_eval(H, Wd, A, args.blocks, args.filters)
+        net_tflops = evals_tick * f_eval / t_net / 1e12  # evaluated leaves only: slots without a request hold stale boards
+        e2e_tflops = evals_all / world / dt_all * f_eval / 1e12  # per GPU, over the whole timed region (gaps + tick kernel included)
+        tree_gbs = sims_tick * b_sim / t_tree / 1e9
+        peak = MFMA_PEAK_TFLOPS[args.dtype]
+        # MFMA work actually ISSUED (padding included) against the 2.5 PFLOP/s fp16 pipe: v_mfma_f32_16x16x32_f16 = 16384 FLOP
+        issued_mfma = evaluator.issued_mfma_per_board() if args.net == "fused" else None
+        issued_frac = (issued_mfma * 16384.0 * evals_tick / t_net / 1e12 / MFMA_PEAK_TFLOPS["f16"]) if issued_mfma else None
+
+        # HBM bytes per launch: rocprofv3 PMC counters cannot be collected from inside this process, so they are read from the
+        # committed summary of the profiled command and quoted only when this run IS that workload (pmc_traffic)
+        traffic_net = traffic_tree = None
+        if args.net == "fused":
+            traffic_net, traffic_tree = pmc_traffic(workload_key(game.name, G, S, args.blocks, args.filters, args.net, args.weights,
+                                                                 args.precision, args.overlap, tpg))
+        extra["roofline"] = {"bound": "mfma", "kernel": (evaluator.kernel_label() if args.net == "fused" else "torch Net.forward (MIOpen)")
+                                       + ", %d boards/launch" % G,
+                             "achieved": net_tflops, "peak": peak, "unit": "TFLOP/s", "frac": net_tflops / peak,
+                             "peak_note": ("dense fp16 MFMA peak 2500 TFLOP/s / 3 MFMAs per product" if args.dtype == "f16x3" else
+                                           "dense MFMA peak for the dtype (MI355X_MICROARCH.md)"),
+                             # the same achieved rate against the guide's RAW peaks, whatever `peak` was derived from
+                             "frac_of_fp16_peak": net_tflops / MFMA_PEAK_TFLOPS["f16"], "x_fp32_mfma_peak": net_tflops / MFMA_PEAK_TFLOPS["f32"],
+                             "frac_issued": issued_frac, "issued_mfma_per_board": issued_mfma,
+                             "frac_end_to_end": e2e_tflops / peak, "end_to_end_tflops": e2e_tflops,
+                             "traffic": traffic_net, "traffic_unit": "bytes/launch (PMC, %s)" % PROFILE_SUMMARY,
+                             "flops_per_eval": f_eval, "ms_per_launch": 1e3 * t_net,
+                             "batch_fill": evals_tick / G}
+        extra["roofline_tree"] = {"bound": "hbm", "kernel": "az_advance_kernel (playouts + move step)",
+                                  "achieved": tree_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                  "frac": tree_gbs / HBM_PEAK_GBS, "traffic": traffic_tree, "bytes_per_sim": b_sim,
+                                  "sims_per_launch": sims_tick, "ms_per_launch": 1e3 * t_tree}
 
     # ---- companion legs: the SAME engine, slots, games in flight and net weights under another evaluator -----------------
     #   steps_leg  whole steps (n_steps x G games completed), the same tpg-ticks-per-graph replay path as the main run:
@@ -517,7 +575,7 @@ def main():
         return leg_result(q0, eng.progress(), dtr, n_ticks, ms)
 
     companion = None
-    if world == 1 and args.net == "fused" and args.overlap == 1 and args.ref_seconds > 0:
+    if args.full and world == 1 and args.net == "fused" and args.overlap == 1 and args.ref_seconds > 0:
         sync_groups()
         other = "f16" if args.precision == "f32x" else "f32x"
         if args.companion_steps > 0:
@@ -566,23 +624,8 @@ def main():
             "terminal_hit_fraction": (p1["terminal_hits"] - p0["terminal_hits"]) / max(1, sims),
             "allgather_ms": allgather_ms, "compactions": p1["compactions"] - p0["compactions"],
             "engine_hbm_gb": eng.sizes.device_bytes / 1e9,
-            "roofline": {"bound": "mfma", "kernel": (evaluator.kernel_label() if args.net == "fused" else "torch Net.forward (MIOpen)")
-                                   + ", %d boards/launch" % G,
-                         "achieved": net_tflops, "peak": peak, "unit": "TFLOP/s", "frac": net_tflops / peak,
-                         "peak_note": ("dense fp16 MFMA peak 2500 TFLOP/s / 3 MFMAs per product" if args.dtype == "f16x3" else
-                                       "dense MFMA peak for the dtype (MI355X_MICROARCH.md)"),
-                         # the same achieved rate against the guide's RAW peaks, whatever `peak` was derived from
-                         "frac_of_fp16_peak": net_tflops / MFMA_PEAK_TFLOPS["f16"], "x_fp32_mfma_peak": net_tflops / MFMA_PEAK_TFLOPS["f32"],
-                         "frac_issued": issued_frac, "issued_mfma_per_board": issued_mfma,
-                         "frac_end_to_end": e2e_tflops / peak, "end_to_end_tflops": e2e_tflops,
-                         "traffic": traffic_net, "traffic_unit": "bytes/launch (PMC, %s)" % PROFILE_SUMMARY,
-                         "flops_per_eval": f_eval, "ms_per_launch": 1e3 * t_net,
-                         "batch_fill": evals_tick / G},
-            "roofline_tree": {"bound": "hbm", "kernel": "az_advance_kernel (playouts + move step)",
-                              "achieved": tree_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                              "frac": tree_gbs / HBM_PEAK_GBS, "traffic": traffic_tree, "bytes_per_sim": b_sim,
-                              "sims_per_launch": sims_tick, "ms_per_launch": 1e3 * t_tree},
         }
+        out.update(extra)
         if companion is not None:
             out["opt_in_f16" if args.precision == "f32x" else "reference_precision"] = companion
         if cpu is not None:

@@ -22,6 +22,8 @@ oracle/fakepolicy.py as policy_fn):
   arena.json          game_utils.play_game between the reference's AlphaZeroBot (outside self-play) and NeuralNetBot
                       instances with different policy functions / settings, both seatings (game_utils.py:16-35,
                       alphazerobot.py:42-120)
+  trainer_on_engine_export.npz  Trainer.remove_duplicates and one net_step on the engine-produced records of
+                      engine_export_connect_four.npz (that fixture must exist first)
   rules_*.json        random playouts of oracle/pygames.py (NOT reference output:
                       OpenSpiel is absent; rules are "parity unpinned")
 
@@ -478,6 +480,53 @@ def gen_arena(ref):
     return out
 
 
+def gen_trainer_on_engine_export(ref):
+    """The reference's own Trainer on ENGINE output: the records of tests/golden/engine_export_connect_four.npz (two
+    engine-produced generations, tools/make_engine_export_fixture.py) in the reference's list format, pushed through its
+    buffer handling (train.py:226-236), Trainer.remove_duplicates (train.py:156-201) and one Trainer.net_step
+    (train.py:95-130) with the shipped connect_four checkpoint (CPU, fp32, one thread)."""
+    import types
+
+    import torch
+    from alphazero_openspiel_amd import distributed as azdist, games
+    from alphazero_openspiel_amd.engine import examples_from_export
+    Trainer = ref.train.Trainer
+    fx = np.load(os.path.join(GOLD, "engine_export_connect_four.npz"))
+    game = games.load_game("connect_four")
+    out, buffer = {}, []
+    for g in range(2):
+        buffer += examples_from_export(game, azdist.unpack_export(fx["gen%d_payload" % g]))
+        while len(buffer) > int(fx["gen%d_capacity" % g]):
+            del buffer[0]
+        flat = [s for game_ in buffer for s in game_]
+        uniq = Trainer.remove_duplicates(flat)
+        pos = {id(it): i for i, it in enumerate(flat)}
+        out["gen%d_unique_pi" % g] = np.array([it[2] for it in uniq], dtype=np.float64)
+        out["gen%d_unique_z" % g] = np.array([it[3] for it in uniq], dtype=np.float64)
+        out["gen%d_unique_index" % g] = np.array([pos[id(it)] for it in uniq], dtype=np.int64)
+    net = ref.network.Net([3, 6, 7], 7)
+    net.load_state_dict(torch.load(os.path.join(ref_harness.REFERENCE_DIR, "models", "example_model_connect_four.pth"),
+                                   map_location="cpu", weights_only=True))
+    net.train()
+    torch.set_num_threads(1)
+    np.random.seed(5)
+    ids = np.random.randint(len(uniq), size=16)
+    out["batch_ids"] = ids.astype(np.int64)
+    out["batch_x"] = np.array([uniq[i][1] for i in ids], dtype=np.float32)
+    out["batch_pi"] = np.array([uniq[i][2] for i in ids]).astype(np.float32)
+    out["batch_z"] = np.array([uniq[i][3] for i in ids]).astype(np.float32)
+    fake = types.SimpleNamespace(current_net=net, batch_size=16, device=torch.device("cpu"),
+                                 criterion_value=torch.nn.MSELoss(), it=0,
+                                 optimizer=torch.optim.Adam(net.parameters(), lr=0.001, weight_decay=0.0001))
+    np.random.seed(5)
+    loss_p, loss_v = Trainer.net_step(fake, uniq)
+    out["loss_p"], out["loss_v"] = np.float64(float(loss_p.detach())), np.float64(float(loss_v.detach()))
+    out["fc1_bias_after"] = net.fc1.bias.detach().numpy().astype(np.float64)
+    path = os.path.join(GOLD, "trainer_on_engine_export.npz")
+    np.savez_compressed(path, **out)
+    return path, os.path.getsize(path)
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
     ref = ref_harness.load_reference()
@@ -497,6 +546,7 @@ def main():
     print("net_forward:", gen_net_forward(ref))
     dump("replay.json", gen_replay(ref))
     dump("arena.json", gen_arena(ref))
+    print("trainer_on_engine_export:", gen_trainer_on_engine_export(ref))
 
 
 if __name__ == "__main__":

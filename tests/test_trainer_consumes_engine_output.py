@@ -1,30 +1,28 @@
-"""The REAL reference Trainer consuming engine output unchanged (BASELINE.json north_star: "the (state, pi, z)
+"""The reference's Trainer consuming engine output unchanged (BASELINE.json north_star: "the (state, pi, z)
 training-example format [is] preserved so train.py's Trainer consumes the output unchanged").
 
-The engine only exists on the GPU box and the reference only in the build container, so the two meet through a DATA
-fixture: tests/golden/engine_export_connect_four.npz, written on an MI355X by tools/make_engine_export_fixture.py - the
-packed records of two engine-produced generations plus what the DEVICE replay store made of them (its
-remove_duplicates result, one gathered training batch, the losses of one update on it).
+The engine only runs on a GPU and the reference is not part of this repository, so the two meet through DATA fixtures:
+tests/golden/engine_export_connect_four.npz, written on an MI355X by tools/make_engine_export_fixture.py - the packed
+records of two engine-produced generations plus what the DEVICE replay store made of them (its remove_duplicates result,
+one gathered training batch, the losses of one update on it) - and tests/golden/trainer_on_engine_export.npz, written by
+oracle/gen_golden.py running the reference's own buffer handling (train.py:226-236), `Trainer.remove_duplicates`
+(train.py:156-201) and `Trainer.net_step` (train.py:95-130) on those same records.
 
-Here (container only: needs /root/reference) the same records are turned into the reference's list format by
-`examples_from_export`, pushed through the reference's own buffer handling (train.py:226-236), its own
-`Trainer.remove_duplicates` (train.py:156-201) and its own `Trainer.net_step` (train.py:95-130), unbound, and compared:
-pi / z of the de-duplicated list bit for bit (float64), the sampled batch bit for bit (float32), the losses to 2e-6.
+Here the records are turned into the reference's list format by `examples_from_export` and pushed through the Python
+restatement of the Trainer (oracle/pyreplay.py, pinned to the reference by tests/golden/replay.json) and the facade's
+`net_step` with the re-packed shipped checkpoint, and compared with both fixtures: pi / z of the de-duplicated list bit for
+bit (float64), the sampled batch bit for bit (float32), the losses to 2e-6.
 """
 import os
-import types
 
 import numpy as np
-import pytest
 import torch
 
 from conftest import GOLDEN
-from oracle import ref_harness
+from oracle import pyreplay
 
 FIXTURE = os.path.join(GOLDEN, "engine_export_connect_four.npz")
-pytestmark = [pytest.mark.reference,
-              pytest.mark.skipif(not ref_harness.reference_available(), reason="needs /root/reference (build container)"),
-              pytest.mark.skipif(not os.path.isfile(FIXTURE), reason="fixture not generated yet")]
+TRAINER = os.path.join(GOLDEN, "trainer_on_engine_export.npz")
 
 
 def _generations():
@@ -53,8 +51,9 @@ def test_engine_records_have_the_format_the_trainer_requires():
 
 
 def test_reference_remove_duplicates_on_engine_output_equals_the_device_store():
-    ref = ref_harness.load_reference()
-    Trainer = ref.train.Trainer
+    from alphazero_openspiel_amd import replay
+    from alphazero_openspiel_amd.network import load_npz_checkpoint
+    ref = np.load(TRAINER)                           # what the reference's Trainer made of these records
     fx, game, gens = _generations()
     buffer = []
     for g, games_ in enumerate(gens):
@@ -64,28 +63,27 @@ def test_reference_remove_duplicates_on_engine_output_equals_the_device_store():
         while len(buffer) > n_games_buffer:          # train.py:233-236
             del buffer[0]
         flattened = [sample for game_ in buffer for sample in game_]
-        out = Trainer.remove_duplicates(flattened)   # train.py:156-201, including its write-back into `buffer`
-        assert len(out) == int(fx["gen%d_n_unique" % g])
-        assert [it[2] for it in out] == fx["gen%d_unique_pi" % g].tolist()
-        assert [it[3] for it in out] == fx["gen%d_unique_z" % g].tolist()
-        # first-occurrence order: the device store reports the flat-buffer index of every unique record
-        assert [id(it) for it in out] == [id(flattened[i]) for i in fx["gen%d_unique_index" % g]]
-    # ---- Trainer.net_step on the de-duplicated list: the same draw, the same batch, the same losses ----
-    ckpt = os.path.join(ref_harness.REFERENCE_DIR, "models", "example_model_connect_four.pth")
-    net = ref.network.Net([3, 6, 7], 7)
-    net.load_state_dict(torch.load(ckpt, map_location="cpu", weights_only=True))
+        out = pyreplay.remove_duplicates(flattened)  # train.py:156-201, including its write-back into `buffer`
+        assert len(out) == int(fx["gen%d_n_unique" % g]) == len(ref["gen%d_unique_z" % g])
+        for want in (fx, ref):
+            assert [it[2] for it in out] == want["gen%d_unique_pi" % g].tolist()
+            assert [it[3] for it in out] == want["gen%d_unique_z" % g].tolist()
+            # first-occurrence order: the device store reports the flat-buffer index of every unique record
+            assert [id(it) for it in out] == [id(flattened[i]) for i in want["gen%d_unique_index" % g]]
+    # ---- net_step on the de-duplicated list: the same draw, the same batch, the same losses ----
+    net = load_npz_checkpoint(os.path.join(GOLDEN, "checkpoint_connect_four.npz"), [3, 6, 7], 7)
     net.train()
     torch.set_num_threads(1)
     np.random.seed(5)
     ids = np.random.randint(len(out), size=16)
-    assert ids.tolist() == fx["batch_ids"].tolist()
-    assert (np.array([out[i][1] for i in ids], dtype=np.float32) == fx["batch_x"]).all()
-    assert (np.array([out[i][2] for i in ids]).astype(np.float32) == fx["batch_pi"]).all()
-    assert (np.array([out[i][3] for i in ids]).astype(np.float32) == fx["batch_z"]).all()
-    fake = types.SimpleNamespace(current_net=net, batch_size=16, device=torch.device("cpu"),
-                                 criterion_value=torch.nn.MSELoss(), it=0,
-                                 optimizer=torch.optim.Adam(net.parameters(), lr=0.001, weight_decay=0.0001))
-    np.random.seed(5)
-    loss_p, loss_v = Trainer.net_step(fake, out)
-    assert abs(float(loss_p) - float(fx["loss_p"])) < 2e-6 and abs(float(loss_v) - float(fx["loss_v"])) < 2e-6
-    assert np.abs(net.fc1.bias.detach().numpy() - fx["fc1_bias_after"]).max() < 2e-6
+    x = np.array([out[i][1] for i in ids], dtype=np.float32)
+    pi = np.array([out[i][2] for i in ids]).astype(np.float32)
+    z = np.array([out[i][3] for i in ids]).astype(np.float32)
+    for want in (fx, ref):
+        assert ids.tolist() == want["batch_ids"].tolist()
+        assert (x == want["batch_x"]).all() and (pi == want["batch_pi"]).all() and (z == want["batch_z"]).all()
+    loss_p, loss_v = replay.net_step(net, replay.make_optimizer(net), torch.from_numpy(x), torch.from_numpy(pi), torch.from_numpy(z))
+    loss_p, loss_v = float(loss_p.detach()), float(loss_v.detach())
+    for want in (fx, ref):
+        assert abs(loss_p - float(want["loss_p"])) < 2e-6 and abs(loss_v - float(want["loss_v"])) < 2e-6
+        assert np.abs(net.fc1.bias.detach().numpy() - want["fc1_bias_after"]).max() < 2e-6

@@ -1,5 +1,5 @@
 set -x
-C="--cpu-baseline off --ref-seconds 0"
+C="--full --cpu-baseline off --ref-seconds 0"
 python bench.py $C --game "breakthrough(rows=6,columns=6)" --playouts 800 > gpurun_out/r3_bench_c3_f32x.json 2> gpurun_out/r3_c3a.err
 python bench.py $C --game "breakthrough(rows=6,columns=6)" --playouts 800 --precision f16 > gpurun_out/r3_bench_c3_f16.json 2> gpurun_out/r3_c3b.err
 python bench.py $C --game "breakthrough(rows=8,columns=8)" --playouts 1600 --blocks 20 --slots 2048 --steps 1 --warmup 1 --precision f16 > gpurun_out/r3_bench_c5_f16.json 2> gpurun_out/r3_c5b.err
