@@ -68,6 +68,16 @@ class AzNetDesc(C.Structure):
                 ("fc_w", C.POINTER(C.c_uint16)), ("fc_b", C.POINTER(C.c_float)),
                 ("conv_w_lo", C.POINTER(C.c_uint16)), ("fc_w_lo", C.POINTER(C.c_uint16))]
 NET_PREC = {"f16": 0, "f32x": 1}
+NET_WIDE_MAX_FILTERS = 256
+
+
+class AzNetWideDesc(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("in_planes", C.c_int32),
+                ("n_filters", C.c_int32), ("n_blocks", C.c_int32), ("num_actions", C.c_int32), ("device", C.c_int32),
+                ("precision", C.c_int32), ("reserved", C.c_int32),
+                ("conv_w", C.POINTER(C.c_float)), ("conv_b", C.POINTER(C.c_float)), ("bn1_scale", C.POINTER(C.c_float)),
+                ("bn1_shift", C.POINTER(C.c_float)), ("skip_w", C.POINTER(C.c_float)), ("fc_w", C.POINTER(C.c_float)),
+                ("fc_b", C.POINTER(C.c_float))]
 
 
 class AzReplayConfig(C.Structure):
@@ -109,6 +119,7 @@ PROTOTYPES = [
     ("az_engine_read_tree", C.c_int64, [_vp, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("az_net_create", C.c_int, [C.POINTER(AzNetDesc), C.POINTER(_vp)]),
+    ("az_net_create_wide", C.c_int, [C.POINTER(AzNetWideDesc), C.POINTER(_vp)]),
     ("az_net_destroy", C.c_int, [_vp]),
     ("az_net_last_error", C.c_char_p, [_vp]),
     ("az_net_forward", C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, _vp]),

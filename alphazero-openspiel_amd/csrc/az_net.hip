@@ -23,6 +23,9 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
+#include <cmath>
+
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -33,6 +36,7 @@
 
 #include "az_net_common.h"
 #include "az_head_params.h"
+#include "az_net_wide.h"
 
 // ================================================================================================
 struct az_net {
@@ -54,6 +58,15 @@ struct az_net {
     int xd_nb = 0, xd_R = 0, xd_rs = 0;
     _Float16 *conv_w_d = nullptr; // the x3d weight stream (conv_w keeps the stream of the small-batch / fallback kernel)
     uint16_t *xd_pos = nullptr, *xd_sdst = nullptr;
+    // the general layer-by-layer path (az_net_create_wide, az_net_wide.h); d then holds the geometry only
+    bool wide = false;
+    int fpad = 0, nbw = 0;
+    std::vector<size_t> w_off;                   // halves from w_wide to conv c's weight stream
+    _Float16 *w_wide = nullptr;                  // every conv's [n_chunks][9][nmt][hi, lo][64][8]
+    float *epi_wide = nullptr, *in_wide = nullptr; // [n_convs][4][fpad]; [in_scale 4][in_shift 4][skip fpad x 4]
+    float *x_wide = nullptr;                     // residual stream [max_boards][HW][fpad]
+    _Float16 *opa_hi = nullptr, *opa_lo = nullptr, *opb_hi = nullptr, *opb_lo = nullptr; // operand planes (opb: conv 0's input, then the tower output)
+    std::string label_wide;                      // az_net_kernel_label
 };
 static std::string g_net_err;
 
@@ -83,6 +96,14 @@ extern "C" int az_net_destroy(az_net *n) {
     (void)hipFree(n->conv_w_d);
     (void)hipFree(n->xd_pos);
     (void)hipFree(n->xd_sdst);
+    (void)hipFree(n->w_wide);
+    (void)hipFree(n->epi_wide);
+    (void)hipFree(n->in_wide);
+    (void)hipFree(n->x_wide);
+    (void)hipFree(n->opa_hi);
+    (void)hipFree(n->opa_lo);
+    (void)hipFree(n->opb_hi);
+    (void)hipFree(n->opb_lo);
     delete n;
     return AZ_OK;
 }
@@ -574,9 +595,223 @@ extern "C" int az_net_create(const az_net_desc *desc, az_net **out) {
     return AZ_OK;
 }
 
+// ================================================================================================
+// The general path (az_net_wide.h): the descriptor holds plain folded fp32 arrays; every device layout is decided here.
+// Conv weights: a power-of-two scale s per output channel puts the channel's largest |w| s in [8, 16), so hi' = 2048 fp16(w s) and
+// lo' = fp16(2048 (w s - fp16(w s))) are finite for any finite weight; the epilogue multiplies by 1 / (2048 s), exactly.
+static std::string wide_label(const az_net *n);
+static int wide_fpad(int f) { return (f + 31) & ~31; }
+static int wide_nks(const az_net *n, int conv) { return conv == 0 ? 9 : 9 * n->fpad / 32; }
+
+extern "C" int az_net_create_wide(const az_net_wide_desc *desc, az_net **out) {
+    if (!desc || !out) {
+        g_net_err = "null argument";
+        return AZ_E_INVALID;
+    }
+    *out = nullptr;
+    if (desc->struct_size != (int32_t)sizeof(az_net_wide_desc)) {
+        g_net_err = "az_net_wide_desc.struct_size mismatch";
+        return AZ_E_INVALID;
+    }
+    const az_net_wide_desc &d = *desc;
+    if (d.rows < 1 || d.cols < 1 || d.rows * d.cols > 64 || d.in_planes < 1 || d.in_planes > 4 || d.n_filters < 1 ||
+        d.n_filters > AZ_NET_WIDE_MAX_FILTERS || d.n_blocks < 1 || d.num_actions < 1 || d.num_actions > 768 || !d.conv_w ||
+        !d.conv_b || !d.bn1_scale || !d.bn1_shift || !d.skip_w || !d.fc_w || !d.fc_b) {
+        g_net_err = "bad wide net description (need rows*cols<=64, 1<=in_planes<=4, 1<=n_filters<=256, A<=768, all buffers)";
+        return AZ_E_INVALID;
+    }
+    if (d.precision != AZ_NET_PREC_F16 && d.precision != AZ_NET_PREC_F16X3) {
+        g_net_err = "precision must be AZ_NET_PREC_F16 or AZ_NET_PREC_F16X3";
+        return AZ_E_INVALID;
+    }
+    const int F = d.n_filters, HW = d.rows * d.cols, cin0 = d.in_planes, C = F > cin0 ? F : cin0, nc = 2 * d.n_blocks;
+    const int fpad = wide_fpad(F), nmt = fpad / 16, A1 = d.num_actions + 1;
+    const size_t n_w = (size_t)nc * F * C * 9;
+    for (size_t i = 0; i < n_w; i++)
+        if (!std::isfinite(d.conv_w[i])) {
+            g_net_err = "az_net_create_wide: a conv weight is not finite";
+            return AZ_E_INVALID;
+        }
+    az_net *n = new az_net();
+    n->d = az_net_desc{};
+    n->d.struct_size = sizeof(az_net_desc);
+    n->d.rows = d.rows, n->d.cols = d.cols, n->d.in_planes = cin0, n->d.n_filters = F, n->d.n_blocks = d.n_blocks;
+    n->d.num_actions = d.num_actions, n->d.device = d.device, n->d.precision = d.precision;
+    n->precision = d.precision;
+    n->wide = true;
+    n->fpad = fpad;
+    n->nbw = 16 * WIDE_NT / HW;
+    n->xc = fpad;
+    n->n_ot = (A1 + 15) / 16;
+    n->fc_ksteps = HW * fpad / 32;
+    n->lds_head = HEAD_NW * OTG * 64 * 16 + 16 * n->n_ot * 16 * 4;
+    hipError_t s = hipSetDevice(d.device);
+    if (s != hipSuccess) {
+        g_net_err = std::string("hipSetDevice: ") + hipGetErrorString(s);
+        delete n;
+        return AZ_E_HIP;
+    }
+    // conv weight streams and epilogue rows
+    std::vector<uint16_t> w;
+    std::vector<float> epi((size_t)nc * 4 * fpad, 0.f);
+    auto h16 = [](double v) {
+        _Float16 h = (_Float16)v;
+        uint16_t b;
+        memcpy(&b, &h, 2);
+        return b;
+    };
+    for (int c = 0; c < nc; c++) {
+        n->w_off.push_back(w.size());
+        const int cin = c == 0 ? WIDE_CIN0 : fpad, n_ch = cin / 32, cin_real = c == 0 ? cin0 : F;
+        const float *wc = d.conv_w + (size_t)c * F * C * 9;
+        std::vector<double> sc(fpad, 1.0);
+        for (int co = 0; co < F; co++) {
+            double m = 0;
+            for (int k = 0; k < cin_real * 9; k++) m = std::max(m, (double)std::fabs(wc[((size_t)co * C + k / 9) * 9 + k % 9]));
+            int e = 0;
+            if (m > 0) {
+                (void)std::frexp(m, &e); // m = f 2^e, f in [0.5, 1): m 2^(4 - e) in [8, 16)
+                e = std::min(100, std::max(-100, 4 - e));
+            }
+            sc[co] = std::ldexp(1.0, e);
+        }
+        const size_t base = w.size();
+        w.resize(base + (size_t)n_ch * 9 * nmt * 2 * 512, 0);
+        for (int ch = 0; ch < n_ch; ch++)
+            for (int tap = 0; tap < 9; tap++)
+                for (int mt = 0; mt < nmt; mt++)
+                    for (int lane = 0; lane < 64; lane++)
+                        for (int j = 0; j < 8; j++) {
+                            const int co = 16 * mt + (lane & 15), ci = 32 * ch + 8 * (lane >> 4) + j;
+                            if (co >= F || ci >= cin_real) continue;
+                            const double v = (double)wc[((size_t)co * C + ci) * 9 + tap] * sc[co];
+                            const double hi = (double)(_Float16)v;
+                            const size_t o = base + ((((size_t)(ch * 9 + tap) * nmt + mt) * 2) * 512) + lane * 8 + j;
+                            w[o] = h16(hi * 2048.0);
+                            w[o + 512] = h16((v - hi) * 2048.0);
+                        }
+        float *e4 = &epi[(size_t)c * 4 * fpad];
+        for (int co = 0; co < fpad; co++) e4[co] = (float)(1.0 / (2048.0 * sc[co]));
+        for (int co = 0; co < F; co++) {
+            e4[fpad + co] = d.conv_b[(size_t)c * F + co];
+            if (c % 2 == 1 && c + 1 < nc) { // the next block's bn1
+                e4[2 * fpad + co] = d.bn1_scale[(size_t)(c / 2 + 1) * C + co];
+                e4[3 * fpad + co] = d.bn1_shift[(size_t)(c / 2 + 1) * C + co];
+            }
+        }
+    }
+    std::vector<float> in((size_t)8 + (size_t)fpad * 4, 0.f);
+    for (int c = 0; c < cin0; c++) in[c] = d.bn1_scale[c], in[4 + c] = d.bn1_shift[c];
+    for (int co = 0; co < F; co++)
+        for (int c = 0; c < cin0; c++) in[8 + (size_t)co * 4 + c] = d.skip_w[(size_t)co * cin0 + c];
+    // fc1 [A+1][F*HW] (index c*HW + pos) -> the heads' stream [n_ot][ksteps][64][8], k = pos * fpad + c; lo = fp16((w - hi) * 2048)
+    const size_t fw = (size_t)n->n_ot * n->fc_ksteps * 512;
+    std::vector<uint16_t> fh(fw, 0), fl(fw, 0);
+    for (int ot = 0; ot < n->n_ot; ot++)
+        for (int ks = 0; ks < n->fc_ksteps; ks++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int j = 0; j < 8; j++) {
+                    const int o = 16 * ot + (lane & 15), k = 32 * ks + 8 * (lane >> 4) + j, pos = k / fpad, c = k % fpad;
+                    if (o >= A1 || c >= F) continue;
+                    const double v = d.fc_w[(size_t)o * F * HW + (size_t)c * HW + pos], hi = (double)(_Float16)v;
+                    const size_t i = (((size_t)ot * n->fc_ksteps + ks) * 64 + lane) * 8 + j;
+                    fh[i] = h16(hi);
+                    fl[i] = h16((v - hi) * 2048.0);
+                }
+    std::vector<float> fb((size_t)n->n_ot * 16, 0.f);
+    for (int o = 0; o < A1; o++) fb[o] = d.fc_b[o];
+    int rc = AZ_OK;
+    auto up = [&](void **dst, const void *src, size_t bytes) {
+        if (rc != AZ_OK) return;
+        if (hipMalloc(dst, bytes) != hipSuccess || hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            g_net_err = "hipMalloc/hipMemcpy of the wide net's weights failed";
+            rc = AZ_E_NOMEM;
+        }
+    };
+    up((void **)&n->w_wide, w.data(), w.size() * 2);
+    up((void **)&n->epi_wide, epi.data(), epi.size() * 4);
+    up((void **)&n->in_wide, in.data(), in.size() * 4);
+    up((void **)&n->fc_w, fh.data(), fw * 2);
+    up((void **)&n->fc_w_lo, fl.data(), fw * 2);
+    up((void **)&n->fc_b, fb.data(), fb.size() * 4);
+    if (rc != AZ_OK) {
+        az_net_destroy(n);
+        return rc;
+    }
+    n->label_wide = wide_label(n);
+    *out = n;
+    return AZ_OK;
+}
+
+// v_mfma_f32_16x16x32_f16 per board of a wide forward of n_boards boards: every workgroup runs all of its channel tiles over
+// ceil(columns / 16) column tiles for every k-step of every conv (x 3 for f32x), then the head
+static double wide_mfma_per_board(const az_net *n, int n_boards) {
+    const int HW = n->d.rows * n->d.cols, nc = 2 * n->d.n_blocks, per = n->precision == AZ_NET_PREC_F16X3 ? 3 : 1;
+    double ks = 0;
+    for (int c = 0; c < nc; c++) ks += wide_nks(n, c);
+    const long full = n_boards / n->nbw, rest = n_boards % n->nbw;
+    const double tiles = (double)full * ((n->nbw * HW + 15) / 16) + (rest ? (rest * HW + 15) / 16 : 0);
+    return per * ks * (n->fpad / 16) * tiles / n_boards + per * (double)n->n_ot * n->fc_ksteps / 16.0;
+}
+static std::string wide_label(const az_net *n) {
+    const bool big = n->n_ot > OTG, x3 = n->precision == AZ_NET_PREC_F16X3;
+    const std::string t = x3 ? "<X3>" : "";
+    return "az_wide_input_kernel + az_conv_wide_kernel" + std::string(x3 ? "<X3>" : "<F16>") + " x" + std::to_string(2 * n->d.n_blocks) +
+           (big ? " + az_head_gemm_kernel" + t + " + az_head_softmax_kernel" + t : " + az_head_kernel" + t);
+}
+static int wide_reserve(az_net *n, int32_t max_boards) {
+    const size_t cells = (size_t)max_boards * n->d.rows * n->d.cols;
+    float **fbufs[] = {&n->x_wide, &n->logits};
+    for (float **b : fbufs) (void)hipFree(*b), *b = nullptr;
+    _Float16 **hbufs[] = {&n->opa_hi, &n->opa_lo, &n->opb_hi, &n->opb_lo};
+    for (_Float16 **b : hbufs) (void)hipFree(*b), *b = nullptr;
+    n->max_boards = 0;
+    NCHK(n, hipMalloc((void **)&n->x_wide, cells * n->fpad * 4));
+    for (_Float16 **b : hbufs) {
+        if (n->precision != AZ_NET_PREC_F16X3 && (b == &n->opa_lo || b == &n->opb_lo)) continue;
+        NCHK(n, hipMalloc((void **)b, cells * n->fpad * 2));
+        NCHK(n, hipMemset(*b, 0, cells * n->fpad * 2));
+    }
+    if (n->n_ot > OTG) NCHK(n, hipMalloc((void **)&n->logits, (size_t)max_boards * n->n_ot * 16 * sizeof(float) * 2));
+    n->max_boards = max_boards;
+    return AZ_OK;
+}
+static int wide_forward(az_net *n, const float *obs, float *priors, float *values, int32_t n_boards, hipStream_t st) {
+    const bool x3 = n->precision == AZ_NET_PREC_F16X3;
+    const int HW = n->d.rows * n->d.cols, nc = 2 * n->d.n_blocks;
+    WideInputParams ip;
+    ip.HW = HW, ip.cin = n->d.in_planes, ip.fpad = n->fpad, ip.n_boards = n_boards;
+    ip.obs = obs, ip.in_scale = n->in_wide, ip.in_shift = n->in_wide + 4, ip.skip_w = n->in_wide + 8;
+    ip.x = n->x_wide, ip.a_hi = n->opb_hi, ip.a_lo = x3 ? n->opb_lo : nullptr;
+    hipError_t s = az_launch_wide_input(ip, st);
+    for (int c = 0; c < nc && s == hipSuccess; c++) {
+        WideConvParams p;
+        p.W = n->d.cols, p.HW = HW, p.nbw = n->nbw, p.n_boards = n_boards;
+        p.cin = c == 0 ? WIDE_CIN0 : n->fpad, p.n_chunks = p.cin / 32;
+        p.fpad = n->fpad, p.nmt = n->fpad / 16;
+        p.mode = c % 2 == 0 ? WIDE_MODE_CONV1 : c + 1 < nc ? WIDE_MODE_CONV2 : WIDE_MODE_LAST;
+        const bool in_a = c % 2 == 1; // conv c reads what conv c - 1 wrote: even convs write opa, odd ones opb
+        p.a_hi = in_a ? n->opa_hi : n->opb_hi, p.a_lo = in_a ? n->opa_lo : n->opb_lo;
+        p.o_hi = in_a ? n->opb_hi : n->opa_hi, p.o_lo = in_a ? n->opb_lo : n->opa_lo;
+        p.w = n->w_wide + n->w_off[c], p.epi = n->epi_wide + (size_t)c * 4 * n->fpad, p.x = n->x_wide;
+        s = az_launch_wide_conv(n->d.device, x3, p, st);
+    }
+    if (s != hipSuccess) {
+        n->err = std::string("wide tower launch: ") + hipGetErrorString(s);
+        return AZ_E_HIP;
+    }
+    HeadParams hp;
+    hp.HW = HW, hp.A = n->d.num_actions, hp.n_ot = n->n_ot, hp.K = HW * n->fpad, hp.ksteps = n->fc_ksteps, hp.n_boards = n_boards;
+    hp.x = n->opb_hi, hp.x_lo = n->opb_lo, hp.fc_w = n->fc_w, hp.fc_w_lo = n->fc_w_lo, hp.fc_b = n->fc_b;
+    hp.priors = priors, hp.values = values;
+    NCHK(n, az_launch_head(n->d.device, x3, hp, n_boards, n->lds_head, n->logits, st));
+    return AZ_OK;
+}
+
 extern "C" int az_net_reserve(az_net *n, int32_t max_boards) {
     if (!n || max_boards < 1) return AZ_E_INVALID;
     NCHK(n, hipSetDevice(n->d.device));
+    if (n->wide) return wide_reserve(n, max_boards);
     if (n->xout) (void)hipFree(n->xout);
     n->xout = nullptr;
     // (+ 64 bytes: the last k-step of fc1 may reach past a board's row - into the next board's, times zero weights)
@@ -639,6 +874,10 @@ static NetDispatch net_dispatch(const az_net *n, int n_boards) {
 
 extern "C" int az_net_issued_mfma_per_board(const az_net *n, int32_t n_boards, double *out) {
     if (!n || !out || n_boards < 1) return AZ_E_INVALID;
+    if (n->wide) {
+        *out = wide_mfma_per_board(n, n_boards);
+        return AZ_OK;
+    }
     const int n_convs = 2 * n->d.n_blocks, nks = n->r3 < 16 ? 15 : AZ_NET_KSTEPS;
     const NetDispatch dp = net_dispatch(n, n_boards);
     const double head = (double)n->n_ot * n->fc_ksteps / 16.0; // one MFMA per (output tile, k-step) per 16 boards
@@ -665,6 +904,7 @@ extern "C" int az_net_issued_mfma_per_board(const az_net *n, int32_t n_boards, d
 
 extern "C" const char *az_net_kernel_label(const az_net *n, int32_t n_boards) {
     if (!n) return "";
+    if (n->wide) return n->label_wide.c_str();
     const bool big = n->n_ot > OTG;
     const NetDispatch dp = net_dispatch(n, n_boards < 1 ? n->max_boards : n_boards);
     if (n->precision == AZ_NET_PREC_F16X3) {
@@ -686,6 +926,7 @@ extern "C" int az_net_forward(az_net *n, const float *obs, float *priors, float 
     }
     NCHK(n, hipSetDevice(n->d.device)); // the launch must pair `stream` with the device the net lives on
     hipStream_t st = (hipStream_t)stream;
+    if (n->wide) return wide_forward(n, obs, priors, values, n_boards, st);
     HeadParams hp;
     hp.HW = n->d.rows * n->d.cols;
     hp.A = n->d.num_actions;
@@ -809,6 +1050,17 @@ extern "C" int az_net_read_tower(az_net *n, float *out, int32_t n_boards) {
     if (!n || !out || n_boards < 1 || n_boards > n->max_boards) return AZ_E_INVALID;
     NCHK(n, hipSetDevice(n->d.device));
     NCHK(n, hipDeviceSynchronize());
+    if (n->wide) { // out: [n_boards][H*W][fpad], hi + lo / 2048 of the tower output
+        const size_t cnt = (size_t)n_boards * n->d.rows * n->d.cols * n->fpad;
+        std::vector<_Float16> h(cnt);
+        NCHK(n, hipMemcpy(h.data(), n->opb_hi, cnt * 2, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < cnt; i++) out[i] = (float)h[i];
+        if (n->precision == AZ_NET_PREC_F16X3) {
+            NCHK(n, hipMemcpy(h.data(), n->opb_lo, cnt * 2, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < cnt; i++) out[i] += (float)h[i] * (1.0f / 2048.0f);
+        }
+        return AZ_OK;
+    }
     // out: [n_boards][H*W][AZ_NET_XOUT_C] whatever the stride on the device (channels past it read as zero)
     const size_t cells = (size_t)n_boards * n->d.rows * n->d.cols, cnt = cells * n->xc;
     const int nc = n->xc < AZ_NET_XOUT_C ? n->xc : AZ_NET_XOUT_C;

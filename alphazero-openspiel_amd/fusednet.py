@@ -67,48 +67,77 @@ def _pack_conv(w3x3):
     return hi.view(np.uint16), lo.view(np.uint16)
 
 
+def fold_net(net):
+    """Net in eval mode -> its eval-mode BatchNorm folded into plain float64 arrays (PyTorch layouts).  Both device paths start
+    from these: pack_net (the tuned kernels' packed layouts) and the wide path's az_net_wide_desc (include/az_net.h).
+
+      conv_w  [2*nb][F][C][3][3]  C = max(F, in_planes); conv 2b = block b's conv1 with bn2 folded in, 2b+1 = its conv2
+      conv_b  [2*nb][F]           block 1's conv2 bias includes the 1x1 skip conv's bias
+      bn1_scale, bn1_shift [nb][C]  bn1 of block b as scale * x + shift (block 1: over the in_planes input planes)
+      skip_w  [F][in_planes]      block 1's skip: the 1x1 conv, or the identity when in_planes == F
+      fc_w [A+1][F*H*W] (column c*H*W + pos), fc_b [A+1]"""
+    if net.training:
+        raise ValueError("folding uses BatchNorm running statistics: call net.eval() first (or pass a copy)")
+    F_ = net.n_filts
+    blocks = [getattr(net, "resblock%d" % (i + 1)) for i in range(getattr(net, "n_blocks", 5))]
+    H, W, A = net.height, net.width, net.num_distinct_actions
+    cin0 = net.num_filters_input
+    nb, C_ = len(blocks), max(F_, cin0)
+    conv_w = np.zeros((2 * nb, F_, C_, 3, 3), dtype=np.float64)
+    conv_b = np.zeros((2 * nb, F_), dtype=np.float64)
+    bn1_scale = np.zeros((nb, C_), dtype=np.float64)
+    bn1_shift = np.zeros((nb, C_), dtype=np.float64)
+    skip_w = np.zeros((F_, cin0), dtype=np.float64)
+    for b, blk in enumerate(blocks):
+        s1, t1 = _bn_affine(blk.bn1)
+        bn1_scale[b, :len(s1)], bn1_shift[b, :len(t1)] = s1, t1
+        s2, t2 = _bn_affine(blk.bn2)
+        w1 = blk.conv1.weight.detach().double().numpy() * s2[:, None, None, None]
+        conv_w[2 * b, :, :w1.shape[1]] = w1
+        conv_b[2 * b] = blk.conv1.bias.detach().double().numpy() * s2 + t2
+        conv_w[2 * b + 1, :, :F_] = blk.conv2.weight.detach().double().numpy()
+        b2 = blk.conv2.bias.detach().double().numpy().copy()
+        if blk.use_1x1conv:
+            if b != 0:
+                raise ValueError("a 1x1 skip conv is only supported on the first block")
+            skip_w[:] = blk.conv3.weight.detach().numpy()[:, :, 0, 0]
+            b2 = b2 + blk.conv3.bias.detach().double().numpy()
+        elif b == 0:  # identity skip on block 1 (in_planes == n_filters)
+            skip_w[:] = np.eye(F_, cin0, dtype=np.float32)
+        conv_b[2 * b + 1] = b2
+    return {"conv_w": conv_w, "conv_b": conv_b, "bn1_scale": bn1_scale, "bn1_shift": bn1_shift, "skip_w": skip_w,
+            "fc_w": net.fc1.weight.detach().double().numpy(), "fc_b": net.fc1.bias.detach().double().numpy(),
+            "rows": H, "cols": W, "in_planes": cin0, "n_filters": F_, "n_blocks": nb, "num_actions": A}
+
+
 def pack_net(net):
     """Net (alphazero_openspiel_amd.network.Net or the reference's Net) -> dict of packed numpy arrays."""
     if net.training:
         raise ValueError("pack_net folds BatchNorm running statistics: call net.eval() first (or pass a copy)")
     F_ = net.n_filts
-    blocks = [getattr(net, "resblock%d" % (i + 1)) for i in range(getattr(net, "n_blocks", 5))]
-    H, W, A = net.height, net.width, net.num_distinct_actions
     cin0 = net.num_filters_input
     if F_ > CPAD or cin0 > 4:
         raise ValueError("fused net supports n_filters <= %d and <= 4 input planes" % CPAD)
-    nb = len(blocks)
+    f = fold_net(net)
+    H, W, A, nb = f["rows"], f["cols"], f["num_actions"], f["n_blocks"]
     conv_w = np.zeros((2 * nb, KSTEPS, 4, 64, 8), dtype=np.uint16)
     conv_w_lo = np.zeros_like(conv_w)
     epi = np.zeros((2 * nb, 3, 64), dtype=np.float32)
     epi[:, 1, :] = 1.0
-    s_in, t_in = _bn_affine(blocks[0].bn1)
     in_affine = np.zeros((2, 8), dtype=np.float32)
-    in_affine[0, :cin0], in_affine[1, :cin0] = s_in, t_in
+    in_affine[0, :cin0], in_affine[1, :cin0] = f["bn1_scale"][0, :cin0], f["bn1_shift"][0, :cin0]
     skip_w = np.zeros((64, 4), dtype=np.float32)
-    for b, blk in enumerate(blocks):
-        s2, t2 = _bn_affine(blk.bn2)
-        w1 = blk.conv1.weight.detach().double().numpy() * s2[:, None, None, None]
-        b1 = blk.conv1.bias.detach().double().numpy() * s2 + t2
-        conv_w[2 * b], conv_w_lo[2 * b] = _pack_conv(w1)
-        epi[2 * b, 0, :F_] = b1
-        w2 = blk.conv2.weight.detach().double().numpy()
-        b2 = blk.conv2.bias.detach().double().numpy().copy()
-        if blk.use_1x1conv:
-            if b != 0:
-                raise ValueError("a 1x1 skip conv is only supported on the first block")
-            skip_w[:F_, :cin0] = blk.conv3.weight.detach().numpy()[:, :, 0, 0]
-            b2 = b2 + blk.conv3.bias.detach().double().numpy()
-        elif b == 0:  # identity skip on block 1 (in_planes == n_filters)
-            skip_w[:F_, :cin0] = np.eye(F_, cin0, dtype=np.float32)
-        conv_w[2 * b + 1], conv_w_lo[2 * b + 1] = _pack_conv(w2)
-        epi[2 * b + 1, 0, :F_] = b2
+    skip_w[:F_, :cin0] = f["skip_w"]
+    for b in range(nb):
+        conv_w[2 * b], conv_w_lo[2 * b] = _pack_conv(f["conv_w"][2 * b, :, :cin0 if b == 0 else F_])
+        epi[2 * b, 0, :F_] = f["conv_b"][2 * b]
+        conv_w[2 * b + 1], conv_w_lo[2 * b + 1] = _pack_conv(f["conv_w"][2 * b + 1, :, :F_])
+        epi[2 * b + 1, 0, :F_] = f["conv_b"][2 * b + 1]
         if b + 1 < nb:
-            s1, t1 = _bn_affine(blocks[b + 1].bn1)
-            epi[2 * b + 1, 1, :F_], epi[2 * b + 1, 2, :F_] = s1, t1
+            epi[2 * b + 1, 1, :F_], epi[2 * b + 1, 2, :F_] = f["bn1_scale"][b + 1, :F_], f["bn1_shift"][b + 1, :F_]
     # fc1: [A+1, F*H*W] with column index c*HW + pos  ->  Wfc'[o][pos*64 + c]
     HW = H * W
-    wfc = net.fc1.weight.detach().double().numpy().reshape(A + 1, F_, HW)
+    wfc = f["fc_w"].reshape(A + 1, F_, HW)
     n_ot = (A + 1 + 15) // 16
     dense = np.zeros((n_ot * 16, HW, XOUT_C), dtype=np.float64)
     dense[:A + 1, :, :F_] = wfc.transpose(0, 2, 1)
@@ -122,7 +151,7 @@ def pack_net(net):
         fc_w64[ot] = dense[rows, kidx]
     fc_w, fc_w_lo = split_fp16(fc_w64)
     fc_b = np.zeros(n_ot * 16, dtype=np.float32)
-    fc_b[:A + 1] = net.fc1.bias.detach().numpy()
+    fc_b[:A + 1] = f["fc_b"]
     return {"conv_w": conv_w, "conv_epi": epi, "in_affine": in_affine, "skip_w": skip_w,
             "fc_w": fc_w.view(np.uint16), "fc_b": fc_b, "conv_w_lo": conv_w_lo, "fc_w_lo": fc_w_lo.view(np.uint16),
             "rows": H, "cols": W, "in_planes": cin0, "n_filters": F_, "n_blocks": nb, "num_actions": A}
@@ -207,6 +236,56 @@ def emulate_forward(packed, obs, round_fp16=True, split=False):
     return e / e.sum(1, keepdims=True), np.tanh(logits[:, A]), tower
 
 
+def wide_fpad(n_filters):
+    """Channel stride of the wide path's activations and tower output (az_net_read_tower)."""
+    return (n_filters + 31) // 32 * 32
+
+
+def wide_desc(f, device, precision):
+    """fold_net arrays -> (az_net_wide_desc, the float32 arrays it points to: keep them alive until az_net_create_wide returns)."""
+    from . import _lib
+    d = _lib.AzNetWideDesc()
+    d.struct_size = C.sizeof(_lib.AzNetWideDesc)
+    d.rows, d.cols, d.in_planes = f["rows"], f["cols"], f["in_planes"]
+    d.n_filters, d.n_blocks, d.num_actions = f["n_filters"], f["n_blocks"], f["num_actions"]
+    d.device, d.precision = device, precision
+    keep = []
+    for k in ("conv_w", "conv_b", "bn1_scale", "bn1_shift", "skip_w", "fc_w", "fc_b"):
+        a = np.ascontiguousarray(f[k], dtype=np.float32)
+        keep.append(a)
+        setattr(d, k, a.ctypes.data_as(C.POINTER(C.c_float)))
+    return d, keep
+
+
+def fold_forward(f, obs):
+    """float64 numpy forward of Net from the fold_net arrays: (priors [B, A], values [B], tower [B, H*W, F])."""
+    H, W, A, nb, F_ = f["rows"], f["cols"], f["num_actions"], f["n_blocks"], f["n_filters"]
+    x0 = np.asarray(obs, dtype=np.float64)
+    B, cin0 = x0.shape[0], x0.shape[1]
+    lrelu = lambda a: np.where(a > 0, a, LRELU * a)
+
+    def conv(a, w, bias):  # a [B, Cin, H, W], w [F, Cin, 3, 3]
+        ap = np.pad(a, ((0, 0), (0, 0), (1, 1), (1, 1)))
+        out = np.zeros((B, w.shape[0], H, W))
+        for ky in range(3):
+            for kx in range(3):
+                out += np.einsum("bchw,fc->bfhw", ap[:, :, ky:ky + H, kx:kx + W], w[:, :, ky, kx])
+        return out + bias[None, :, None, None]
+
+    x = np.einsum("bchw,fc->bfhw", x0, f["skip_w"])
+    a = lrelu(f["bn1_scale"][0, :cin0, None, None] * x0 + f["bn1_shift"][0, :cin0, None, None])
+    for b in range(nb):
+        cin = cin0 if b == 0 else F_
+        if b > 0:
+            a = lrelu(f["bn1_scale"][b, :F_, None, None] * x + f["bn1_shift"][b, :F_, None, None])
+        u = lrelu(conv(a, f["conv_w"][2 * b, :, :cin], f["conv_b"][2 * b]))
+        x = x + conv(u, f["conv_w"][2 * b + 1, :, :F_], f["conv_b"][2 * b + 1])
+    logits = x.reshape(B, -1) @ f["fc_w"].T + f["fc_b"][None, :]
+    lp = logits[:, :A]
+    e = np.exp(lp - lp.max(1, keepdims=True))
+    return e / e.sum(1, keepdims=True), np.tanh(logits[:, A]), x.reshape(B, F_, H * W).transpose(0, 2, 1)
+
+
 # Arithmetic of the matrix products (include/az_net.h): "f16" = fp16 operands, one MFMA per product; "f32x" = fp32-grade,
 # every operand a (hi, lo) pair of fp16 numbers, three MFMAs per product (AZ_NET_PREC_F16X3)
 PRECISIONS = ("f16", "f32x")
@@ -227,14 +306,40 @@ class FusedNet:
             raise RuntimeError("FusedNet needs a HIP device; there is no CPU path")
         self.device_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         self.device = torch.device("cuda", self.device_index)
-        self.packed = pack_net(copy.deepcopy(net).cpu().eval())  # never move or switch the caller's module
-        p = self.packed
+        net = copy.deepcopy(net).cpu().eval()  # never move or switch the caller's module
+        # Routing: the tuned kernels (pack_net + az_net_create) whenever they take the net; the general layer-by-layer path
+        # (az_net_create_wide) when pack_net refuses it (more than CPAD filters) or az_net_create does (conv weight range,
+        # LDS budget: AZ_E_INVALID; a refused az_net_create frees what it allocated)
+        self.wide = net.n_filts > CPAD
+        self._h = C.c_void_p()
+        if not self.wide:
+            self.packed = pack_net(net)
+            rc = self._create_narrow(self.packed)
+            if rc == -1:  # AZ_E_INVALID
+                self.wide = True
+            elif rc != 0:
+                raise RuntimeError("az_net_create failed (%d): %s" % (rc, self.lib.az_net_last_error(None).decode()))
+        if self.wide:
+            self.packed = None
+            self.folded = fold_net(net)
+            rc = self._create_wide(self.folded)
+            if rc != 0:
+                raise RuntimeError("az_net_create_wide failed (%d): %s" % (rc, self.lib.az_net_last_error(None).decode()))
+        p = self.packed or self.folded
+        self._check(self.lib.az_net_reserve(self._h, int(max_boards)))
+        self.max_boards = int(max_boards)
+        self.A = p["num_actions"]
+        self.obs_shape = (p["in_planes"], p["rows"], p["cols"])
+        self.tower_shape = (p["rows"] * p["cols"], wide_fpad(p["n_filters"]) if self.wide else XOUT_C)
+
+    def _create_narrow(self, p):
+        from . import _lib
         d = _lib.AzNetDesc()
         d.struct_size = C.sizeof(_lib.AzNetDesc)
         d.rows, d.cols, d.in_planes = p["rows"], p["cols"], p["in_planes"]
         d.n_filters, d.n_blocks, d.num_actions = p["n_filters"], p["n_blocks"], p["num_actions"]
         d.device = self.device_index
-        d.precision = _lib.NET_PREC[precision]
+        d.precision = _lib.NET_PREC[self.precision]
         self._keep = [np.ascontiguousarray(p[k]) for k in ("conv_w", "conv_epi", "in_affine", "fc_w", "fc_b", "skip_w",
                                                            "conv_w_lo", "fc_w_lo")]
         d.conv_w_lo = self._keep[6].ctypes.data_as(C.POINTER(C.c_uint16))
@@ -245,14 +350,12 @@ class FusedNet:
         d.fc_w = self._keep[3].ctypes.data_as(C.POINTER(C.c_uint16))
         d.fc_b = self._keep[4].ctypes.data_as(C.POINTER(C.c_float))
         d.skip_w = self._keep[5].ctypes.data_as(C.POINTER(C.c_float))
-        self._h = C.c_void_p()
-        rc = self.lib.az_net_create(C.byref(d), C.byref(self._h))
-        if rc != 0:
-            raise RuntimeError("az_net_create failed (%d): %s" % (rc, self.lib.az_net_last_error(None).decode()))
-        self._check(self.lib.az_net_reserve(self._h, int(max_boards)))
-        self.max_boards = int(max_boards)
-        self.A = p["num_actions"]
-        self.obs_shape = (p["in_planes"], p["rows"], p["cols"])
+        return self.lib.az_net_create(C.byref(d), C.byref(self._h))
+
+    def _create_wide(self, f):
+        from . import _lib
+        d, self._keep = wide_desc(f, self.device_index, _lib.NET_PREC[self.precision])
+        return self.lib.az_net_create_wide(C.byref(d), C.byref(self._h))
 
     def _check(self, rc):
         if rc < 0:
@@ -297,6 +400,8 @@ class FusedNet:
         return self.lib.az_net_kernel_label(self._h, int(n_boards or self.max_boards)).decode()
 
     def read_tower(self, n_boards):
-        out = np.zeros((n_boards, self.packed["rows"] * self.packed["cols"], XOUT_C), dtype=np.float32)
+        """Tower output of the last forward: [n_boards, H*W, 64], or [n_boards, H*W, Fpad] on the wide path (Fpad = n_filters
+        rounded up to a multiple of 32)."""
+        out = np.zeros((n_boards,) + self.tower_shape, dtype=np.float32)
         self._check(self.lib.az_net_read_tower(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), n_boards))
         return out

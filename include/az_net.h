@@ -62,9 +62,38 @@ typedef struct az_net_desc {
     const uint16_t *fc_w_lo;
 } az_net_desc;
 
+/* The general path (az_net_create_wide): any net of 1..AZ_NET_WIDE_MAX_FILTERS filters, conv weights of any finite magnitude, run
+ * layer by layer (one kernel per conv, activations in device memory between convs).  The descriptor holds PLAIN fp32 arrays in
+ * PyTorch layouts, eval-mode BatchNorm already folded (fusednet.fold_net): bn2 of every block folded into its conv1's weights and
+ * bias; bn1 kept as a per-channel scale / shift.  C = max(n_filters, in_planes); conv 0 (block 1's conv1) reads channels
+ * < in_planes of its row, every other conv channels < n_filters.  az_net_create_wide decides every device layout. */
+#define AZ_NET_WIDE_MAX_FILTERS 256
+
+typedef struct az_net_wide_desc {
+    int32_t struct_size;
+    int32_t rows, cols;     /* rows * cols <= 64 */
+    int32_t in_planes;      /* 1..4 */
+    int32_t n_filters;      /* 1..AZ_NET_WIDE_MAX_FILTERS */
+    int32_t n_blocks;
+    int32_t num_actions;    /* A <= 768; fc1 has A+1 outputs */
+    int32_t device;
+    int32_t precision;      /* AZ_NET_PREC_* */
+    int32_t reserved;
+    /* host pointers (copied by az_net_create_wide) */
+    const float *conv_w;    /* [2*n_blocks][n_filters][C][3][3]: conv 2b = block b's conv1 (bn2 folded in), conv 2b+1 = its conv2 */
+    const float *conv_b;    /* [2*n_blocks][n_filters]; block 1's conv2 bias includes the 1x1 skip conv's bias */
+    const float *bn1_scale; /* [n_blocks][C]: bn1 of block b as y = scale * x + shift (block 1: over the in_planes input planes) */
+    const float *bn1_shift; /* [n_blocks][C] */
+    const float *skip_w;    /* [n_filters][in_planes]: block 1's 1x1 skip conv (identity when in_planes == n_filters) */
+    const float *fc_w;      /* [A+1][n_filters*rows*cols], column c*rows*cols + pos (flattened NCHW, network.py:61) */
+    const float *fc_b;      /* [A+1] */
+} az_net_wide_desc;
+
 typedef struct az_net az_net;
 
 int az_net_create(const az_net_desc *desc, az_net **out);
+/* The same handle type as az_net_create: every az_net_* call below works on it. */
+int az_net_create_wide(const az_net_wide_desc *desc, az_net **out);
 int az_net_destroy(az_net *n);
 const char *az_net_last_error(const az_net *n);
 
@@ -77,7 +106,8 @@ int az_net_forward(az_net *n, const float *obs, float *priors, float *values, in
 int az_net_reserve(az_net *n, int32_t max_boards);
 
 /* Debug/parity: copy the tower output of the last forward (pre-fc residual stream, fp16 as float32,
- * [n_boards][H*W][64]) to a host buffer.  Synchronises the device. */
+ * [n_boards][H*W][64]) to a host buffer.  Synchronises the device.  A handle of az_net_create_wide writes
+ * [n_boards][H*W][Fpad], Fpad = n_filters rounded up to a multiple of 32 (channels >= n_filters read as zero). */
 int az_net_read_tower(az_net *n, float *out, int32_t n_boards);
 
 /* Measurement aid (bench.py's roofline.frac_issued): the number of v_mfma_f32_16x16x32_f16 instructions (16384 FLOP each,
