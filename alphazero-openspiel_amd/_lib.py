@@ -100,6 +100,7 @@ PROTOTYPES = [
     ("az_engine_reset", C.c_int, [_vp, C.c_uint64, C.c_int64, _vp]),
     ("az_engine_set_injected_rng", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64]),
     ("az_engine_set_start_prefix", C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int32]),
+    ("az_engine_set_start_positions", C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.c_int64]),
     ("az_engine_advance", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     ("az_engine_advance_slots", C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     ("az_engine_compact_rows", C.c_int, [_vp, C.POINTER(C.c_int32), _vp]),
@@ -112,6 +113,8 @@ PROTOTYPES = [
     ("az_engine_export", C.c_int, [_vp, C.POINTER(AzExampleView), _vp]),
     ("az_engine_export_device_bytes", C.c_int64, [_vp]),
     ("az_engine_export_device", C.c_int, [_vp, _vp, C.c_int64, _vp]),
+    ("az_engine_roots_device_bytes", C.c_int64, [_vp]),
+    ("az_engine_export_roots_device", C.c_int, [_vp, _vp, C.c_int64, _vp]),
     ("az_engine_read_root", C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double)]),

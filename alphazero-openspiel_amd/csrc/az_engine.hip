@@ -588,6 +588,12 @@ __device__ __forceinline__ bool finish_game_take_next(const Params &p, int g, in
     }
     sr.gid = (int)nxt;
     sr.rs = p.start;
+    if (p.starts) { // a start position per game id (az_engine_set_start_positions)
+        const AzState *s = p.starts + nxt;
+        sr.rs.bb0 = rfl64(s->bb0);
+        sr.rs.bb1 = rfl64(s->bb1);
+        sr.rs.ply = rfl(s->ply);
+    }
     sr.sims = 0;
     return true;
 }
@@ -1379,9 +1385,10 @@ __global__ void az_reset_kernel(Params p) {
                  : ((p.arena_agent != AZ_ARENA_SELF_PLAY && ((p.start.ply ^ g ^ p.arena_flip) & 1)) ? PH_OPPONENT
                                                                                        : (p.use_dirichlet ? PH_NEED_ROOT : PH_RUN));
     p.gid[g] = active ? g : -1;
-    p.bb0[g] = p.start.bb0;
-    p.bb1[g] = p.start.bb1;
-    p.ply[g] = p.start.ply;
+    const AzState s0 = (p.starts && active) ? p.starts[g] : p.start; // game id g (manual_moves engines only: see the phase above)
+    p.bb0[g] = s0.bb0;
+    p.bb1[g] = s0.bb1;
+    p.ply[g] = s0.ply;
     p.sims[g] = 0;
     p.which[g] = g | (!p.keep_tree || p.manual_moves ? AZ_SELECT_PUCT
                       : (p.start.ply >= (p.arena_agent == AZ_ARENA_SELF_PLAY ? 1 : 2) ? p.select_rule : AZ_SELECT_PUCT)) << 30; // pool g, start_rule
@@ -1455,6 +1462,7 @@ extern "C" int az_engine_destroy(az_engine *e) {
     if (e->d_etas) (void)hipFree(e->d_etas);
     if (e->d_us) (void)hipFree(e->d_us);
     if (e->d_actions) (void)hipFree(e->d_actions);
+    if (e->d_starts) (void)hipFree(e->d_starts);
     delete e;
     return AZ_OK;
 }
@@ -1670,6 +1678,10 @@ extern "C" int az_engine_reset(az_engine *e, uint64_t seed, int64_t n_games, voi
         e->err = "n_games must be in [1, max_games]";
         return AZ_E_INVALID;
     }
+    if (e->p.starts && n_games > e->starts_n) {
+        e->err = "n_games exceeds the games given to az_engine_set_start_positions";
+        return AZ_E_INVALID;
+    }
     HIPCHK(e, hipSetDevice(e->cfg.device));
     e->p.seed = seed;
     e->p.n_games = n_games;
@@ -1706,44 +1718,91 @@ extern "C" int az_engine_set_injected_rng(az_engine *e, const double *etas, cons
     return AZ_OK;
 }
 
-extern "C" int az_engine_set_start_prefix(az_engine *e, const int32_t *actions, int32_t n) {
-    if (!e || (n > 0 && !actions)) return AZ_E_INVALID;
-    AzState s;
+// Replay an action prefix from the initial position on the host, with the legality checks of the game: 0 = ok (s = the position),
+// 1 = an illegal action, 2 = the prefix ends the game.
+static int replay_prefix(const az_engine *e, const int32_t *actions, int32_t n, AzState &s) {
     float ret0 = 0.f;
     int term = 0;
     if (e->cfg.game == AZ_GAME_CONNECT_FOUR) {
         az_init_state<AZG_CONNECT_FOUR>(s, e->p.geom);
         for (int i = 0; i < n && !term; i++) {
-            if (actions[i] < 0 || actions[i] > 6 || !((az_c4_legal_mask(s) >> actions[i]) & 1u)) {
-                e->err = "illegal prefix action";
-                return AZ_E_INVALID;
-            }
+            if (actions[i] < 0 || actions[i] > 6 || !((az_c4_legal_mask(s) >> actions[i]) & 1u)) return 1;
             term = az_apply<AZG_CONNECT_FOUR>(s, e->p.geom, actions[i], &ret0);
         }
     } else {
         az_init_state<AZG_BREAKTHROUGH>(s, e->p.geom);
         for (int i = 0; i < n && !term; i++) {
             int a = actions[i];
-            if (a < 0 || a >= e->p.A) {
-                e->err = "illegal prefix action";
-                return AZ_E_INVALID;
-            }
+            if (a < 0 || a >= e->p.A) return 1;
             int d = (a >> 1) % 6, cell = (a >> 1) / 6, me = s.ply & 1;
             uint32_t mv = az_bt_cell_moves(s, e->p.geom, cell);
             int dd = d - (me ? 3 : 0);
-            if (dd < 0 || dd > 2 || !(mv & (1u << dd)) || (int)((mv >> (4 + dd)) & 1u) != (a & 1)) {
-                e->err = "illegal prefix action";
-                return AZ_E_INVALID;
-            }
+            if (dd < 0 || dd > 2 || !(mv & (1u << dd)) || (int)((mv >> (4 + dd)) & 1u) != (a & 1)) return 1;
             term = az_apply<AZG_BREAKTHROUGH>(s, e->p.geom, a, &ret0);
         }
     }
-    if (term) {
-        e->err = "prefix ends the game";
+    return term ? 2 : 0;
+}
+
+extern "C" int az_engine_set_start_prefix(az_engine *e, const int32_t *actions, int32_t n) {
+    if (!e || (n > 0 && !actions)) return AZ_E_INVALID;
+    AzState s;
+    int bad = replay_prefix(e, actions, n, s);
+    if (bad) {
+        e->err = bad == 1 ? "illegal prefix action" : "prefix ends the game";
         return AZ_E_INVALID;
     }
     e->p.start = s;
+    e->p.starts = nullptr; // one prefix for every game again
+    e->starts_n = 0;
     e->reset_done = false; // caller must reset again so that slots pick the new start up
+    return AZ_OK;
+}
+
+extern "C" int az_engine_set_start_positions(az_engine *e, const int32_t *actions, const int32_t *lengths, int64_t stride,
+                                             int64_t n_games) {
+    if (!e) return AZ_E_INVALID;
+    if (!e->cfg.manual_moves) {
+        e->err = "az_engine_set_start_positions needs an engine created with manual_moves = 1: self-play and arena engines keep "
+                 "ONE start ply for the record offset, the value targets, the replay append and the side assignment";
+        return AZ_E_INVALID;
+    }
+    if (!lengths || n_games < 1 || n_games > e->cfg.max_games || stride < 0) {
+        e->err = "az_engine_set_start_positions: n_games must be in [1, max_games], lengths non-null, stride >= 0";
+        return AZ_E_INVALID;
+    }
+    std::vector<AzState> tab((size_t)n_games);
+    for (int64_t i = 0; i < n_games; i++) {
+        const int32_t n = lengths[i];
+        if (n < 0 || n > stride || (n > 0 && !actions)) {
+            e->err = "az_engine_set_start_positions: game " + std::to_string(i) + ": prefix length " + std::to_string(n) +
+                     " outside [0, stride]";
+            return AZ_E_INVALID;
+        }
+        int bad = replay_prefix(e, n > 0 ? actions + i * stride : nullptr, n, tab[(size_t)i]);
+        if (bad) {
+            e->err = "az_engine_set_start_positions: game " + std::to_string(i) +
+                     (bad == 1 ? ": illegal prefix action" : ": prefix ends the game");
+            return AZ_E_INVALID;
+        }
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, hipDeviceSynchronize()); // a reset of the previous chunk may still be reading the table
+    if (n_games > e->starts_cap) {
+        if (e->d_starts) (void)hipFree(e->d_starts);
+        e->d_starts = nullptr;
+        e->starts_cap = 0;
+        e->p.starts = nullptr;
+        e->starts_n = 0;
+        HIPCHK(e, hipMalloc((void **)&e->d_starts, (size_t)n_games * sizeof(AzState)));
+        e->starts_cap = n_games;
+    }
+    HIPCHK(e, hipMemcpy(e->d_starts, tab.data(), (size_t)n_games * sizeof(AzState), hipMemcpyHostToDevice));
+    if (e->cfg.game == AZ_GAME_CONNECT_FOUR) az_init_state<AZG_CONNECT_FOUR>(e->p.start, e->p.geom); // supersedes a single prefix
+    else az_init_state<AZG_BREAKTHROUGH>(e->p.start, e->p.geom);
+    e->p.starts = e->d_starts;
+    e->starts_n = n_games;
+    e->reset_done = false; // caller must reset again so that slots pick the new starts up
     return AZ_OK;
 }
 
@@ -2119,6 +2178,139 @@ extern "C" int az_engine_export_device(az_engine *e, void *dev_buf, int64_t byte
                           e->p.rec_child_visits, e->p.rec_value};
     const size_t sizes[8] = {n * 4, n * 4, n * mp * 16, n * mp * 2, n * mp, n * mp * mc * 2, n * mp * mc * 4, n * mp * 8};
     for (int i = 0; i < 8; i++) HIPCHK(e, hipMemcpyAsync(b + off[i], src[i], sizes[i], hipMemcpyDeviceToDevice, st));
+    return AZ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Every slot's root in one buffer (layout: include/az_engine.h, az_engine_export_roots_device).  A wave per slot: the root's
+// children are one contiguous run of 32-byte nodes, lane i takes child i (two 16-byte loads per lane, a wave reads the run end
+// to end) and the four child arrays are written lane-contiguously.  Rows beyond n_children are written too (action -1, zeros),
+// so the buffer's contents depend on the trees alone.  Runs once per search (or every few ticks), not per tick.
+#define AZ_ROOTS_ARRAYS 12
+static void roots_offsets(size_t G, size_t mc, size_t off[AZ_ROOTS_ARRAYS + 1]) {
+    const size_t sizes[AZ_ROOTS_ARRAYS] = {16, G * 4, G * 4, G * 4, G * 4, G * 4, G * 4, G * 8, G * mc * 4, G * mc * 4, G * mc * 8, G * mc * 8};
+    off[0] = 0;
+    for (int i = 0; i < AZ_ROOTS_ARRAYS; i++) off[i + 1] = off[i] + ((sizes[i] + 15) & ~(size_t)15);
+}
+struct RootsOut {
+    int *header, *game_id, *phase, *ply, *sims_done, *n_children;
+    uint32_t *root_n;
+    double *root_q;
+    int *child_action;
+    uint32_t *child_n;
+    double *child_q, *child_p;
+};
+
+__global__ __launch_bounds__(256) void az_export_roots_kernel(Params p, RootsOut o) {
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= p.G) return;
+    const int ph = rfl(p.phase[g]);
+    const int pool = rfl(p.which[g]) & POOL_MASK;
+    const uint32_t root = rflu(p.root[g]);
+    const AzNode *nd = p.nodes + (size_t)pool * p.cap;
+    uint32_t rn = 0, c0 = NONE32;
+    int nc = 0;
+    double rq = 0.0;
+    if (pool < p.G + p.n_spare && root < p.cap) { // (a slot's own words: never out of the pools)
+        rn = rflu(nd[root].N);
+        c0 = rflu(nd[root].C0);
+        nc = c0 == NONE32 ? 0 : (int)(rflu(nd[root].META) >> 16);
+        rq = nd[root].Q;
+        if (nc > p.maxc || c0 >= p.cap || c0 + (uint32_t)nc > p.cap) nc = 0;
+    }
+    if (lane == 0) {
+        o.game_id[g] = p.gid[g];
+        o.phase[g] = ph;
+        o.ply[g] = p.ply[g];
+        o.sims_done[g] = p.sims[g];
+        o.n_children[g] = nc;
+        o.root_n[g] = rn;
+        o.root_q[g] = rq;
+    }
+    for (int i = lane; i < p.maxc; i += 64) {
+        int act = -1;
+        uint32_t cn = 0;
+        double cq = 0.0, cp = 0.0;
+        if (i < nc) {
+            const AzNode c = nd[c0 + i];
+            act = (int)(c.META & 0xFFFFu);
+            cn = c.N;
+            cq = c.Q;
+            cp = c.P;
+        }
+        const size_t k = (size_t)g * p.maxc + i;
+        o.child_action[k] = act;
+        o.child_n[k] = cn;
+        o.child_q[k] = cq;
+        o.child_p[k] = cp;
+    }
+}
+// The header, by one workgroup launched behind the export on the same stream: it counts the phases the export wrote (no
+// counter to clear, no atomics: every replay of a captured graph writes all four words afresh).
+__global__ __launch_bounds__(1024) void az_roots_header_kernel(Params p, RootsOut o) {
+    __shared__ int s_cnt[16];
+    int n = 0;
+    for (int g = threadIdx.x; g < p.G; g += 1024) {
+        const int ph = o.phase[g];
+        n += ph == PH_SEARCH_DONE || ph == PH_IDLE;
+    }
+    for (int d = 32; d > 0; d >>= 1) n += __shfl_down(n, d);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < 16; w++) tot += s_cnt[w];
+        o.header[0] = tot;
+        o.header[1] = p.G;
+        o.header[2] = p.maxc;
+        o.header[3] = (int)*p.faults;
+    }
+}
+
+extern "C" int64_t az_engine_roots_device_bytes(const az_engine *e) {
+    if (!e) return AZ_E_INVALID;
+    size_t off[AZ_ROOTS_ARRAYS + 1];
+    roots_offsets((size_t)e->p.G, (size_t)e->p.maxc, off);
+    return (int64_t)off[AZ_ROOTS_ARRAYS];
+}
+
+extern "C" int az_engine_export_roots_device(az_engine *e, void *dev_buf, int64_t bytes, void *stream) {
+    if (!e || !dev_buf) return AZ_E_INVALID;
+    size_t off[AZ_ROOTS_ARRAYS + 1];
+    roots_offsets((size_t)e->p.G, (size_t)e->p.maxc, off);
+    if (bytes < (int64_t)off[AZ_ROOTS_ARRAYS]) {
+        e->err = "az_engine_export_roots_device: buffer smaller than az_engine_roots_device_bytes()";
+        return AZ_E_INVALID;
+    }
+    if (((uintptr_t)dev_buf & 15) != 0) {
+        e->err = "az_engine_export_roots_device: the buffer must be 16-byte aligned";
+        return AZ_E_INVALID;
+    }
+    if (!e->reset_done) {
+        e->err = "az_engine_export_roots_device before az_engine_reset";
+        return AZ_E_STATE;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    char *b = (char *)dev_buf;
+    RootsOut o;
+    o.header = (int *)(b + off[0]);
+    o.game_id = (int *)(b + off[1]);
+    o.phase = (int *)(b + off[2]);
+    o.ply = (int *)(b + off[3]);
+    o.sims_done = (int *)(b + off[4]);
+    o.n_children = (int *)(b + off[5]);
+    o.root_n = (uint32_t *)(b + off[6]);
+    o.root_q = (double *)(b + off[7]);
+    o.child_action = (int *)(b + off[8]);
+    o.child_n = (uint32_t *)(b + off[9]);
+    o.child_q = (double *)(b + off[10]);
+    o.child_p = (double *)(b + off[11]);
+    hipLaunchKernelGGL(az_export_roots_kernel, dim3((e->p.G + 3) / 4), dim3(256), 0, st, e->p, o);
+    HIPCHK(e, hipGetLastError());
+    hipLaunchKernelGGL(az_roots_header_kernel, dim3(1), dim3(1024), 0, st, e->p, o);
+    HIPCHK(e, hipGetLastError());
     return AZ_OK;
 }
 

@@ -93,6 +93,8 @@ struct Params {
     uint8_t *rec_nchild;
     uint32_t *rec_child_visits;
     double *rec_value;
+    // start position per GAME ID (az_engine_set_start_positions; manual_moves engines only): null = every game starts from `start`
+    const AzState *starts;
 };
 
 
@@ -108,6 +110,8 @@ struct az_engine {
     int *d_actions = nullptr;
     int64_t ticks = 0;
     int64_t inj_games = 0;
+    AzState *d_starts = nullptr; // the table behind p.starts (kept across az_engine_set_start_positions calls)
+    int64_t starts_cap = 0, starts_n = 0;
     bool rows_mapped = false; // az_engine_compact_rows has been called since the last reset
     int rows_live = 0;
     bool may_compact = false; // a pool cannot hold a whole game: re-rooting may have to compact (launches carry extra workgroups)

@@ -89,6 +89,7 @@ class SelfPlayEngine:
         self.obs_shape = (z.obs_planes, z.rows, z.cols)
         self.max_plies, self.max_children = z.max_plies, z.max_children
         self.start_history = []
+        self.start_histories = None  # set_start_positions: one history per game
         self.n_games = 0
 
     # ------------------------------------------------------------------ plumbing
@@ -129,6 +130,18 @@ class SelfPlayEngine:
         arr = (C.c_int32 * max(1, len(actions)))(*[int(a) for a in actions])
         self._check(self.lib.az_engine_set_start_prefix(self._h, arr, len(actions)))
         self.start_history = [int(a) for a in actions]
+        self.start_histories = None
+
+    def set_start_positions(self, histories):
+        """A start position per game (manual_moves engines): histories[i] is the action list that leads from the initial
+        position to game i's; reset(n <= len(histories)) afterwards.  An illegal action or a prefix that ends the game raises
+        EngineError naming the game's index.  May be called again (the next chunk); set_start_prefix returns to one prefix."""
+        actions, lengths, stride = pack_histories(histories)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.az_engine_set_start_positions(self._h, actions.ctypes.data_as(ip), lengths.ctypes.data_as(ip),
+                                                           stride, len(lengths)))
+        self.start_history = []  # injected draws are indexed by absolute ply (set_injected_rng(absolute_ply=True))
+        self.start_histories = [[int(a) for a in h] for h in histories]
 
     def set_injected_rng(self, etas, us, absolute_ply=False):
         """etas: per game, per ply, the Dirichlet draw (ragged lists ok); us: per game, per ply uniforms.  Lists are
@@ -261,6 +274,75 @@ class SelfPlayEngine:
         buf = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
         self._check(self.lib.az_engine_export_device(self._h, C.c_void_p(buf.data_ptr()), int(nbytes), self._stream()))
         return buf
+
+
+    def roots_device_bytes(self):
+        return int(self._check(self.lib.az_engine_roots_device_bytes(self._h)))
+
+    def alloc_roots(self):
+        """A uint8 device tensor that holds one root export (layout: roots_export_layout)."""
+        return torch.empty(self.roots_device_bytes(), dtype=torch.uint8, device=self.device)
+
+    def export_roots_device(self, buf):
+        """Pack every slot's root into `buf` (alloc_roots()) on the current stream: one kernel, no host synchronisation, may
+        be captured in a graph.  buf[:16] is the header: int32 {slots in phase 5 or idle, n_slots, max_children, error_flags}."""
+        if buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.device != self.device:
+            raise EngineError("expected a contiguous uint8 tensor on %s" % (self.device,))
+        self._check(self.lib.az_engine_export_roots_device(self._h, C.c_void_p(buf.data_ptr()), int(buf.numel()), self._stream()))
+        return buf
+
+    def read_roots(self, buf=None):
+        """The root of EVERY slot from one kernel and one device-to-host copy: dict of numpy arrays game_id / phase / ply /
+        sims_done / n_children [G], root_n [G] int64, root_q [G] float64, child_action [G, mc] int32 (-1 beyond n_children),
+        child_n [G, mc] int64, child_q / child_p [G, mc] float64, plus n_finished and error_flags from the header.  Row for
+        row what read_slot / read_root return for one slot per (synchronising) call."""
+        buf = self.export_roots_device(self.alloc_roots() if buf is None else buf)
+        return unpack_roots_export(buf.cpu().numpy(), self.G, self.max_children)
+
+
+def pack_histories(histories):
+    """Action lists -> (actions int32 [n, stride], lengths int32 [n], stride): the arguments of az_engine_set_start_positions."""
+    lengths = np.asarray([len(h) for h in histories], dtype=np.int32)
+    stride = max(1, int(lengths.max()) if len(lengths) else 1)
+    actions = np.zeros((len(lengths), stride), dtype=np.int32)
+    for i, h in enumerate(histories):
+        actions[i, :len(h)] = [int(a) for a in h]
+    return actions, lengths, stride
+
+
+def roots_export_layout(n_slots, max_children):
+    """(name, dtype, shape, byte offset) of every array in the packed root export (include/az_engine.h,
+    az_engine_export_roots_device) + total bytes."""
+    G, mc = int(n_slots), int(max_children)
+    spec = (("header", np.int32, (4,)), ("game_id", np.int32, (G,)), ("phase", np.int32, (G,)), ("ply", np.int32, (G,)),
+            ("sims_done", np.int32, (G,)), ("n_children", np.int32, (G,)), ("root_n", np.uint32, (G,)),
+            ("root_q", np.float64, (G,)), ("child_action", np.int32, (G, mc)), ("child_n", np.uint32, (G, mc)),
+            ("child_q", np.float64, (G, mc)), ("child_p", np.float64, (G, mc)))
+    out, off = [], 0
+    for name, dt, shape in spec:
+        out.append((name, dt, shape, off))
+        off += (int(np.prod(shape)) * np.dtype(dt).itemsize + 15) & ~15
+    return out, off
+
+
+def unpack_roots_export(host_bytes, n_slots, max_children):
+    """A host copy of a packed root export -> the dict SelfPlayEngine.read_roots() returns."""
+    host_bytes = np.ascontiguousarray(host_bytes, dtype=np.uint8)
+    layout, total = roots_export_layout(n_slots, max_children)
+    if host_bytes.size < total:
+        raise ValueError("root export buffer holds %d bytes, layout needs %d" % (host_bytes.size, total))
+    out = {}
+    for name, dt, shape, off in layout:
+        cnt = int(np.prod(shape)) * np.dtype(dt).itemsize
+        out[name] = host_bytes[off:off + cnt].view(dt).reshape(shape)
+    hdr = out.pop("header")
+    if int(hdr[1]) != int(n_slots) or int(hdr[2]) != int(max_children):
+        raise ValueError("root export header says %d slots x %d children, expected %d x %d"
+                         % (hdr[1], hdr[2], n_slots, max_children))
+    out["n_finished"], out["error_flags"] = int(hdr[0]), int(hdr[3]) & 0xFFFFFFFF
+    out["root_n"] = out["root_n"].astype(np.int64)
+    out["child_n"] = out["child_n"].astype(np.int64)
+    return out
 
 
 def device_export_layout(n_games, max_plies, max_children):

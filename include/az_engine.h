@@ -200,6 +200,18 @@ int az_engine_set_injected_rng(az_engine *e, const double *etas, const double *u
  * traces).  actions: host [n] action prefix applied to the initial state. Call after reset. */
 int az_engine_set_start_prefix(az_engine *e, const int32_t *actions, int32_t n);
 
+/* A start position per GAME: game id i (0 <= i < n_games) starts from the position that the action prefix
+ * actions[i * stride .. i * stride + lengths[i]) reaches from the initial one (host arrays, copied; 0 <= lengths[i] <= stride).
+ * manual_moves engines only - the batched form of MCTS.search(state) for many given states: reset with at most n_games games,
+ * tick until every slot has finished its search, read all roots with az_engine_export_roots_device.  Self-play and arena
+ * engines keep ONE start ply (the record offset, the value targets, the replay append and the arena's side assignment use it)
+ * and return AZ_E_INVALID.  Every prefix is replayed on the host with the game's legality checks: an illegal action, or a
+ * prefix that ends the game, is refused with AZ_E_INVALID and az_last_error names the index of the offending game; nothing is
+ * changed then.  As with az_engine_set_start_prefix the caller resets afterwards.  May be called again on the same engine
+ * (the next chunk of positions); it supersedes a single prefix, and az_engine_set_start_prefix clears the table.
+ * Injected Dirichlet draws are indexed by the state's ply number, as everywhere.  Synchronises the device. */
+int az_engine_set_start_positions(az_engine *e, const int32_t *actions, const int32_t *lengths, int64_t stride, int64_t n_games);
+
 /*
  * One tick = MCTS.playout's select + expand + backup (mcts.py:126-153) for all slots, fused with the
  * agent's move step when a slot has finished its S playouts (alphazerobot.py:71-93,
@@ -275,6 +287,18 @@ int az_engine_export(az_engine *e, az_example_view *out, void *stream);
  * (the arrays of az_example_view; on-policy value targets are filled in on the device). */
 int64_t az_engine_export_device_bytes(const az_engine *e);
 int az_engine_export_device(az_engine *e, void *dev_buf, int64_t bytes, void *stream);
+
+/* Every slot's root, packed into ONE caller-owned device buffer by one kernel: asynchronous on `stream`, no host
+ * synchronisation, usable inside a captured graph - what az_engine_read_root / az_engine_read_slot give for one slot per
+ * synchronising call.  The values are the node records' own (no arithmetic), so they equal az_engine_read_root's.
+ * Layout, G = n_slots, mc = max_children, every array 16-byte aligned (and so must dev_buf be), in this order:
+ *   header i32[4] | game_id i32[G] | phase i32[G] | ply i32[G] | sims_done i32[G] | n_children i32[G] | root_n u32[G] |
+ *   root_q f64[G] | child_action i32[G][mc] | child_n u32[G][mc] | child_q f64[G][mc] | child_p f64[G][mc]
+ * header = { number of slots whose phase is 5 (search done) or 0 (idle), G, mc, az_progress.error_flags }: a tick loop learns
+ * from one 16-byte copy when every search has finished.  phase / game_id / ply / sims_done are az_slot_info's; children are in
+ * ascending-action order; rows of the child arrays beyond n_children hold action -1 and zeros. */
+int64_t az_engine_roots_device_bytes(const az_engine *e);
+int az_engine_export_roots_device(az_engine *e, void *dev_buf, int64_t bytes, void *stream);
 
 /* debug / parity read-back of one slot's root (mcts.root.{N,Q,children[a].{N,Q,P}}, read by
  * game_utils.py:30-31,174,178,183-193).  Arrays sized max_children.  Returns n_children or <0.
