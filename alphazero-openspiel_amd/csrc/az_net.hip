@@ -1,24 +1,18 @@
-// az_net.hip — fused PV-net inference for gfx950 (MI355X): the whole residual tower in ONE kernel.
+// az_net.hip — the host side of the fused PV-net forward: the C ABI of include/az_net.h.  No kernels live here.
 //
-// Reference computation: Net.forward / ResidualBlock.forward (network.py:48-64,99-104) in eval mode.
-// Mapping (weights pre-packed by alphazero-openspiel_amd/fusednet.py, see include/az_net.h):
-//   * a wavefront owns BPW whole boards; their activations never leave the CU: one fp16 LDS image
-//     [board][cell][56 ch] with a zero halo (cell = (y+1)*(W+1) + (x+1); the halo column is shared between
-//     rows), rewritten in place layer after layer; the fp32 residual stream lives in registers.
-//   * every 3x3 conv is an implicit GEMM on v_mfma_f32_16x16x32_f16:  D[co][n] += Wp[co][k] * Act[k][n],
-//     n = (board, position) over the wave's boards, k = 64 groups x 8 channels (group -> tap, channel
-//     octet; group 63 = zero padding); conv 0, which sees only the input planes, is compacted on upload to
-//     16 groups (9 taps x one octet) = 4 k-steps.  M = 64 output channels (4 tiles),
-//     so the accumulator of lane l holds 4 CONSECUTIVE channels of one position: the epilogue
-//     (bias, LeakyReLU, next BN scale/shift) packs them to fp16 and writes 8 bytes back to the image.
-//   * weights are the A operand, shared by all waves of the workgroup: streamed L2 -> LDS by
-//     global_load_lds (16 B/lane) in 16 KiB chunks (4 k-steps), double buffered, one barrier per chunk.
-//     They are stored fragment-linear, so an A fragment is one contiguous KiB (conflict-free ds_read_b128).
-// The fc1 + softmax + tanh head is a second small MFMA kernel over the tower output (fp16, [B][HW][64]).
+// Reference computation: Net.forward / ResidualBlock.forward (network.py) in eval mode.  Two create paths fill one az_net:
+//   * az_net_create takes the layouts packed by fusednet.pack_net (<= 56 filters; fp16, or split-fp16 hi / lo pairs for the
+//     fp32-grade precision), re-groups them into the weight streams of the tuned tower kernels and records the net's scheme:
+//     which of those kernels can run it;
+//   * az_net_create_wide takes plain folded fp32 arrays (up to 256 filters, any finite weight) for the general layer-by-layer
+//     path (az_net_wide.h), which runs the nets that pack_net or az_net_create refuse.
+// plan_forward picks, from the scheme and the batch size alone, the tower kernel of a forward and its launch shape;
+// az_net_forward launches it (then the head, unless the tower kernel ran fc1 itself), and az_net_kernel_label and
+// az_net_issued_mfma_per_board describe that same plan.
 //
-// Files: az_net_common.h (types, LDS access helpers, launch parameters), az_tower_f16.h (the kernel described above),
-// az_tower_x3.h (the same tower with split-fp16 operands: fp32-grade precision), az_head.h (fc1 + softmax + tanh kernels);
-// this file: the C ABI (include/az_net.h) - weight re-grouping and upload, geometry, launches.
+// Kernels: az_tower_f16.h, az_tower_f16c.h (fp16 operands), az_tower_x3.h, az_tower_x3b.h, az_tower_x3c.h, az_tower_x3d.h
+// (split-fp16 operands: fp32-grade), az_net_wide.h, az_head.h and az_head_fused.h (fc1 + softmax + tanh); shared types and
+// launch parameters: az_net_common.h, az_head_params.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -27,8 +21,6 @@
 #include <cmath>
 
 #include <string>
-#include <type_traits>
-#include <utility>
 #include <vector>
 
 #include "../../include/az_engine.h"
@@ -38,35 +30,54 @@
 #include "az_head_params.h"
 #include "az_net_wide.h"
 
+#define AZ_X3C_MAX_BOARDS 512 // (set from profiles/r3_tower_vs_boards.txt)
+#define AZ_F16C_MAX_BOARDS 512 // the same for the f16 tower (az_tower_f16c.h)
+#define AZ_X3C_ONE_PER_WG 256 // up to here a board per workgroup fills fewer CUs than the chip has; above, two boards per workgroup (39 vs 49 us at 512 boards)
+
+// Which tower kernels can run a net, fixed at create; plan_forward picks among them by batch size.
+enum class NetScheme {
+    F16,     // az_tower_kernel
+    F16C,    // az_tower_f16c_kernel up to AZ_F16C_MAX_BOARDS boards, az_tower_kernel above (row-pair board of <= 6 rows, <= 50 filters)
+    X3,      // az_tower_x3_kernel
+    X3B,     // row-pair board with <= 50 filters: az_tower_x3c_kernel up to AZ_X3C_MAX_BOARDS boards, az_tower_x3b_kernel above
+    X3B_X3D, // the same, and the positions pack into whole column tiles: az_tower_x3d_kernel above 128 x xd_nb boards
+    X3D,     // the positions pack into whole column tiles, not a row-pair board (8x8): az_tower_x3d_kernel
+    WIDE,    // az_net_create_wide: az_conv_wide_kernel per conv
+};
+// The tower kernel of one forward.  X3C_FUSED_HEAD: az_tower_x3c_kernel also runs fc1 + softmax + tanh for its boards.
+enum class TowerKind { F16, F16C, X3, X3B, X3C, X3C_FUSED_HEAD, X3D, WIDE };
+constexpr int N_TOWER_KINDS = 8;
+// az_net_kernel_label's name of each kind's tower launch (kind_label: + the head kernels, and the conv count of WIDE)
+static const char *const TOWER_NAME[N_TOWER_KINDS] = {
+    "az_tower_kernel", "az_tower_f16c_kernel", "az_tower_x3_kernel", "az_tower_x3b_kernel", "az_tower_x3c_kernel",
+    "az_tower_x3c_kernel (fc1 + softmax + tanh in the same launch)", "az_tower_x3d_kernel", "az_wide_input_kernel + az_conv_wide_kernel"};
+
 // ================================================================================================
 struct az_net {
     az_net_desc d;
     std::string err;
+    NetScheme scheme = NetScheme::F16;
     _Float16 *conv_w = nullptr, *fc_w = nullptr, *xout = nullptr;
     _Float16 *fc_w_lo = nullptr, *xout_lo = nullptr; // f16x3 only
     float *epi = nullptr, *fc_b = nullptr, *skip_w = nullptr, *logits = nullptr;
     int xc = AZ_NET_XOUT_C, fc_ksteps = 0; // channel stride of xout / k-steps of fc1 (az_net_create)
     float in_affine[16];
     int max_boards = 0;
-    int bpw_max = 0, lds_head = 0, n_ot = 0, r3 = 16;
+    int bpw_max = 0, lds_head = 0, n_ot = 0;
+    int r3 = 16;                  // 2: <= 50 filters, output-channel tile 3 holds two stored rows (a template argument of the kernels)
     int precision = AZ_NET_PREC_F16;
-    bool x3b = false; // f16x3 on a row-pair board with <= 50 filters: the x3b scheme (no output-channel tile for channels 48, 49)
-    // f16x3 with <= 50 filters on a board whose positions pack into whole column tiles (6x7, 6x6, 8x8): az_tower_x3d_kernel.
-    // AZ_NET_TOWER=x3b in the environment at az_net_create keeps the kernels of round 3 (az_tower_x3b_kernel / az_tower_x3_kernel)
-    // for same-box A/B runs; on row-pair boards the bits are the same either way.
-    int x3d = -1;                 // variant of az_launch_tower_x3d, -1: none
-    int xd_nb = 0, xd_R = 0, xd_rs = 0;
+    // az_tower_x3d_kernel (schemes X3B_X3D, X3D): its variant, boards per workgroup, cells per board region, row stride
+    int xd_variant = -1, xd_nb = 0, xd_R = 0, xd_rs = 0;
     _Float16 *conv_w_d = nullptr; // the x3d weight stream (conv_w keeps the stream of the small-batch / fallback kernel)
     uint16_t *xd_pos = nullptr, *xd_sdst = nullptr;
     // the general layer-by-layer path (az_net_create_wide, az_net_wide.h); d then holds the geometry only
-    bool wide = false;
     int fpad = 0, nbw = 0;
     std::vector<size_t> w_off;                   // halves from w_wide to conv c's weight stream
     _Float16 *w_wide = nullptr;                  // every conv's [n_chunks][9][nmt][hi, lo][64][8]
     float *epi_wide = nullptr, *in_wide = nullptr; // [n_convs][4][fpad]; [in_scale 4][in_shift 4][skip fpad x 4]
     float *x_wide = nullptr;                     // residual stream [max_boards][HW][fpad]
     _Float16 *opa_hi = nullptr, *opa_lo = nullptr, *opb_hi = nullptr, *opb_lo = nullptr; // operand planes (opb: conv 0's input, then the tower output)
-    std::string label_wide;                      // az_net_kernel_label
+    std::string labels[N_TOWER_KINDS];           // az_net_kernel_label of each kind (finish_create)
 };
 static std::string g_net_err;
 
@@ -84,36 +95,22 @@ extern "C" const char *az_net_last_error(const az_net *n) { return n ? n->err.c_
 extern "C" int az_net_destroy(az_net *n) {
     if (!n) return AZ_OK;
     (void)hipSetDevice(n->d.device);
-    (void)hipFree(n->conv_w);
-    (void)hipFree(n->fc_w);
-    (void)hipFree(n->fc_w_lo);
-    (void)hipFree(n->xout_lo);
-    (void)hipFree(n->xout);
-    (void)hipFree(n->epi);
-    (void)hipFree(n->fc_b);
-    (void)hipFree(n->skip_w);
-    (void)hipFree(n->logits);
-    (void)hipFree(n->conv_w_d);
-    (void)hipFree(n->xd_pos);
-    (void)hipFree(n->xd_sdst);
-    (void)hipFree(n->w_wide);
-    (void)hipFree(n->epi_wide);
-    (void)hipFree(n->in_wide);
-    (void)hipFree(n->x_wide);
-    (void)hipFree(n->opa_hi);
-    (void)hipFree(n->opa_lo);
-    (void)hipFree(n->opb_hi);
-    (void)hipFree(n->opb_lo);
+    void *bufs[] = {n->conv_w, n->fc_w,   n->fc_w_lo, n->xout,   n->xout_lo,  n->epi,    n->fc_b,   n->skip_w, n->logits, n->conv_w_d,
+                    n->xd_pos, n->xd_sdst, n->w_wide, n->epi_wide, n->in_wide, n->x_wide, n->opa_hi, n->opa_lo, n->opb_hi, n->opb_lo};
+    for (void *b : bufs) (void)hipFree(b);
     delete n;
     return AZ_OK;
 }
 
-// geometry of one launch for a given boards-per-wave
+// geometry of one launch: boards per wave, column tiles per wave, k-steps per weight chunk, waves per workgroup, the cell grid
+// (az_net_common.h: TowerParams) and the LDS layout
 struct TowerGeom {
     int bpw, nt, ck, waves, rcells, zcell, rs, tpb, cells, off_epi, off_act, lds;
+    bool rp1; // f16x3: a row-pair board whose lo planes sit at the compile-time distance X3_LOFF_RP1
 };
+// the f16 tower for a given boards-per-wave
 static TowerGeom tower_geom(int bpw, int waves, int H, int W) {
-    TowerGeom g;
+    TowerGeom g = {};
     g.bpw = bpw;
     if (W <= 7) { // row-pair tiles at row stride 8 (conflict-free B reads)
         g.rs = 8;
@@ -143,34 +140,19 @@ static TowerGeom tower_geom(int bpw, int waves, int H, int W) {
     return g;
 }
 
-// geometry of the f16x3 tower: one board per wave, 4 waves, 4-k-step chunks of (hi, lo) records
-struct X3Geom {
-    int nt, rcells, zcell, rs, tpb, cells, off_epi, off_act, lds, lo_off;
-    bool rp1;
-};
-static X3Geom x3_geom(int H, int W, int r3) {
-    X3Geom g;
-    if (W <= 7) {
-        g.rs = 8;
-        g.tpb = (H + 1) / 2;
-        g.nt = g.tpb;
-    } else {
-        g.rs = W + 1;
-        g.tpb = 0;
-        g.nt = (H * W + 15) / 16;
-    }
-    g.cells = (H + 2) * g.rs + 1;
-    int zpad = 2 * (g.rs + 1) + 1;
-    g.rcells = (g.cells + zpad + 15) & ~15;
-    g.zcell = g.cells + (g.rs + 1);
+// bytes of one k-step record of the record streams (conv_stream): output-channel tiles 0..2 + the stored rows of tile 3
+static int record_bytes(int r3) { return 3 * 1024 + 4 * (r3 < 16 ? r3 + 1 : 16) * 16; }
+
+// geometry of the f16x3 tower: one board per wave (the cell grid of the f16 tower's), 4 waves, 4-k-step chunks of (hi, lo) records
+static TowerGeom x3_geom(int H, int W, int r3) {
+    TowerGeom g = tower_geom(1, 4, H, W);
+    g.ck = 4;
     g.rp1 = g.tpb && g.rs == 8 && g.tpb <= 3 && g.rcells <= 96;
-    const int region_b = N_OCT * g.rcells * OCT_B;
-    g.lo_off = g.rp1 ? X3_LOFF_RP1 : region_b;
-    const int rows = r3 < 16 ? r3 + 1 : 16, rec = 3 * 1024 + 4 * rows * 16;
-    const int chunk_s = (4 * 2 * rec + 1023) & ~1023;
+    const int lo_off = g.rp1 ? X3_LOFF_RP1 : N_OCT * g.rcells * OCT_B;
+    const int chunk_s = (4 * 2 * record_bytes(r3) + 1023) & ~1023;
     g.off_epi = 2 * chunk_s;
     g.off_act = g.off_epi + 2048 + 256 * 16;
-    g.lds = g.off_act + 4 * 2 * g.lo_off;
+    g.lds = g.off_act + 4 * 2 * lo_off;
     if (g.nt < 3) g.nt = 3;
     return g;
 }
@@ -179,6 +161,89 @@ static X3Geom x3_geom(int H, int W, int r3) {
 static inline uint16_t abi_weight(const uint16_t *src, int c, int co, int tap, int ch) {
     const int g = tap * 7 + (ch >> 3), oks = g >> 2, olane = (g & 3) * 16 + (co & 15), mt = co >> 4;
     return src[(size_t)c * AZ_NET_KSTEPS * 2048 + ((((size_t)oks * 4 + mt) * 64 + olane) * 8) + (ch & 7)];
+}
+
+// Device weight stream of az_tower_kernel, az_tower_f16c_kernel and az_tower_x3_kernel: [conv 0 compacted to AZ_NET_K0STEPS
+// k-steps][conv 1 ..][..], one RECORD per k-step: output-channel tiles 0..2 as in the ABI layout (3 KiB), tile 3 with only its
+// stored rows (see WRec).  Conv 0 sees the input planes only (channel octet 0), i.e. ABI groups 7*tap; they become groups 0..8 of
+// its 4 k-steps.  <= 50 filters (r3 < 16): the K dimension is re-grouped into 15 k-steps - channels 48, 49 of the nine taps fit
+// ONE k-step instead of filling the seventh channel octet of every tap.
+static void build_records(const unsigned char *src, int r3, int n_convs, std::vector<unsigned char> &dev) {
+    const bool l15 = r3 < 16;
+    const int nks = l15 ? 15 : AZ_NET_KSTEPS;
+    const int rows = r3 < 16 ? r3 + 1 : 16, rec = record_bytes(r3);
+    const size_t conv_b = (size_t)AZ_NET_KSTEPS * 4096;
+    const size_t n_rec = (size_t)AZ_NET_K0STEPS + (size_t)(n_convs - 1) * nks;
+    dev.assign(n_rec * rec, 0);
+    auto put_record = [&](unsigned char *dst, const unsigned char *ks4k) { // ks4k: [4 mt][64 lanes][16 B]
+        memcpy(dst, ks4k, 3 * 1024);
+        for (int q = 0; q < 4; q++)
+            for (int r = 0; r < (r3 < 16 ? r3 : 16); r++)
+                memcpy(dst + 3 * 1024 + (q * rows + r) * 16, ks4k + 3 * 1024 + (q * 16 + r) * 16, 16);
+    };
+    // ABI: element j of group g = tap * 7 + c8 is channel 8 * c8 + j at that tap.  abi_half: one fp16 of a conv
+    auto abi_half = [&](int c, int mt, int l15_, int tap, int ch) -> uint16_t {
+        int g = tap * 7 + (ch >> 3), oks = g >> 2, olane = (g & 3) * 16 + l15_;
+        const uint16_t *w = (const uint16_t *)(src + (size_t)c * conv_b);
+        return w[((((size_t)oks * 4 + mt) * 64 + olane) * 8) + (ch & 7)];
+    };
+    std::vector<unsigned char> c0(AZ_NET_K0STEPS * 4096, 0); // conv 0 compacted, still in 4 KiB k-steps
+    for (int ks = 0; ks < AZ_NET_K0STEPS; ks++)
+        for (int mt = 0; mt < 4; mt++)
+            for (int lane = 0; lane < 64; lane++) {
+                int g = 4 * ks + (lane >> 4);
+                if (g >= 9) continue;
+                int go = 7 * g, oks = go >> 2, olane = (go & 3) * 16 + (lane & 15);
+                memcpy(&c0[(((size_t)ks * 4 + mt) * 64 + lane) * 16], src + (((size_t)oks * 4 + mt) * 64 + olane) * 16, 16);
+            }
+    size_t off = 0;
+    for (int ks = 0; ks < AZ_NET_K0STEPS; ks++, off += rec) put_record(&dev[off], &c0[(size_t)ks * 4096]);
+    std::vector<uint16_t> k4(4096 / 2);
+    for (int c = 1; c < n_convs; c++)
+        for (int ks = 0; ks < nks; ks++, off += rec) {
+            if (!l15) {
+                put_record(&dev[off], src + (size_t)c * conv_b + (size_t)ks * 4096);
+                continue;
+            }
+            // 15-k-step grouping: group g' = 4 ks + q.  g' < 54: (tap, octet) = divmod(g', 6), the 48 channels of six
+            // full octets; g' = 54, 55: zero; k-step 14: element j of group q < 3 is channel 48 + (j & 1) at tap
+            // 4 q + j / 2 (taps > 8: zero), group 3 zero.
+            std::fill(k4.begin(), k4.end(), (uint16_t)0);
+            for (int mt = 0; mt < 4; mt++)
+                for (int lane = 0; lane < 64; lane++) {
+                    const int q = lane >> 4, l = lane & 15, gp = 4 * ks + q;
+                    uint16_t *o = &k4[(((size_t)mt * 64) + lane) * 8];
+                    for (int j = 0; j < 8; j++) {
+                        if (ks < 14) {
+                            if (gp < 54) o[j] = abi_half(c, mt, l, gp / 6, 8 * (gp % 6) + j);
+                        } else if (q < 3) {
+                            int tap = 4 * q + (j >> 1);
+                            if (tap < 9) o[j] = abi_half(c, mt, l, tap, 48 + (j & 1));
+                        }
+                    }
+                }
+            put_record(&dev[off], (const unsigned char *)k4.data());
+        }
+}
+// the records of conv_w (f16x3: per k-step the hi record, then the lo record) + a chunk of padding: the last (short) chunk is
+// fetched at full length
+static std::vector<unsigned char> conv_stream(const az_net_desc &d, int r3) {
+    const int n_convs = 2 * d.n_blocks;
+    const size_t pad = 2 * 8 * 4096 + 1024, rec = record_bytes(r3);
+    std::vector<unsigned char> hi, lo, dev;
+    build_records((const unsigned char *)d.conv_w, r3, n_convs, hi);
+    if (d.precision != AZ_NET_PREC_F16X3) {
+        hi.resize(hi.size() + pad, 0);
+        return hi;
+    }
+    build_records((const unsigned char *)d.conv_w_lo, r3, n_convs, lo);
+    const size_t n_rec = hi.size() / rec;
+    dev.assign(2 * n_rec * rec + pad, 0);
+    for (size_t r = 0; r < n_rec; r++) {
+        memcpy(&dev[2 * r * rec], &hi[r * rec], rec);
+        memcpy(&dev[(2 * r + 1) * rec], &lo[r * rec], rec);
+    }
+    return dev;
 }
 
 // Device weight streams of the kernels on the x3b scheme (meaning of tiles T and X: az_tower_x3b.h).  A conv is cut into parts
@@ -352,22 +417,87 @@ static X3DLayout x3d_layout(int H, int W) {
     return out;
 }
 
-#define AZ_X3C_MAX_BOARDS 512 // (set from profiles/r3_tower_vs_boards.txt)
-#define AZ_F16C_MAX_BOARDS 512 // the same for the f16 tower (az_tower_f16c.h)
-#define AZ_X3C_ONE_PER_WG 256 // up to here a board per workgroup fills fewer CUs than the chip has; above, two boards per workgroup (39 vs 49 us at 512 boards)
+// fc1 of the ABI layout (AZ_NET_XOUT_C channels per cell) -> xc channels per cell: [ot][k-step][lane][8], k = 32 ks + 8 (lane >> 4) + e,
+// row lane & 15
+static std::vector<uint16_t> repack_fc(const uint16_t *src, int n_ot, int fc_ksteps, int HW, int xc) {
+    const int ks64 = HW * AZ_NET_XOUT_C / 32;
+    std::vector<uint16_t> dst((size_t)n_ot * fc_ksteps * 64 * 8, 0);
+    for (int ot = 0; ot < n_ot; ot++)
+        for (int ks = 0; ks < fc_ksteps; ks++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int e = 0; e < 8; e++) {
+                    const int k = 32 * ks + 8 * (lane >> 4) + e;
+                    if (k >= HW * xc) continue;
+                    const int k64 = (k / xc) * AZ_NET_XOUT_C + k % xc;
+                    dst[(((size_t)ot * fc_ksteps + ks) * 64 + lane) * 8 + e] =
+                        src[(((size_t)ot * ks64 + k64 / 32) * 64 + ((k64 % 32) / 8) * 16 + (lane & 15)) * 8 + k64 % 8];
+                }
+    return dst;
+}
+
 // v_mfma instructions one wave (= one board) of az_tower_x3_kernel issues (az_tower_x3.h: 3 per product, every tile)
 static double x3_mfma_per_wave(int nt, int n_convs, int nks) { return 3.0 * (AZ_NET_K0STEPS + (double)(n_convs - 1) * nks) * 4 * nt; }
 
-extern "C" int az_net_create(const az_net_desc *desc, az_net **out) {
+// the head kernels of a forward, as az_net_kernel_label names them
+static std::string head_label(const az_net *n) {
+    const std::string t = n->precision == AZ_NET_PREC_F16X3 ? "<X3>" : "";
+    return n->n_ot > OTG ? "az_head_gemm_kernel" + t + " + az_head_softmax_kernel" + t : "az_head_kernel" + t;
+}
+static std::string kind_label(const az_net *n, TowerKind k) {
+    std::string s = TOWER_NAME[(int)k];
+    if (k == TowerKind::WIDE) s += std::string(n->precision == AZ_NET_PREC_F16X3 ? "<X3>" : "<F16>") + " x" + std::to_string(2 * n->d.n_blocks);
+    return k == TowerKind::X3C_FUSED_HEAD ? s : s + " + " + head_label(n);
+}
+
+// ---- what the two create paths share -----------------------------------------------------------------------------------------
+template <class Desc> static int check_args(const Desc *desc, az_net **out, const char *desc_name) {
     if (!desc || !out) {
         g_net_err = "null argument";
         return AZ_E_INVALID;
     }
     *out = nullptr;
-    if (desc->struct_size != (int32_t)sizeof(az_net_desc)) {
-        g_net_err = "az_net_desc.struct_size mismatch";
+    if (desc->struct_size != (int32_t)sizeof(Desc)) {
+        g_net_err = std::string(desc_name) + ".struct_size mismatch";
         return AZ_E_INVALID;
     }
+    return AZ_OK;
+}
+// once the description passed the path's own checks: the device, and a fresh net on it
+static int new_net(int device, az_net **n) {
+    const hipError_t s = hipSetDevice(device);
+    if (s != hipSuccess) {
+        g_net_err = std::string("hipSetDevice: ") + hipGetErrorString(s);
+        return AZ_E_HIP;
+    }
+    *n = new az_net();
+    return AZ_OK;
+}
+// hipMalloc + hipMemcpy of host-built buffers into the net; the first failure sticks (later uploads are skipped)
+struct Upload {
+    int rc = AZ_OK;
+    void fail(int code, const char *msg) {
+        if (rc != AZ_OK) return;
+        g_net_err = msg;
+        rc = code;
+    }
+    template <class T> void operator()(T *&dst, const void *src, size_t bytes) {
+        if (rc == AZ_OK && (hipMalloc((void **)&dst, bytes) != hipSuccess || hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess))
+            fail(AZ_E_NOMEM, "hipMalloc/hipMemcpy of the net's weights failed");
+    }
+};
+// the end of both create paths: a failed upload frees the net and everything uploaded so far
+static int finish_create(az_net *n, const Upload &up, az_net **out) {
+    if (up.rc != AZ_OK) {
+        az_net_destroy(n);
+        return up.rc;
+    }
+    for (int k = 0; k < N_TOWER_KINDS; k++) n->labels[k] = kind_label(n, (TowerKind)k);
+    *out = n;
+    return AZ_OK;
+}
+
+extern "C" int az_net_create(const az_net_desc *desc, az_net **out) {
+    if (int rc = check_args(desc, out, "az_net_desc")) return rc;
     const az_net_desc &d = *desc;
     if (d.rows < 3 || d.cols < 3 || d.rows * d.cols > 64 || d.in_planes < 1 || d.in_planes > 4 || d.n_filters < 1 ||
         d.n_filters > AZ_NET_CPAD || d.n_blocks < 1 || d.num_actions < 1 || !d.conv_w || !d.conv_epi || !d.in_affine ||
@@ -379,23 +509,27 @@ extern "C" int az_net_create(const az_net_desc *desc, az_net **out) {
         g_net_err = "precision must be AZ_NET_PREC_F16 or AZ_NET_PREC_F16X3";
         return AZ_E_INVALID;
     }
-    if (d.precision == AZ_NET_PREC_F16X3 && (!d.conv_w_lo || !d.fc_w_lo)) {
+    const bool x3 = d.precision == AZ_NET_PREC_F16X3;
+    if (x3 && (!d.conv_w_lo || !d.fc_w_lo)) {
         g_net_err = "AZ_NET_PREC_F16X3 needs conv_w_lo and fc_w_lo";
         return AZ_E_INVALID;
     }
-    az_net *n = new az_net();
-    n->d = d;
-    n->precision = d.precision;
-    memcpy(n->in_affine, d.in_affine, sizeof n->in_affine);
-    const int HW = d.rows * d.cols;
-    if (n->precision == AZ_NET_PREC_F16X3) {
-        X3Geom g = x3_geom(d.rows, d.cols, d.n_filters <= 50 ? 2 : 16);
-        n->x3b = g.rp1 && d.n_filters <= 50; // row-pair board, channels 48, 49 the only ones past three tiles
-        if (!n->x3b && (g.nt > 4 || g.lds > 160 * 1024)) {
+    // the scheme.  <= 50 filters (r3 = 2): output-channel tile 3 holds only channels 48, 49
+    const int r3 = d.n_filters <= 50 ? 2 : 16, HW = d.rows * d.cols;
+    NetScheme scheme;
+    X3DLayout xd;
+    if (x3) {
+        const TowerGeom g = x3_geom(d.rows, d.cols, r3);
+        const bool x3b = g.rp1 && r3 == 2; // row-pair board, channels 48, 49 the only ones past three tiles
+        if (!x3b && (g.nt > 4 || g.lds > 160 * 1024)) {
             g_net_err = "board / filter count does not fit the f16x3 tower kernel's LDS budget";
-            delete n;
             return AZ_E_INVALID;
         }
+        if (r3 == 2) xd = x3d_layout(d.rows, d.cols);
+        scheme = xd.variant >= 0 ? (x3b ? NetScheme::X3B_X3D : NetScheme::X3D) : x3b ? NetScheme::X3B : NetScheme::X3;
+    } else {
+        const TowerGeom gc = tower_geom(1, 1, d.rows, d.cols);
+        scheme = r3 == 2 && gc.tpb && gc.rs == 8 && gc.tpb <= 3 ? NetScheme::F16C : NetScheme::F16;
     }
     // boards per wave: at most 4 column tiles per wave (larger tiles spill registers under the hand-scheduled k-loop
     // and measured slower than more, smaller waves) within the 160 KiB LDS
@@ -407,182 +541,65 @@ extern "C" int az_net_create(const az_net_desc *desc, az_net **out) {
     }
     if (!best) {
         g_net_err = "board does not fit the tower kernel's LDS budget";
-        delete n;
         return AZ_E_INVALID;
     }
+    az_net *n;
+    if (int rc = new_net(d.device, &n)) return rc;
+    n->d = d;
+    n->precision = d.precision;
+    n->scheme = scheme;
+    n->r3 = r3;
+    memcpy(n->in_affine, d.in_affine, sizeof n->in_affine);
     n->bpw_max = best;
     n->n_ot = (d.num_actions + 1 + 15) / 16;
     n->lds_head = HEAD_NW * OTG * 64 * 16 + 16 * n->n_ot * 16 * 4;
-    hipError_t s = hipSetDevice(d.device);
-    if (s != hipSuccess) {
-        g_net_err = std::string("hipSetDevice: ") + hipGetErrorString(s);
-        delete n;
-        return AZ_E_HIP;
-    }
     // Channel stride of the tower output = K index of fc1.  The descriptor's fc stream is laid out for 64 (AZ_NET_XOUT_C: 50 channels
     // padded to two 32-wide k-steps per cell).  Where fc1 is a real GEMM (az_head_gemm_kernel) the 14 padding channels are 22 % of its
     // MFMAs and bytes: those nets keep 52 channels per cell (8-byte stores stay aligned; H*W even keeps the board rows 16-byte aligned)
     // and the stream is repacked here.  The small heads (az_head_kernel, az_head_fused.h) walk k-steps of (cell, channel half): 64.
     n->xc = (n->n_ot > OTG && HW % 2 == 0 && d.n_filters <= 52) ? 52 : AZ_NET_XOUT_C; // (the reference's nets have 50 filters)
     n->fc_ksteps = (HW * n->xc + 31) / 32;
-    const int ks64 = HW * AZ_NET_XOUT_C / 32;
-    size_t fw = (size_t)n->n_ot * n->fc_ksteps * 64 * 8 * 2, fb = (size_t)n->n_ot * 16 * 4;
-    std::vector<uint16_t> fc_re, fc_re_lo;
-    auto repack_fc = [&](const uint16_t *src, std::vector<uint16_t> &dst) { // [ot][k-step][lane][8]: k = 32 ks + 8 (lane >> 4) + e, row lane & 15
-        dst.assign(fw / 2, 0);
-        for (int ot = 0; ot < n->n_ot; ot++)
-            for (int ks = 0; ks < n->fc_ksteps; ks++)
-                for (int lane = 0; lane < 64; lane++)
-                    for (int e = 0; e < 8; e++) {
-                        const int k = 32 * ks + 8 * (lane >> 4) + e;
-                        if (k >= HW * n->xc) continue;
-                        const int k64 = (k / n->xc) * AZ_NET_XOUT_C + k % n->xc;
-                        dst[(((size_t)ot * n->fc_ksteps + ks) * 64 + lane) * 8 + e] =
-                            src[(((size_t)ot * ks64 + k64 / 32) * 64 + ((k64 % 32) / 8) * 16 + (lane & 15)) * 8 + k64 % 8];
-                    }
+    Upload up;
+    // conv weights: the x3d stream where the positions pack; conv_w holds the x3b stream on the x3b schemes, the records elsewhere
+    const int n_convs = 2 * d.n_blocks;
+    auto x3_stream = [&](const X3Stream &L, _Float16 *&dst) {
+        std::vector<unsigned char> s;
+        if (!build_x3_stream(L, d.conv_w, d.conv_w_lo, n_convs, s))
+            up.fail(AZ_E_INVALID, "AZ_NET_PREC_F16X3: a conv weight of magnitude >= 32 (the device copy holds the weights x 2048 in fp16)");
+        up(dst, s.data(), s.size());
     };
-    int rc = AZ_OK;
-    auto up = [&](void **dst, const void *src, size_t bytes) {
-        if (rc != AZ_OK) return;
-        if (hipMalloc(dst, bytes) != hipSuccess || hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-            g_net_err = "hipMalloc/hipMemcpy of the packed weights failed";
-            rc = AZ_E_NOMEM;
-        }
-    };
-    {   // device layout: [conv 0 compacted to AZ_NET_K0STEPS k-steps][conv 1 ..][..], one RECORD per k-step: output-channel
-        // tiles 0..2 as in the ABI layout (3 KiB), tile 3 with only its stored rows (see WRec).  Conv 0 sees the input
-        // planes only (channel octet 0), i.e. ABI groups 7*tap; they become groups 0..8 of its 4 k-steps.
-        // <= 50 filters: the K dimension is re-grouped into 15 k-steps (see dev_group below) - channels 48, 49 of the nine
-        // taps fit ONE k-step instead of filling the seventh channel octet of every tap.
-        n->r3 = d.n_filters <= 50 ? 2 : 16;
-        const bool l15 = n->r3 < 16;
-        const int nks = l15 ? 15 : AZ_NET_KSTEPS;
-        const int rows = n->r3 < 16 ? n->r3 + 1 : 16, rec = 3 * 1024 + 4 * rows * 16;
-        const int n_convs = 2 * d.n_blocks;
-        const size_t conv_b = (size_t)AZ_NET_KSTEPS * 4096;
-        const size_t n_rec = (size_t)AZ_NET_K0STEPS + (size_t)(n_convs - 1) * nks;
-        auto build_records = [&](const unsigned char *src, std::vector<unsigned char> &dev) { // one `rec`-byte record per k-step
-        dev.assign(n_rec * rec, 0);
-        auto put_record = [&](unsigned char *dst, const unsigned char *ks4k) { // ks4k: [4 mt][64 lanes][16 B]
-            memcpy(dst, ks4k, 3 * 1024);
-            for (int q = 0; q < 4; q++)
-                for (int r = 0; r < (n->r3 < 16 ? n->r3 : 16); r++)
-                    memcpy(dst + 3 * 1024 + (q * rows + r) * 16, ks4k + 3 * 1024 + (q * 16 + r) * 16, 16);
-        };
-        // ABI: element j of group g = tap * 7 + c8 is channel 8 * c8 + j at that tap.  abi_half: one fp16 of a conv
-        auto abi_half = [&](int c, int mt, int l15_, int tap, int ch) -> uint16_t {
-            int g = tap * 7 + (ch >> 3), oks = g >> 2, olane = (g & 3) * 16 + l15_;
-            const uint16_t *w = (const uint16_t *)(src + (size_t)c * conv_b);
-            return w[((((size_t)oks * 4 + mt) * 64 + olane) * 8) + (ch & 7)];
-        };
-        std::vector<unsigned char> c0(AZ_NET_K0STEPS * 4096, 0); // conv 0 compacted, still in 4 KiB k-steps
-        for (int ks = 0; ks < AZ_NET_K0STEPS; ks++)
-            for (int mt = 0; mt < 4; mt++)
-                for (int lane = 0; lane < 64; lane++) {
-                    int g = 4 * ks + (lane >> 4);
-                    if (g >= 9) continue;
-                    int go = 7 * g, oks = go >> 2, olane = (go & 3) * 16 + (lane & 15);
-                    memcpy(&c0[(((size_t)ks * 4 + mt) * 64 + lane) * 16], src + (((size_t)oks * 4 + mt) * 64 + olane) * 16, 16);
-                }
-        size_t off = 0;
-        for (int ks = 0; ks < AZ_NET_K0STEPS; ks++, off += rec) put_record(&dev[off], &c0[(size_t)ks * 4096]);
-        std::vector<uint16_t> k4(4096 / 2);
-        for (int c = 1; c < n_convs; c++)
-            for (int ks = 0; ks < nks; ks++, off += rec) {
-                if (!l15) {
-                    put_record(&dev[off], src + (size_t)c * conv_b + (size_t)ks * 4096);
-                    continue;
-                }
-                // 15-k-step grouping: group g' = 4 ks + q.  g' < 54: (tap, octet) = divmod(g', 6), the 48 channels of six
-                // full octets; g' = 54, 55: zero; k-step 14: element j of group q < 3 is channel 48 + (j & 1) at tap
-                // 4 q + j / 2 (taps > 8: zero), group 3 zero.
-                std::fill(k4.begin(), k4.end(), (uint16_t)0);
-                for (int mt = 0; mt < 4; mt++)
-                    for (int lane = 0; lane < 64; lane++) {
-                        const int q = lane >> 4, l = lane & 15, gp = 4 * ks + q;
-                        uint16_t *o = &k4[(((size_t)mt * 64) + lane) * 8];
-                        for (int j = 0; j < 8; j++) {
-                            if (ks < 14) {
-                                if (gp < 54) o[j] = abi_half(c, mt, l, gp / 6, 8 * (gp % 6) + j);
-                            } else if (q < 3) {
-                                int tap = 4 * q + (j >> 1);
-                                if (tap < 9) o[j] = abi_half(c, mt, l, tap, 48 + (j & 1));
-                            }
-                        }
-                    }
-                put_record(&dev[off], (const unsigned char *)k4.data());
-            }
-        };
-        std::vector<unsigned char> hi, dev;
-        const char *tw = getenv("AZ_NET_TOWER");
-        if (n->precision == AZ_NET_PREC_F16X3 && d.n_filters <= 50 && !(tw && strcmp(tw, "x3b") == 0)) {
-            const X3DLayout L = x3d_layout(d.rows, d.cols);
-            if (L.variant >= 0) {
-                n->x3d = L.variant, n->xd_nb = L.nb, n->xd_R = L.R, n->xd_rs = L.rs;
-                std::vector<unsigned char> sd;
-                if (!build_x3_stream(x3d_stream_layout(), d.conv_w, d.conv_w_lo, n_convs, sd)) {
-                    g_net_err = "AZ_NET_PREC_F16X3: a conv weight of magnitude >= 32 (the device copy holds the weights x 2048 in fp16)";
-                    rc = AZ_E_INVALID;
-                }
-                up((void **)&n->conv_w_d, sd.data(), sd.size());
-                up((void **)&n->xd_pos, L.pos.data(), L.pos.size() * 2);
-                up((void **)&n->xd_sdst, L.sdst.data(), L.sdst.size() * 2);
-            }
-        }
-        if (n->x3b) {
-            if (!build_x3_stream(x3b_stream_layout(), d.conv_w, d.conv_w_lo, n_convs, dev)) {
-                g_net_err = "AZ_NET_PREC_F16X3: a conv weight of magnitude >= 32 (the device copy holds the weights x 2048 in fp16)";
-                rc = AZ_E_INVALID;
-            }
-            up((void **)&n->conv_w, dev.data(), dev.size());
-        } else {
-        build_records((const unsigned char *)d.conv_w, hi);
-        const size_t pad = 2 * 8 * 4096 + 1024; // a chunk of padding: the last (short) chunk is fetched at full length
-        if (n->precision == AZ_NET_PREC_F16X3) { // per k-step: hi record, lo record
-            std::vector<unsigned char> lo;
-            build_records((const unsigned char *)d.conv_w_lo, lo);
-            dev.assign(2 * n_rec * rec + pad, 0);
-            for (size_t r = 0; r < n_rec; r++) {
-                memcpy(&dev[2 * r * rec], &hi[r * rec], rec);
-                memcpy(&dev[(2 * r + 1) * rec], &lo[r * rec], rec);
-            }
-        } else {
-            dev = hi;
-            dev.resize(n_rec * rec + pad, 0);
-        }
-        up((void **)&n->conv_w, dev.data(), dev.size());
-        }
+    if (xd.variant >= 0) {
+        n->xd_variant = xd.variant, n->xd_nb = xd.nb, n->xd_R = xd.R, n->xd_rs = xd.rs;
+        x3_stream(x3d_stream_layout(), n->conv_w_d);
+        up(n->xd_pos, xd.pos.data(), xd.pos.size() * 2);
+        up(n->xd_sdst, xd.sdst.data(), xd.sdst.size() * 2);
+    }
+    if (scheme == NetScheme::X3B || scheme == NetScheme::X3B_X3D) x3_stream(x3b_stream_layout(), n->conv_w);
+    else {
+        const std::vector<unsigned char> s = conv_stream(d, r3);
+        up(n->conv_w, s.data(), s.size());
     }
     {   // [conv][3][64] (ABI) -> [conv][4][64] with the NEXT conv's bias in row 3 (what the kernel's ring slot holds; f32x: x 2048)
-        int nc = 2 * d.n_blocks;
-        std::vector<float> e4((size_t)nc * 256, 0.f);
-        for (int c = 0; c < nc; c++) {
+        std::vector<float> e4((size_t)n_convs * 256, 0.f);
+        for (int c = 0; c < n_convs; c++) {
             memcpy(&e4[(size_t)c * 256], d.conv_epi + (size_t)c * 192, 192 * sizeof(float));
-            if (c + 1 < nc) memcpy(&e4[(size_t)c * 256 + 192], d.conv_epi + (size_t)(c + 1) * 192, 64 * sizeof(float));
+            if (c + 1 < n_convs) memcpy(&e4[(size_t)c * 256 + 192], d.conv_epi + (size_t)(c + 1) * 192, 64 * sizeof(float));
             // fp32-grade towers: an accumulator holds 2048 x the conv (X3_WSCALE), so its initial value is 2048 x the bias - scaled here
             // (exact), not by two multiplies per output tile in every epilogue
-            if (n->precision == AZ_NET_PREC_F16X3)
+            if (x3)
                 for (int i = 0; i < 64; i++) e4[(size_t)c * 256 + 192 + i] *= X3_WSCALE;
         }
-        up((void **)&n->epi, e4.data(), e4.size() * sizeof(float));
+        up(n->epi, e4.data(), e4.size() * sizeof(float));
     }
-    if (n->xc != AZ_NET_XOUT_C) {
-        repack_fc(d.fc_w, fc_re);
-        up((void **)&n->fc_w, fc_re.data(), fw);
-        if (n->precision == AZ_NET_PREC_F16X3) {
-            repack_fc(d.fc_w_lo, fc_re_lo);
-            up((void **)&n->fc_w_lo, fc_re_lo.data(), fw);
-        }
-    } else {
-        up((void **)&n->fc_w, d.fc_w, fw);
-        if (n->precision == AZ_NET_PREC_F16X3) up((void **)&n->fc_w_lo, d.fc_w_lo, fw);
+    const size_t fw = (size_t)n->n_ot * n->fc_ksteps * 64 * 8 * 2;
+    for (int lo = 0; lo < (x3 ? 2 : 1); lo++) { // fc1: hi (and lo) halves
+        const uint16_t *src = lo ? d.fc_w_lo : d.fc_w;
+        std::vector<uint16_t> re;
+        if (n->xc != AZ_NET_XOUT_C) re = repack_fc(src, n->n_ot, n->fc_ksteps, HW, n->xc), src = re.data();
+        up(lo ? n->fc_w_lo : n->fc_w, src, fw);
     }
-    up((void **)&n->fc_b, d.fc_b, fb);
-    up((void **)&n->skip_w, d.skip_w, 64 * 4 * sizeof(float));
-    if (rc != AZ_OK) {
-        az_net_destroy(n);
-        return rc;
-    }
+    up(n->fc_b, d.fc_b, (size_t)n->n_ot * 16 * 4);
+    up(n->skip_w, d.skip_w, 64 * 4 * sizeof(float));
     n->d.conv_w_lo = nullptr;
     n->d.fc_w_lo = nullptr;
     n->d.conv_w = nullptr; // host pointers are not kept
@@ -591,28 +608,18 @@ extern "C" int az_net_create(const az_net_desc *desc, az_net **out) {
     n->d.skip_w = nullptr;
     n->d.fc_w = nullptr;
     n->d.fc_b = nullptr;
-    *out = n;
-    return AZ_OK;
+    return finish_create(n, up, out);
 }
 
 // ================================================================================================
 // The general path (az_net_wide.h): the descriptor holds plain folded fp32 arrays; every device layout is decided here.
 // Conv weights: a power-of-two scale s per output channel puts the channel's largest |w| s in [8, 16), so hi' = 2048 fp16(w s) and
 // lo' = fp16(2048 (w s - fp16(w s))) are finite for any finite weight; the epilogue multiplies by 1 / (2048 s), exactly.
-static std::string wide_label(const az_net *n);
 static int wide_fpad(int f) { return (f + 31) & ~31; }
 static int wide_nks(const az_net *n, int conv) { return conv == 0 ? 9 : 9 * n->fpad / 32; }
 
 extern "C" int az_net_create_wide(const az_net_wide_desc *desc, az_net **out) {
-    if (!desc || !out) {
-        g_net_err = "null argument";
-        return AZ_E_INVALID;
-    }
-    *out = nullptr;
-    if (desc->struct_size != (int32_t)sizeof(az_net_wide_desc)) {
-        g_net_err = "az_net_wide_desc.struct_size mismatch";
-        return AZ_E_INVALID;
-    }
+    if (int rc = check_args(desc, out, "az_net_wide_desc")) return rc;
     const az_net_wide_desc &d = *desc;
     if (d.rows < 1 || d.cols < 1 || d.rows * d.cols > 64 || d.in_planes < 1 || d.in_planes > 4 || d.n_filters < 1 ||
         d.n_filters > AZ_NET_WIDE_MAX_FILTERS || d.n_blocks < 1 || d.num_actions < 1 || d.num_actions > 768 || !d.conv_w ||
@@ -632,25 +639,20 @@ extern "C" int az_net_create_wide(const az_net_wide_desc *desc, az_net **out) {
             g_net_err = "az_net_create_wide: a conv weight is not finite";
             return AZ_E_INVALID;
         }
-    az_net *n = new az_net();
+    az_net *n;
+    if (int rc = new_net(d.device, &n)) return rc;
     n->d = az_net_desc{};
     n->d.struct_size = sizeof(az_net_desc);
     n->d.rows = d.rows, n->d.cols = d.cols, n->d.in_planes = cin0, n->d.n_filters = F, n->d.n_blocks = d.n_blocks;
     n->d.num_actions = d.num_actions, n->d.device = d.device, n->d.precision = d.precision;
     n->precision = d.precision;
-    n->wide = true;
+    n->scheme = NetScheme::WIDE;
     n->fpad = fpad;
     n->nbw = 16 * WIDE_NT / HW;
     n->xc = fpad;
     n->n_ot = (A1 + 15) / 16;
     n->fc_ksteps = HW * fpad / 32;
     n->lds_head = HEAD_NW * OTG * 64 * 16 + 16 * n->n_ot * 16 * 4;
-    hipError_t s = hipSetDevice(d.device);
-    if (s != hipSuccess) {
-        g_net_err = std::string("hipSetDevice: ") + hipGetErrorString(s);
-        delete n;
-        return AZ_E_HIP;
-    }
     // conv weight streams and epilogue rows
     std::vector<uint16_t> w;
     std::vector<float> epi((size_t)nc * 4 * fpad, 0.f);
@@ -720,27 +722,14 @@ extern "C" int az_net_create_wide(const az_net_wide_desc *desc, az_net **out) {
                 }
     std::vector<float> fb((size_t)n->n_ot * 16, 0.f);
     for (int o = 0; o < A1; o++) fb[o] = d.fc_b[o];
-    int rc = AZ_OK;
-    auto up = [&](void **dst, const void *src, size_t bytes) {
-        if (rc != AZ_OK) return;
-        if (hipMalloc(dst, bytes) != hipSuccess || hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-            g_net_err = "hipMalloc/hipMemcpy of the wide net's weights failed";
-            rc = AZ_E_NOMEM;
-        }
-    };
-    up((void **)&n->w_wide, w.data(), w.size() * 2);
-    up((void **)&n->epi_wide, epi.data(), epi.size() * 4);
-    up((void **)&n->in_wide, in.data(), in.size() * 4);
-    up((void **)&n->fc_w, fh.data(), fw * 2);
-    up((void **)&n->fc_w_lo, fl.data(), fw * 2);
-    up((void **)&n->fc_b, fb.data(), fb.size() * 4);
-    if (rc != AZ_OK) {
-        az_net_destroy(n);
-        return rc;
-    }
-    n->label_wide = wide_label(n);
-    *out = n;
-    return AZ_OK;
+    Upload up;
+    up(n->w_wide, w.data(), w.size() * 2);
+    up(n->epi_wide, epi.data(), epi.size() * 4);
+    up(n->in_wide, in.data(), in.size() * 4);
+    up(n->fc_w, fh.data(), fw * 2);
+    up(n->fc_w_lo, fl.data(), fw * 2);
+    up(n->fc_b, fb.data(), fb.size() * 4);
+    return finish_create(n, up, out);
 }
 
 // v_mfma_f32_16x16x32_f16 per board of a wide forward of n_boards boards: every workgroup runs all of its channel tiles over
@@ -752,12 +741,6 @@ static double wide_mfma_per_board(const az_net *n, int n_boards) {
     const long full = n_boards / n->nbw, rest = n_boards % n->nbw;
     const double tiles = (double)full * ((n->nbw * HW + 15) / 16) + (rest ? (rest * HW + 15) / 16 : 0);
     return per * ks * (n->fpad / 16) * tiles / n_boards + per * (double)n->n_ot * n->fc_ksteps / 16.0;
-}
-static std::string wide_label(const az_net *n) {
-    const bool big = n->n_ot > OTG, x3 = n->precision == AZ_NET_PREC_F16X3;
-    const std::string t = x3 ? "<X3>" : "";
-    return "az_wide_input_kernel + az_conv_wide_kernel" + std::string(x3 ? "<X3>" : "<F16>") + " x" + std::to_string(2 * n->d.n_blocks) +
-           (big ? " + az_head_gemm_kernel" + t + " + az_head_softmax_kernel" + t : " + az_head_kernel" + t);
 }
 static int wide_reserve(az_net *n, int32_t max_boards) {
     const size_t cells = (size_t)max_boards * n->d.rows * n->d.cols;
@@ -776,7 +759,8 @@ static int wide_reserve(az_net *n, int32_t max_boards) {
     n->max_boards = max_boards;
     return AZ_OK;
 }
-static int wide_forward(az_net *n, const float *obs, float *priors, float *values, int32_t n_boards, hipStream_t st) {
+// the wide tower: the input launch, then one launch per conv; the tower output ends in opb
+static hipError_t wide_tower(az_net *n, const float *obs, int32_t n_boards, hipStream_t st) {
     const bool x3 = n->precision == AZ_NET_PREC_F16X3;
     const int HW = n->d.rows * n->d.cols, nc = 2 * n->d.n_blocks;
     WideInputParams ip;
@@ -796,22 +780,13 @@ static int wide_forward(az_net *n, const float *obs, float *priors, float *value
         p.w = n->w_wide + n->w_off[c], p.epi = n->epi_wide + (size_t)c * 4 * n->fpad, p.x = n->x_wide;
         s = az_launch_wide_conv(n->d.device, x3, p, st);
     }
-    if (s != hipSuccess) {
-        n->err = std::string("wide tower launch: ") + hipGetErrorString(s);
-        return AZ_E_HIP;
-    }
-    HeadParams hp;
-    hp.HW = HW, hp.A = n->d.num_actions, hp.n_ot = n->n_ot, hp.K = HW * n->fpad, hp.ksteps = n->fc_ksteps, hp.n_boards = n_boards;
-    hp.x = n->opb_hi, hp.x_lo = n->opb_lo, hp.fc_w = n->fc_w, hp.fc_w_lo = n->fc_w_lo, hp.fc_b = n->fc_b;
-    hp.priors = priors, hp.values = values;
-    NCHK(n, az_launch_head(n->d.device, x3, hp, n_boards, n->lds_head, n->logits, st));
-    return AZ_OK;
+    return s;
 }
 
 extern "C" int az_net_reserve(az_net *n, int32_t max_boards) {
     if (!n || max_boards < 1) return AZ_E_INVALID;
     NCHK(n, hipSetDevice(n->d.device));
-    if (n->wide) return wide_reserve(n, max_boards);
+    if (n->scheme == NetScheme::WIDE) return wide_reserve(n, max_boards);
     if (n->xout) (void)hipFree(n->xout);
     n->xout = nullptr;
     // (+ 64 bytes: the last k-step of fc1 may reach past a board's row - into the next board's, times zero weights)
@@ -852,70 +827,140 @@ static TowerGeom choose_geom(const az_net *n, int n_boards) {
     return g;
 }
 
-// which kernels az_net_forward launches for a batch of n_boards (the SAME conditions as there)
-struct NetDispatch {
-    bool x3c, x3c_head, x3d, f16c;
+// ================================================================================================
+// One forward of n_boards boards: the tower kernel and its launch shape.  A pure function of (net, n_boards) - forwards are
+// captured in graphs, so nothing here may keep state; az_net_forward, az_net_kernel_label and az_net_issued_mfma_per_board
+// all follow it.
+struct ForwardPlan {
+    TowerKind kind;
+    TowerGeom g = {};    // the launch geometry (ck: k-steps per weight chunk); unused by WIDE
+    int per_wg = 0;      // boards per workgroup
+    int grid = 0;        // workgroups of the tower launch
+    int xd_variant = -1; // X3D: the kernel variant
+    bool head = true;    // a separate head launch follows the tower
 };
-static NetDispatch net_dispatch(const az_net *n, int n_boards) {
-    NetDispatch d = {false, false, false, false};
-    const int ksteps = n->fc_ksteps;
-    if (n->precision == AZ_NET_PREC_F16X3) {
-        d.x3c = n->x3b && n_boards <= AZ_X3C_MAX_BOARDS;
-        d.x3c_head = d.x3c && n->n_ot == 1 && ksteps <= 96 && n->d.cols >= 4;
-        // packed tiles put xd_nb boards in a workgroup: with eight (6x6) a batch must be large enough to occupy the chip - at 1024
-        // boards 128 workgroups of 4.5 tiles per SIMD lose to 256 of 3 (az_tower_x3b_kernel, one round), from 1280 on they win
-        d.x3d = !d.x3c && n->x3d >= 0 && (!n->x3b || n_boards > 128 * n->xd_nb);
-    } else {
-        const TowerGeom gc = tower_geom(1, 1, n->d.rows, n->d.cols);
-        d.f16c = n_boards <= AZ_F16C_MAX_BOARDS && n->r3 == 2 && gc.tpb && gc.rs == 8 && gc.tpb <= 3;
+static ForwardPlan plan_forward(const az_net *n, int n_boards) {
+    ForwardPlan p;
+    const int H = n->d.rows, W = n->d.cols;
+    switch (n->scheme) {
+    case NetScheme::WIDE:
+        p.kind = TowerKind::WIDE;
+        return p;
+    case NetScheme::F16C:
+        if (n_boards <= AZ_F16C_MAX_BOARDS) { // small batch of a row-pair board: a board per four-wave workgroup (az_tower_f16c.h)
+            p.kind = TowerKind::F16C;
+            p.g = tower_geom(1, 1, H, W);
+            // up to a board per CU: 32 KiB weight chunks (half the barriers); above: 16 KiB chunks, so that two workgroups fit a CU's LDS
+            p.g.ck = n_boards <= AZ_X3C_ONE_PER_WG ? 8 : 4;
+            p.g.off_epi = (p.g.ck == 8 ? 4 : 3) * p.g.ck * 4096; // a ring of four 32-KiB / three 16-KiB weight buffers (147 / 65 KB with the planes)
+            p.g.off_act = p.g.off_epi + 2048 + 8 * 64 * 8;
+            p.g.lds = p.g.off_act + N_OCT * p.g.rcells * OCT_B;
+            p.per_wg = 1;
+            break;
+        }
+        [[fallthrough]];
+    case NetScheme::F16:
+        p.kind = TowerKind::F16;
+        p.g = choose_geom(n, n_boards);
+        p.per_wg = p.g.waves * p.g.bpw;
+        break;
+    default: { // the f16x3 schemes: one board per wave, 4 waves per workgroup
+        const bool x3b = n->scheme == NetScheme::X3B || n->scheme == NetScheme::X3B_X3D;
+        p.g = x3_geom(H, W, n->r3);
+        p.per_wg = 4;
+        if (x3b && n_boards <= AZ_X3C_MAX_BOARDS) { // small batch: one board per four waves (az_tower_x3c.h), two per workgroup above 256
+            // ... and with a single output tile (connect_four: 7 + 1 outputs) that kernel also runs fc1 + softmax + tanh for its board:
+            // at <= 512 boards the head kernel is 7 us of a 49 us tick (profiles/r3_small_generation_kernel_stats.csv).  (The same inside
+            // az_tower_x3b_kernel, measured: bit-identical and SLOWER - 1146 vs 1182 games/s in a same-box A/B: at one workgroup per CU
+            // the head phase of each of the four rounds, ~5 us, has nothing to hide behind.)  Eight chains x HMAX k-steps; a chain
+            // steps 4 columns: az_tower_x3c.h.
+            p.head = !(n->n_ot == 1 && n->fc_ksteps <= 96 && W >= 4);
+            p.kind = p.head ? TowerKind::X3C : TowerKind::X3C_FUSED_HEAD;
+            p.per_wg = n_boards > AZ_X3C_ONE_PER_WG ? 2 : 1;
+        } else if (n->scheme == NetScheme::X3D || (n->scheme == NetScheme::X3B_X3D && n_boards > 128 * n->xd_nb)) {
+            // packed column tiles (az_tower_x3d.h).  They put xd_nb boards in a workgroup: with eight (6x6) a batch must be large enough
+            // to occupy the chip - at 1024 boards 128 workgroups of 4.5 tiles per SIMD lose to 256 of 3 (az_tower_x3b_kernel, one
+            // round), from 1280 on they win
+            p.kind = TowerKind::X3D;
+            p.per_wg = n->xd_nb;
+            p.xd_variant = n->xd_variant;
+        } else
+            p.kind = x3b ? TowerKind::X3B : TowerKind::X3;
     }
-    return d;
+    }
+    p.grid = (n_boards + p.per_wg - 1) / p.per_wg;
+    return p;
+}
+
+// launch parameters of the tuned tower kernels
+static TowerParams tower_params(const az_net *n, const ForwardPlan &p, const float *obs, float *priors, float *values, int n_boards) {
+    TowerParams tp = {};
+    tp.H = n->d.rows, tp.W = n->d.cols, tp.HW = tp.H * tp.W, tp.cin = n->d.in_planes, tp.n_convs = 2 * n->d.n_blocks;
+    tp.n_boards = n_boards;
+    tp.cells = p.g.cells, tp.rs = p.g.rs, tp.tpb = p.g.tpb, tp.bpw = p.g.bpw, tp.rcells = p.g.rcells, tp.zcell = p.g.zcell;
+    tp.off_epi = p.g.off_epi, tp.off_act = p.g.off_act;
+    tp.conv_w = p.kind == TowerKind::X3D ? n->conv_w_d : n->conv_w;
+    tp.epi = n->epi, tp.skip_w = n->skip_w;
+    memcpy(tp.in_scale, n->in_affine, 32);
+    memcpy(tp.in_shift, n->in_affine + 8, 32);
+    tp.obs = obs, tp.xout = n->xout, tp.xout_lo = n->xout_lo, tp.xout_c = n->xc;
+    tp.fc_w = p.kind == TowerKind::X3C_FUSED_HEAD ? n->fc_w : nullptr; // set: the tower kernel runs the head
+    tp.fc_w_lo = n->fc_w_lo, tp.fc_b = n->fc_b, tp.priors = priors, tp.values = values;
+    tp.A = n->d.num_actions, tp.fc_ksteps = n->fc_ksteps;
+    tp.xd_nb = n->xd_nb, tp.xd_R = n->xd_R, tp.xd_rs = n->xd_rs, tp.xd_pos = n->xd_pos, tp.xd_sdst = n->xd_sdst;
+    return tp;
+}
+// launch parameters of the head kernels: the tower output of either path
+static HeadParams head_params(const az_net *n, float *priors, float *values, int n_boards) {
+    const bool wide = n->scheme == NetScheme::WIDE;
+    HeadParams hp;
+    hp.HW = n->d.rows * n->d.cols, hp.A = n->d.num_actions, hp.n_ot = n->n_ot, hp.K = hp.HW * n->xc, hp.ksteps = n->fc_ksteps;
+    hp.n_boards = n_boards;
+    hp.x = wide ? n->opb_hi : n->xout, hp.x_lo = wide ? n->opb_lo : n->xout_lo;
+    hp.fc_w = n->fc_w, hp.fc_w_lo = n->fc_w_lo, hp.fc_b = n->fc_b;
+    hp.priors = priors, hp.values = values;
+    return hp;
 }
 
 extern "C" int az_net_issued_mfma_per_board(const az_net *n, int32_t n_boards, double *out) {
     if (!n || !out || n_boards < 1) return AZ_E_INVALID;
-    if (n->wide) {
-        *out = wide_mfma_per_board(n, n_boards);
-        return AZ_OK;
-    }
+    const ForwardPlan p = plan_forward(n, n_boards);
     const int n_convs = 2 * n->d.n_blocks, nks = n->r3 < 16 ? 15 : AZ_NET_KSTEPS;
-    const NetDispatch dp = net_dispatch(n, n_boards);
     const double head = (double)n->n_ot * n->fc_ksteps / 16.0; // one MFMA per (output tile, k-step) per 16 boards
     // a column tile on the x3b scheme: conv 0: 4 k-steps x (9 + 2 T); then 15 x 9 + 2 x (2 T + 3 X) + 2 T (gather k-step)
     const double per_tile = AZ_NET_K0STEPS * 11 + (double)(n_convs - 1) * (15 * 9 + 2 * 5 + 2);
-    if (n->precision == AZ_NET_PREC_F16X3) {
-        const X3Geom g = x3_geom(n->d.rows, n->d.cols, n->r3);
-        if (dp.x3d) *out = az_x3d_variant(n->x3d).tiles * per_tile / n->xd_nb + 3.0 * head; // the workgroup's tiles over its boards
-        else if (n->x3b) // three tiles per board (x3b, x3c); the head fused into x3c runs its eight chains once per board or pair of boards
-            *out = 3.0 * per_tile + 3.0 * (dp.x3c_head ? head * 16.0 / (n_boards > AZ_X3C_ONE_PER_WG ? 2 : 1) : head);
-        else
-            *out = x3_mfma_per_wave(g.nt <= 3 ? 3 : 4, n_convs, nks) + 3.0 * head; // one board per wave
-        return AZ_OK;
+    switch (p.kind) {
+    case TowerKind::F16: {
+        const int nt = p.g.nt < 3 ? 3 : (p.g.nt > 3 ? 4 : 3);
+        *out = (double)(AZ_NET_K0STEPS + (n_convs - 1) * nks) * 4 * nt / p.g.bpw + head;
+        break;
     }
-    if (dp.f16c) { // one board per four-wave workgroup: three column tiles x 4 output-channel tiles
+    case TowerKind::F16C: // one board per four-wave workgroup: three column tiles x 4 output-channel tiles
         *out = (double)(AZ_NET_K0STEPS + (n_convs - 1) * nks) * 4 * 3 + head;
-        return AZ_OK;
+        break;
+    case TowerKind::X3: // one board per wave
+        *out = x3_mfma_per_wave(p.g.nt <= 3 ? 3 : 4, n_convs, nks) + 3.0 * head;
+        break;
+    case TowerKind::X3B: // three tiles per board
+    case TowerKind::X3C:
+        *out = 3.0 * per_tile + 3.0 * head;
+        break;
+    case TowerKind::X3C_FUSED_HEAD: // the fused head runs its eight chains once per board or pair of boards
+        *out = 3.0 * per_tile + 3.0 * (head * 16.0 / p.per_wg);
+        break;
+    case TowerKind::X3D: // the workgroup's tiles over its boards
+        *out = az_x3d_variant(p.xd_variant).tiles * per_tile / p.per_wg + 3.0 * head;
+        break;
+    case TowerKind::WIDE:
+        *out = wide_mfma_per_board(n, n_boards);
+        break;
     }
-    const TowerGeom g = choose_geom(n, n_boards);
-    const int nt = g.nt < 3 ? 3 : (g.nt > 3 ? 4 : 3);
-    *out = (double)(AZ_NET_K0STEPS + (n_convs - 1) * nks) * 4 * nt / g.bpw + head;
     return AZ_OK;
 }
 
 extern "C" const char *az_net_kernel_label(const az_net *n, int32_t n_boards) {
     if (!n) return "";
-    if (n->wide) return n->label_wide.c_str();
-    const bool big = n->n_ot > OTG;
-    const NetDispatch dp = net_dispatch(n, n_boards < 1 ? n->max_boards : n_boards);
-    if (n->precision == AZ_NET_PREC_F16X3) {
-        if (dp.x3c_head) return "az_tower_x3c_kernel (fc1 + softmax + tanh in the same launch)";
-        if (dp.x3c) return big ? "az_tower_x3c_kernel + az_head_gemm_kernel<X3> + az_head_softmax_kernel<X3>" : "az_tower_x3c_kernel + az_head_kernel<X3>";
-        if (dp.x3d) return big ? "az_tower_x3d_kernel + az_head_gemm_kernel<X3> + az_head_softmax_kernel<X3>" : "az_tower_x3d_kernel + az_head_kernel<X3>";
-        if (n->x3b) return big ? "az_tower_x3b_kernel + az_head_gemm_kernel<X3> + az_head_softmax_kernel<X3>" : "az_tower_x3b_kernel + az_head_kernel<X3>";
-        return big ? "az_tower_x3_kernel + az_head_gemm_kernel<X3> + az_head_softmax_kernel<X3>" : "az_tower_x3_kernel + az_head_kernel<X3>";
-    }
-    if (dp.f16c) return big ? "az_tower_f16c_kernel + az_head_gemm_kernel + az_head_softmax_kernel" : "az_tower_f16c_kernel + az_head_kernel";
-    return big ? "az_tower_kernel + az_head_gemm_kernel + az_head_softmax_kernel" : "az_tower_kernel + az_head_kernel";
+    return n->labels[(int)plan_forward(n, n_boards < 1 ? n->max_boards : n_boards).kind].c_str();
 }
 
 extern "C" int az_net_forward(az_net *n, const float *obs, float *priors, float *values, int32_t n_boards, void *stream) {
@@ -926,123 +971,26 @@ extern "C" int az_net_forward(az_net *n, const float *obs, float *priors, float 
     }
     NCHK(n, hipSetDevice(n->d.device)); // the launch must pair `stream` with the device the net lives on
     hipStream_t st = (hipStream_t)stream;
-    if (n->wide) return wide_forward(n, obs, priors, values, n_boards, st);
-    HeadParams hp;
-    hp.HW = n->d.rows * n->d.cols;
-    hp.A = n->d.num_actions;
-    hp.n_ot = n->n_ot;
-    hp.K = hp.HW * n->xc;
-    hp.ksteps = n->fc_ksteps;
-    hp.n_boards = n_boards;
-    hp.x = n->xout;
-    hp.x_lo = n->xout_lo;
-    hp.fc_w = n->fc_w;
-    hp.fc_w_lo = n->fc_w_lo;
-    hp.fc_b = n->fc_b;
-    hp.priors = priors;
-    hp.values = values;
-    if (n->precision == AZ_NET_PREC_F16X3) { // split-fp16 tower: one board per wave, 4 waves per workgroup
-        const X3Geom g = x3_geom(n->d.rows, n->d.cols, n->r3);
-        TowerParams tp;
-        tp.H = n->d.rows;
-        tp.W = n->d.cols;
-        tp.HW = tp.H * tp.W;
-        tp.cells = g.cells;
-        tp.rs = g.rs;
-        tp.tpb = g.tpb;
-        tp.off_epi = g.off_epi;
-        tp.off_act = g.off_act;
-        tp.cin = n->d.in_planes;
-        tp.n_convs = 2 * n->d.n_blocks;
-        tp.n_boards = n_boards;
-        tp.bpw = 1;
-        tp.rcells = g.rcells;
-        tp.zcell = g.zcell;
-        tp.conv_w = n->conv_w;
-        tp.epi = n->epi;
-        tp.skip_w = n->skip_w;
-        memcpy(tp.in_scale, n->in_affine, 32);
-        memcpy(tp.in_shift, n->in_affine + 8, 32);
-        tp.obs = obs;
-        tp.xout = n->xout;
-        tp.xout_lo = n->xout_lo;
-        tp.xout_c = n->xc;
-        const int grid = (n_boards + 3) / 4;
-        const NetDispatch dp = net_dispatch(n, n_boards);
-        const bool x3c = dp.x3c; // small batch: one board per workgroup (az_tower_x3c.h)
-        // ... and with a single output tile (connect_four: 7 + 1 outputs) that kernel also runs fc1 + softmax + tanh for its board:
-        // at <= 512 boards the head kernel is 7 us of a 49 us tick (profiles/r3_small_generation_kernel_stats.csv).  (The same inside
-        // az_tower_x3b_kernel, measured: bit-identical and SLOWER - 1146 vs 1182 games/s in a same-box A/B: at one workgroup per CU
-        // the head phase of each of the four rounds, ~5 us, has nothing to hide behind.)
-        const bool fused_head = dp.x3c_head; // (eight chains x HMAX k-steps; a chain steps 4 columns: az_tower_x3c.h)
-        tp.fc_w = fused_head ? n->fc_w : nullptr;
-        tp.fc_w_lo = n->fc_w_lo;
-        tp.fc_b = n->fc_b;
-        tp.priors = priors;
-        tp.values = values;
-        tp.A = n->d.num_actions;
-        tp.fc_ksteps = hp.ksteps;
-        hipError_t s;
-        if (x3c) s = az_launch_tower_x3c(n->d.device, n_boards > AZ_X3C_ONE_PER_WG ? 2 : 1, tp, n_boards, st);
-        else if (dp.x3d) { // packed column tiles (az_tower_x3d.h)
-            tp.conv_w = n->conv_w_d;
-            tp.xd_nb = n->xd_nb, tp.xd_R = n->xd_R, tp.xd_rs = n->xd_rs;
-            tp.xd_pos = n->xd_pos, tp.xd_sdst = n->xd_sdst;
-            s = az_launch_tower_x3d(n->d.device, n->x3d, tp, (n_boards + n->xd_nb - 1) / n->xd_nb, st);
-        } else if (n->x3b) s = az_launch_tower_x3b(n->d.device, tp, grid, st);
-        else s = az_launch_tower_x3(n->d.device, g.nt, g.rp1, n->r3, tp, grid, g.lds, st);
-        if (s != hipSuccess) {
-            n->err = std::string("f16x3 tower launch: ") + hipGetErrorString(s);
-            return AZ_E_HIP;
-        }
-        if (!fused_head) NCHK(n, az_launch_head(n->d.device, true, hp, n_boards, n->lds_head, n->logits, st));
-        return AZ_OK;
+    const ForwardPlan p = plan_forward(n, n_boards);
+    const TowerParams tp = tower_params(n, p, obs, priors, values, n_boards);
+    const int dv = n->d.device;
+    const bool x3 = n->precision == AZ_NET_PREC_F16X3;
+    hipError_t s = hipSuccess;
+    switch (p.kind) {
+    case TowerKind::F16: s = az_launch_tower_f16(dv, p.g.nt, p.g.ck, p.g.waves, n->r3, tp, p.grid, p.g.lds, st); break;
+    case TowerKind::F16C: s = az_launch_tower_f16c(dv, p.g.ck, tp, n_boards, p.g.lds, st); break;
+    case TowerKind::X3: s = az_launch_tower_x3(dv, p.g.nt, p.g.rp1, n->r3, tp, p.grid, p.g.lds, st); break;
+    case TowerKind::X3B: s = az_launch_tower_x3b(dv, tp, p.grid, st); break;
+    case TowerKind::X3C:
+    case TowerKind::X3C_FUSED_HEAD: s = az_launch_tower_x3c(dv, p.per_wg, tp, n_boards, st); break;
+    case TowerKind::X3D: s = az_launch_tower_x3d(dv, p.xd_variant, tp, p.grid, st); break;
+    case TowerKind::WIDE: s = wide_tower(n, obs, n_boards, st); break;
     }
-    const TowerGeom g = choose_geom(n, n_boards);
-    TowerParams tp;
-    tp.H = n->d.rows;
-    tp.W = n->d.cols;
-    tp.HW = tp.H * tp.W;
-    tp.cells = g.cells;
-    tp.rs = g.rs;
-    tp.tpb = g.tpb;
-    tp.off_epi = g.off_epi;
-    tp.cin = n->d.in_planes;
-    tp.n_convs = 2 * n->d.n_blocks;
-    tp.n_boards = n_boards;
-    tp.bpw = g.bpw;
-    tp.rcells = g.rcells;
-    tp.zcell = g.zcell;
-    tp.off_act = g.off_act;
-    tp.conv_w = n->conv_w;
-    tp.epi = n->epi;
-    tp.skip_w = n->skip_w;
-    memcpy(tp.in_scale, n->in_affine, 32);
-    memcpy(tp.in_shift, n->in_affine + 8, 32);
-    tp.obs = obs;
-    tp.xout = n->xout;
-    tp.xout_lo = nullptr;
-    tp.xout_c = n->xc;
-    tp.fc_w = nullptr;
-    int per_wg = g.waves * g.bpw, grid = (n_boards + per_wg - 1) / per_wg;
-    hipError_t s;
-    // small batch of a row-pair board with <= 50 filters: a board per four-wave workgroup (az_tower_f16c.h; same bits)
-    const TowerGeom gc = tower_geom(1, 1, n->d.rows, n->d.cols);
-    if (net_dispatch(n, n_boards).f16c) {
-        // up to a board per CU: 32 KiB weight chunks (half the barriers); above: 16 KiB chunks, so that two workgroups fit a CU's LDS
-        const int ck = n_boards <= AZ_X3C_ONE_PER_WG ? 8 : 4;
-        tp.cells = gc.cells, tp.rs = gc.rs, tp.tpb = gc.tpb;
-        tp.off_epi = (ck == 8 ? 4 : 3) * ck * 4096; // a ring of four 32-KiB / three 16-KiB weight buffers (147 / 65 KB with the planes)
-        tp.off_act = tp.off_epi + 2048 + 8 * 64 * 8;
-        tp.bpw = 1, tp.rcells = gc.rcells, tp.zcell = gc.zcell;
-        s = az_launch_tower_f16c(n->d.device, ck, tp, n_boards, tp.off_act + N_OCT * gc.rcells * OCT_B, st);
-    } else
-        s = az_launch_tower_f16(n->d.device, g.nt, g.ck, g.waves, n->r3, tp, grid, g.lds, st);
     if (s != hipSuccess) {
-        n->err = std::string("tower launch: ") + hipGetErrorString(s);
+        n->err = std::string(p.kind == TowerKind::WIDE ? "wide tower launch: " : x3 ? "f16x3 tower launch: " : "tower launch: ") + hipGetErrorString(s);
         return AZ_E_HIP;
     }
-    NCHK(n, az_launch_head(n->d.device, false, hp, n_boards, n->lds_head, n->logits, st));
+    if (p.head) NCHK(n, az_launch_head(dv, x3, head_params(n, priors, values, n_boards), n_boards, n->lds_head, n->logits, st));
     return AZ_OK;
 }
 
@@ -1050,7 +998,7 @@ extern "C" int az_net_read_tower(az_net *n, float *out, int32_t n_boards) {
     if (!n || !out || n_boards < 1 || n_boards > n->max_boards) return AZ_E_INVALID;
     NCHK(n, hipSetDevice(n->d.device));
     NCHK(n, hipDeviceSynchronize());
-    if (n->wide) { // out: [n_boards][H*W][fpad], hi + lo / 2048 of the tower output
+    if (n->scheme == NetScheme::WIDE) { // out: [n_boards][H*W][fpad], hi + lo / 2048 of the tower output
         const size_t cnt = (size_t)n_boards * n->d.rows * n->d.cols * n->fpad;
         std::vector<_Float16> h(cnt);
         NCHK(n, hipMemcpy(h.data(), n->opb_hi, cnt * 2, hipMemcpyDeviceToHost));

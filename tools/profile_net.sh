@@ -1,6 +1,6 @@
 #!/bin/bash
 # rocprofv3 counters for the PV-net forward alone (tools/net_microbench.py).  tools/profile_net.sh OUT [net_microbench flags ...]
-# (environment, e.g. AZ_NET_TOWER=x3b, is exported by the caller: the program itself comes right after `--`)
+# (environment, e.g. AZ_ENGINE_LIB for another build, is exported by the caller: the program itself comes right after `--`)
 export TMPDIR=/tmp
 OUT=${1:-gpurun_out/netprof}
 shift
