@@ -16,7 +16,8 @@ field of every root with `==`), and with the fused network at f32x the result do
 import numpy as np
 import torch
 
-from .engine import DeviceEvaluator, EngineError, HostPolicyEvaluator, SelfPlayEngine
+from .engine import (DeviceEvaluator, EngineError, HostPolicyEvaluator, SelfPlayEngine, TickDriver, close_all, default_device,
+                     make_evaluator)
 from .games import Game, State
 
 PHASE_IDLE, PHASE_SEARCH_DONE = 0, 5
@@ -43,13 +44,12 @@ def position_prefixes(game, histories):
 
 
 def _make_evaluator(policy_fn, device, backend, precision, n_slots):
-    """-> (evaluator, owned): a network becomes the package's device evaluator (arena._evaluator); an evaluator object is
-    taken as it is (and stays the caller's)."""
+    """-> (evaluator, owned): a network becomes the package's device evaluator (engine.make_evaluator); an evaluator object
+    is taken as it is (and stays the caller's)."""
     from .fusednet import FusedNet
     if isinstance(policy_fn, (FusedNet, DeviceEvaluator, HostPolicyEvaluator)):
         return policy_fn, False
-    from .arena import _evaluator
-    return _evaluator(policy_fn, device, backend, precision, n_slots), True
+    return make_evaluator(policy_fn, device, backend, precision, n_slots), True
 
 
 class Analyzer:
@@ -76,16 +76,11 @@ class Analyzer:
 
     def __init__(self, policy_fn, game_name, n_slots, n_playouts=100, c_puct=2.5, use_dirichlet=False, device=None,
                  eval_backend="fused", eval_precision="f32x", seed=None, check_every=16, **kwargs):
-        from .mcts import _as_module
         if int(n_slots) < 1:
             raise ValueError("n_slots must be positive")
         if int(check_every) < 1:
             raise ValueError("check_every must be positive")
-        if device is None:
-            mod = _as_module(policy_fn)
-            par = next(mod.parameters(), None) if mod is not None else None
-            device = par.device if par is not None and par.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
+        self.device = torch.device(device if device is not None else default_device(policy_fn))
         self.n_playouts, self.check_every = int(n_playouts), int(check_every)
         self.seed = int(np.random.randint(0, 2 ** 31 - 1)) if seed is None else int(seed)
         kwargs.setdefault("keep_search_tree", True)
@@ -108,10 +103,8 @@ class Analyzer:
         self.roots = None
 
     def close(self):
-        if self._owns_evaluator and hasattr(self.evaluator, "close"):
-            self.evaluator.close()
+        close_all(self.evaluator if self._owns_evaluator else None, self.engine)
         self.evaluator = None
-        self.engine.close()
 
     def __enter__(self):
         return self
@@ -154,21 +147,23 @@ class Analyzer:
             raise EngineError("Analyzer has no evaluator: pass the network, or set .evaluator")
         e = self.engine
         limit = int(max_ticks) if max_ticks is not None else 4 * self.n_playouts + 64
+
+        def tick():
+            e.advance(self.pri, self.val, self.obs)
+            self.evaluator(self.obs, self.pri, self.val)
+
+        drv = TickDriver(e.device, tick)  # eager ticks: this loop captures no graph
         with torch.cuda.device(e.device):
-            ticks = 0
             while True:
                 done, flags = self._finished()
                 if flags:
                     e.progress()  # raises with the decoded fault names
                 if done >= e.G:
                     break
-                if ticks >= limit:
+                if drv.ticks >= limit:
                     raise EngineError("analysis did not finish within %d ticks: %r" % (limit, e.progress()))
-                for _ in range(self.check_every):
-                    e.advance(self.pri, self.val, self.obs)
-                    self.evaluator(self.obs, self.pri, self.val)
-                ticks += self.check_every
-            self.ticks += ticks
+                drv.run(self.check_every)
+            self.ticks += drv.ticks
             self.roots = e.read_roots(self.roots_buf)
         return self.roots
 

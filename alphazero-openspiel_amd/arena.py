@@ -17,9 +17,9 @@ the pair (2k, 2k+1) is one reference `test_*` call and scores  ret0(2k) - ret0(2
 import numpy as np
 import torch
 
-from .engine import DeviceEvaluator, EngineError, SelfPlayEngine
+from .engine import EngineError, SelfPlayEngine, TickDriver, close_all, default_device, make_evaluator, tick_until
 
-_ENGINE_KW = ("n_playouts", "c_puct", "temperature", "keep_search_tree", "use_puct", "use_probabilistic_actions",
+ENGINE_KW = ("n_playouts", "c_puct", "temperature", "keep_search_tree", "use_puct", "use_probabilistic_actions",
               "num_probabilistic_actions")
 
 
@@ -27,7 +27,7 @@ def arena_engine(game, n_slots, n_games, agent, opponent, opponent_sims=0, devic
     """An engine configured for evaluation games.  kwargs: the AlphaZeroBot keywords the reference passes through
     (n_playouts default 100: mcts.py:98; c_puct, temperature; dirichlet_ratio is accepted and unused: the test pairings
     construct the bot with use_dirichlet=False, game_utils.py:72)."""
-    kw = {k: kwargs[k] for k in _ENGINE_KW if k in kwargs}
+    kw = {k: kwargs[k] for k in ENGINE_KW if k in kwargs}
     if agent == "net":
         kw.update(n_playouts=1, keep_search_tree=False)
     else:
@@ -48,33 +48,12 @@ def run_arena(engine, evaluator, n_games, seed=None, check_every=16, use_graph=T
         engine.opponent_moves()
         evaluator(obs, pri, val)
 
-    ticks, graph = 0, None
+    drv = TickDriver(engine.device, tick)
     if use_graph:
-        torch.cuda.synchronize(engine.device)
-        side = torch.cuda.Stream(engine.device)
-        side.wait_stream(torch.cuda.current_stream(engine.device))
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                tick()
-                ticks += 1
-        torch.cuda.current_stream(engine.device).wait_stream(side)
-        torch.cuda.synchronize(engine.device)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            tick()
-    while True:
-        for _ in range(check_every):
-            if graph is not None:
-                graph.replay()
-            else:
-                tick()
-            ticks += 1
-        if engine.games_done() >= n_games:
-            break
-        if max_ticks is not None and ticks >= max_ticks:
-            raise EngineError("arena did not finish within %d ticks: %r" % (max_ticks, engine.progress()))
+        drv.capture()
+    tick_until(drv, check_every, lambda: engine.games_done() >= n_games, max_ticks, "arena", engine)
     prog = engine.progress()
-    prog["ticks"] = ticks
+    prog["ticks"] = drv.ticks
     ex = engine.export()
     return ex["game_ret0"].copy(), prog, ex
 
@@ -102,34 +81,13 @@ def run_duel(eng_a, eng_b, ev_a, ev_b, n_games, seed=None, check_every=16, use_g
         ev_a(*io_a)
         ev_b(*io_b)
 
-    ticks, graph = 0, None
-    dev = eng_a.device
+    drv = TickDriver(eng_a.device, tick)
     if use_graph:
-        torch.cuda.synchronize(dev)
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(2):
-                tick()
-                ticks += 1
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            tick()
-    while True:
-        for _ in range(check_every):
-            if graph is not None:
-                graph.replay()
-            else:
-                tick()
-            ticks += 1
-        if eng_a.games_done() >= n_games and eng_b.games_done() >= n_games:
-            break
-        if max_ticks is not None and ticks >= max_ticks:
-            raise EngineError("duel did not finish within %d ticks: %r / %r" % (max_ticks, eng_a.progress(), eng_b.progress()))
+        drv.capture()
+    tick_until(drv, check_every, lambda: eng_a.games_done() >= n_games and eng_b.games_done() >= n_games, max_ticks,
+               "duel", eng_a, eng_b)
     prog = eng_a.progress()
-    prog["ticks"] = ticks
+    prog["ticks"] = drv.ticks
     ex_a, ex_b = eng_a.export(), eng_b.export()
     if not ((ex_a["game_len"] == ex_b["game_len"]).all() and (ex_a["game_ret0"] == ex_b["game_ret0"]).all()):
         raise EngineError("the two engines of a duel disagree about the games they played")
@@ -141,11 +99,7 @@ def play_zero_vs_zero(policy_fn, policy_fn2, game_name, n_tests, settings1=None,
     """n_tests `test_zero_vs_zero` calls (2 games each: network 1 first, network 1 second) in one batch: two AlphaZero agents
     with their own networks and settings (n_playouts, c_puct, ...), both with root noise as in the reference
     (game_utils.py:131-132).  -> (score1 [n_tests], score2 [n_tests], progress), scores from network 1's point of view."""
-    from .mcts import _as_module
-    if device is None:
-        mod = _as_module(policy_fn)
-        device = next(mod.parameters()).device if mod is not None and next(mod.parameters()).is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
+    device = torch.device(device if device is not None else default_device(policy_fn))
     n_games = 2 * int(n_tests)
     if n_games > 4096:
         raise ValueError("at most 2048 tests per call (one game per slot)")
@@ -153,52 +107,30 @@ def play_zero_vs_zero(policy_fn, policy_fn2, game_name, n_tests, settings1=None,
     engines, evals = [], []
     try:
         for flip, (fn, settings) in enumerate(((policy_fn, settings1), (policy_fn2 if policy_fn2 is not None else policy_fn, settings2))):
-            kw = {k: v for k, v in dict(settings or {}).items() if k in _ENGINE_KW + ("dirichlet_ratio",)}
+            kw = {k: v for k, v in dict(settings or {}).items() if k in ENGINE_KW + ("dirichlet_ratio",)}
             kw.setdefault("n_playouts", 100)
             engines.append(SelfPlayEngine(game_name, n_games, max_games=n_games, device=device, seed=seed + 17 * flip,
                                           use_dirichlet=use_dirichlet, arena_agent="zero", opponent="external", arena_flip=bool(flip), **kw))
-            evals.append(_evaluator(fn, device, eval_backend, eval_precision, n_games))
+            evals.append(make_evaluator(fn, device, eval_backend, eval_precision, n_games))
         ret0, prog, _ = run_duel(engines[0], engines[1], evals[0], evals[1], n_games, seed=seed)
     finally:
-        for e in engines:
-            e.close()
-        for ev in evals:
-            if hasattr(ev, "close"):
-                ev.close()
+        close_all(*engines, *evals)
     s1, s2 = pair_scores(ret0)
     return s1, s2, prog
-
-
-def _evaluator(net_or_fn, device, backend, precision, n_slots):
-    from .mcts import _as_module
-    mod = _as_module(net_or_fn)
-    if mod is None:
-        raise TypeError("the device arena needs the network itself (an nn.Module or its bound .predict), not an arbitrary "
-                        "python policy_fn")
-    if backend == "fused":
-        from .fusednet import FusedNet
-        return FusedNet(mod, device, max_boards=n_slots, precision=precision)
-    return DeviceEvaluator(mod, device)
 
 
 def play_tests(policy_fn, game_name, n_tests, agent, opponent, opponent_sims=0, device=None, seed=None, n_slots=None,
                eval_backend="fused", eval_precision="f32x", **kwargs):
     """n_tests reference `test_*` calls (2 * n_tests games) in one batch -> (score1 [n_tests], score2 [n_tests], progress)."""
-    from .mcts import _as_module
-    if device is None:
-        mod = _as_module(policy_fn)
-        device = next(mod.parameters()).device if mod is not None and next(mod.parameters()).is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
+    device = torch.device(device if device is not None else default_device(policy_fn))
     n_games = 2 * int(n_tests)
     n_slots = int(n_slots or min(n_games, 4096))
     seed = int(np.random.randint(0, 2 ** 31 - 1)) if seed is None else int(seed)
     eng = arena_engine(game_name, n_slots, n_games, agent, opponent, opponent_sims, device=device, seed=seed, **kwargs)
-    ev = _evaluator(policy_fn, device, eval_backend, eval_precision, n_slots)
+    ev = make_evaluator(policy_fn, device, eval_backend, eval_precision, n_slots)
     try:
         ret0, prog, _ = run_arena(eng, ev, n_games)
     finally:
-        eng.close()
-        if hasattr(ev, "close"):
-            ev.close()
+        close_all(eng, ev)
     s1, s2 = pair_scores(ret0)
     return s1, s2, prog

@@ -494,6 +494,112 @@ class HostPolicyEvaluator:
         values_out.copy_(torch.from_numpy(val))
 
 
+def module_of(policy_fn):
+    """The nn.Module behind a policy_fn: the module itself or the owner of a bound `.predict`; None for any other callable."""
+    if isinstance(policy_fn, torch.nn.Module):
+        return policy_fn
+    owner = getattr(policy_fn, "__self__", None)
+    if isinstance(owner, torch.nn.Module) and getattr(policy_fn, "__name__", "") == "predict":
+        return owner
+    return None
+
+
+def default_device(policy_fn):
+    """Where to run when the caller names no device: the network's, if it has a parameter and that is on a GPU, else the
+    current HIP device."""
+    mod = module_of(policy_fn)
+    par = next(mod.parameters(), None) if mod is not None else None
+    return par.device if par is not None and par.is_cuda else torch.device("cuda", torch.cuda.current_device())
+
+
+def make_evaluator(net_or_fn, device, backend, precision, max_boards, dtype=torch.float32):
+    """The device evaluator of a network: backend "fused" = FusedNet (csrc/az_net.hip) at `precision` for up to max_boards
+    rows, anything else = DeviceEvaluator (torch forward) at `dtype`."""
+    mod = module_of(net_or_fn)
+    if mod is None:
+        raise TypeError("the device arena needs the network itself (an nn.Module or its bound .predict), not an arbitrary "
+                        "python policy_fn")
+    if backend == "fused":
+        from .fusednet import FusedNet
+        return FusedNet(mod, device, max_boards=max_boards, precision=precision)
+    return DeviceEvaluator(mod, device, dtype=dtype)
+
+
+def close_all(*things, drain=False):
+    """close() whatever has one (engines, FusedNets; a DeviceEvaluator and None have none), in the order given.
+    drain: wait for each thing's device first (a pool that raised leaves the others' enqueued batches behind)."""
+    for t in things:
+        if drain:
+            try:
+                torch.cuda.synchronize(t.device)
+            except Exception:
+                pass
+        if hasattr(t, "close"):
+            t.close()
+
+
+# ---------------------------------------------------------------------- the tick loop
+class TickDriver:
+    """Enqueues ticks on the current stream, eagerly or as replays of a captured HIP graph, and counts them.
+    tick: zero-argument callable, what one tick launches (e.g. [az_engine_advance, PV-net forward])."""
+
+    def __init__(self, device, tick):
+        self.device, self.tick = device, tick
+        self.ticks = 0
+        self.graph, self.tpg = None, 1  # tpg: ticks per graph
+
+    def _eager(self, n):
+        for _ in range(n):
+            self.tick()
+        self.ticks += n
+
+    def _capture(self):
+        torch.cuda.synchronize(self.device)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            for _ in range(self.tpg):
+                self.tick()
+
+    def capture(self, ticks_per_graph=1):
+        """From now on run() replays a graph of ticks_per_graph ticks.  Two eager ticks first, on a side stream: MIOpen /
+        workspace allocation and the kernels' first-use attribute calls must happen outside capture."""
+        self.tpg = max(1, int(ticks_per_graph))
+        main = torch.cuda.current_stream(self.device)
+        torch.cuda.synchronize(self.device)
+        side = torch.cuda.Stream(self.device)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            self._eager(2)
+        main.wait_stream(side)
+        self._capture()
+
+    def recapture(self):
+        """Capture again after what tick() launches has changed (a new row count).  One eager tick first: new kernel
+        variants set their attributes on first use, which must not happen inside a capture."""
+        self._eager(1)
+        self._capture()
+
+    def run(self, n):
+        """n ticks' worth: n eager ticks, or max(1, n // ticks_per_graph) replays."""
+        if self.graph is None:
+            return self._eager(n)
+        for _ in range(max(1, n // self.tpg)):
+            self.graph.replay()
+            self.ticks += self.tpg
+
+
+def tick_until(driver, check_every, done, max_ticks, what, *engines):
+    """driver.run(check_every) until done() says so after a batch; EngineError with the engines' progress once
+    driver.ticks >= max_ticks (None: no limit)."""
+    while True:
+        driver.run(check_every)
+        if done():
+            return
+        if max_ticks is not None and driver.ticks >= max_ticks:
+            raise EngineError("%s did not finish within %d ticks: %s"
+                              % (what, max_ticks, " / ".join(repr(e.progress()) for e in engines)))
+
+
 def slot_groups(n_slots, k):
     """Split [0, n_slots) into k contiguous groups whose sizes are multiples of 8 (a tower workgroup evaluates 8 boards)."""
     per = -(-n_slots // max(1, int(k)))
@@ -561,8 +667,6 @@ def selfplay_steps(engine, evaluator, n_games, seed=None, check_every=32, max_ti
     the final progress dict is the generator's return value."""
     engine.reset(n_games, seed)
     obs, pri, val = engine.alloc_io()
-    ticks = 0
-    graph = None
     n_first = min(int(n_games), engine.G)  # games handed out by the reset
     levels = _tail_levels(engine.G) if (compact_tail and on_tick is None) else []
     rows = None  # None: one row per slot
@@ -575,39 +679,23 @@ def selfplay_steps(engine, evaluator, n_games, seed=None, check_every=32, max_ti
             engine.advance_rows(rows, pri, val, obs)
             evaluator(obs[:rows], pri[:rows], val[:rows])
 
+    drv = TickDriver(engine.device, tick)
     if use_graph:
-        # one tick = [az_advance_kernel, net.forward] replayed as a HIP graph
-        torch.cuda.synchronize(engine.device)
-        side = torch.cuda.Stream(engine.device)
-        side.wait_stream(torch.cuda.current_stream(engine.device))
-        with torch.cuda.stream(side):
-            for _ in range(2):  # warm-up (MIOpen / workspace allocation must happen outside capture)
-                tick()
-                ticks += 1
-        torch.cuda.current_stream(engine.device).wait_stream(side)
-        torch.cuda.synchronize(engine.device)
         # several ticks per captured graph: fewer graph-boundary bubbles on the stream (+2-3 % games/s at 8-16)
-        tpg = 1 if on_tick is not None else max(1, min(int(ticks_per_graph), check_every))
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            for _ in range(tpg):
-                tick()
+        drv.capture(1 if on_tick is not None else min(int(ticks_per_graph), check_every))
     compactions = 0
     while True:
-        for _ in range(check_every if graph is None else max(1, check_every // tpg)):
-            if graph is not None:
-                graph.replay()
-                ticks += tpg
-            else:
-                tick()
-                ticks += 1
-            if on_tick is not None:
-                on_tick(engine, ticks)
-        yield ticks  # (a driver of several engines enqueues the others' batches here)
+        if on_tick is None:
+            drv.run(check_every)
+        else:
+            for _ in range(check_every):
+                drv.run(1)
+                on_tick(engine, drv.ticks)
+        yield drv.ticks  # (a driver of several engines enqueues the others' batches here)
         done = engine.games_done()
         if done >= n_games:
             break
-        if max_ticks is not None and ticks >= max_ticks:
+        if max_ticks is not None and drv.ticks >= max_ticks:
             raise EngineError("self-play did not finish within %d ticks: %r" % (max_ticks, engine.progress()))
         # the tail: every game handed out (a finished slot took the next id until they ran out) and few slots still playing
         if levels and min(n_games, n_first + done) >= n_games and n_games - done <= levels[0]:
@@ -615,16 +703,10 @@ def selfplay_steps(engine, evaluator, n_games, seed=None, check_every=32, max_ti
             while levels and live <= levels[0]:
                 rows = levels.pop(0)
             compactions += 1
-            if graph is not None:  # re-capture for the new row count (one eager tick first: new kernel variants set their
-                tick()             # attributes on first use, which must not happen inside a capture)
-                ticks += 1
-                torch.cuda.synchronize(engine.device)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    for _ in range(tpg):
-                        tick()
+            if drv.graph is not None:
+                drv.recapture()  # for the new row count
     prog = engine.progress()
-    prog["ticks"] = ticks
+    prog["ticks"] = drv.ticks
     prog["tail_compactions"] = compactions
     return prog
 
@@ -673,6 +755,10 @@ class OverlappedTicker:
                     self._tick(i)
         self.ticks += 1
 
+    def run(self, n):
+        for _ in range(n):
+            self.tick()
+
     def synchronize(self):
         for st in self.streams:
             st.synchronize()
@@ -682,14 +768,12 @@ def _run_selfplay_overlapped(engine, evaluators, n_games, seed, check_every, max
     engine.reset(n_games, seed)
     torch.cuda.current_stream(engine.device).synchronize()
     tk = OverlappedTicker(engine, evaluators, overlap, use_graph=use_graph)
-    while True:
-        for _ in range(check_every):
-            tk.tick()
+
+    def done():
         tk.synchronize()
-        if engine.games_done() >= n_games:
-            break
-        if max_ticks is not None and tk.ticks >= max_ticks:
-            raise EngineError("self-play did not finish within %d ticks: %r" % (max_ticks, engine.progress()))
+        return engine.games_done() >= n_games
+
+    tick_until(tk, check_every, done, max_ticks, "self-play", engine)
     prog = engine.progress()
     prog["ticks"] = tk.ticks
     return prog

@@ -12,8 +12,8 @@ import copy
 import numpy as np
 import torch
 
-from .engine import (DeviceEvaluator, EngineError, SelfPlayEngine, examples_from_export, run_selfplay,
-                     slot_groups, unpack_device_export)
+from .engine import (EngineError, SelfPlayEngine, close_all, examples_from_export, make_evaluator, run_selfplay,
+                     run_selfplay_pools, slot_groups, unpack_device_export)
 from .games import Game
 from . import distributed as azdist
 
@@ -92,7 +92,6 @@ class ExampleGenerator:
     def _play_pools(self, n_games, devices):
         """One engine + evaluator per pool, each on its device, driven from this thread (engine.run_selfplay_pools); the pools'
         packed records are brought to self.device and laid out like the ranks of an all-gather."""
-        from .engine import run_selfplay_pools
         n_each = int(n_games / len(devices))
         if n_each < 1:
             raise ValueError("n_games=%d is fewer than the %d pools" % (n_games, len(devices)))
@@ -103,11 +102,8 @@ class ExampleGenerator:
                 with torch.cuda.device(dev):
                     engines.append(SelfPlayEngine(self.game, n_slots, max_games=n_each, device=dev,
                                                   seed=self.seed + 1000003 * self._generation + 7919 * i, **self._engine_kwargs()))
-                    if self.eval_backend == "fused":
-                        from .fusednet import FusedNet
-                        evaluators.append(FusedNet(self.net, dev, max_boards=n_slots, precision=self.eval_precision))
-                    else:
-                        evaluators.append(DeviceEvaluator(copy.deepcopy(self.net), dev, dtype=self.eval_dtype))
+                    net = self.net if self.eval_backend == "fused" else copy.deepcopy(self.net)  # a torch pool gets its own copy
+                    evaluators.append(make_evaluator(net, dev, self.eval_backend, self.eval_precision, n_slots, self.eval_dtype))
             progs = run_selfplay_pools(engines, evaluators, n_each, use_graph=self.use_graph)
             self.last_progress = _sum_progress(progs)
             bufs = []
@@ -118,15 +114,8 @@ class ExampleGenerator:
                 bufs.append(b.to(self.device))
             dims = (engines[0].max_plies, engines[0].max_children)
         finally:
-            for e in engines:  # (a pool that raised leaves the others' enqueued batches behind: let every device drain first)
-                try:
-                    torch.cuda.synchronize(e.device)
-                except Exception:
-                    pass
-                e.close()
-            for ev in evaluators:
-                if hasattr(ev, "close"):
-                    ev.close()
+            close_all(*engines, drain=True)  # a pool that raised leaves the others' enqueued batches behind
+            close_all(*evaluators)
         self._generation += 1
         return torch.cat(bufs), bufs[0].numel(), n_each, len(devices), dims
 
@@ -154,21 +143,15 @@ class ExampleGenerator:
         evaluators = []
         try:
             sizes = [n for _, n in slot_groups(n_slots, self.overlap)] if self.overlap > 1 else [n_slots]
-            if self.eval_backend == "fused":
-                from .fusednet import FusedNet
-                evaluators = [FusedNet(self.net, self.device, max_boards=n, precision=self.eval_precision) for n in sizes]
-            else:
-                evaluators = [DeviceEvaluator(self.net, self.device, dtype=self.eval_dtype) for _ in sizes]
+            evaluators = [make_evaluator(self.net, self.device, self.eval_backend, self.eval_precision, n, self.eval_dtype)
+                          for n in sizes]
             self.last_progress = run_selfplay(engine, evaluators if self.overlap > 1 else evaluators[0], n_local,
                                               use_graph=self.use_graph, overlap=self.overlap)
             buf = engine.export_device()
             dims = (engine.max_plies, engine.max_children)
             torch.cuda.current_stream(self.device).synchronize()
         finally:
-            engine.close()
-            for ev in evaluators:
-                if hasattr(ev, "close"):
-                    ev.close()
+            close_all(engine, *evaluators)
         self._generation += 1
         return azdist.all_gather_device_exports(buf), buf.numel(), n_local, world, dims
 
@@ -218,8 +201,7 @@ class ExampleGenerator:
         if world > 1:
             self.net = self.net.to(self.device)
             azdist.broadcast_net(self.net, src=0)
-        kw = {k: self.kwargs[k] for k in ("n_playouts", "c_puct", "temperature", "keep_search_tree", "use_puct",
-                                          "use_probabilistic_actions", "num_probabilistic_actions") if k in self.kwargs}
+        kw = {k: self.kwargs[k] for k in arena.ENGINE_KW if k in self.kwargs}
         statistics = [None] * n_local  # the pairings against bots return no statistics (game_utils.py:65,83)
         if name == "test_zero_vs_zero" and self.generate_statistics:
             # both search trees after every move (game_utils.py:29-31): the reference's own per-game loop over façade bots,

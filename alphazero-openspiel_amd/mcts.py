@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import DeviceEvaluator, SelfPlayEngine
+from .engine import DeviceEvaluator, SelfPlayEngine, default_device, module_of
 from .games import Game, State
 
 
@@ -52,15 +52,6 @@ def _tree_to_nodes(tree):
     return nodes[0]
 
 
-def _as_module(policy_fn):
-    if isinstance(policy_fn, torch.nn.Module):
-        return policy_fn
-    owner = getattr(policy_fn, "__self__", None)
-    if isinstance(owner, torch.nn.Module) and getattr(policy_fn, "__name__", "") == "predict":
-        return owner
-    return None
-
-
 class MCTS:
     def __init__(self, policy_fn, num_distinct_actions, c_puct=2.5, n_playouts=100, use_dirichlet=True,
                  dirichlet_ratio=0.25, use_puct=True, **kwargs):
@@ -85,17 +76,14 @@ class MCTS:
         game = state.get_game() if hasattr(state, "get_game") else state._game
         if not isinstance(game, Game):
             game = Game(str(game))
-        dev = self.device
-        if dev is None:
-            mod = _as_module(self.policy_fn)
-            dev = next(mod.parameters()).device if mod is not None else torch.device("cuda", torch.cuda.current_device())
+        dev = self.device if self.device is not None else default_device(self.policy_fn)
         self._game = game
         self._engine = SelfPlayEngine(game, 1, n_playouts=self.n_playouts, c_puct=self.c_puct,
                                       use_dirichlet=self.use_dirichlet, dirichlet_ratio=self.dirichlet_ratio,
                                       keep_search_tree=True, manual_moves=True, rng="injected", device=dev,
                                       use_puct=self.use_puct, max_games=1, max_sims_per_tick=max(32, self.n_playouts))
         self._io = self._engine.alloc_io()
-        mod = _as_module(self.policy_fn)
+        mod = module_of(self.policy_fn)
         self._evaluator = DeviceEvaluator(mod, self._engine.device) if mod is not None else None
 
     def _restart(self, history):

@@ -251,3 +251,69 @@ def test_arena_configuration_errors():
     with pytest.raises(E.EngineError):
         eng.opponent_moves()                                                                      # not an arena engine
     eng.close()
+
+
+def _ticks_expected(T, check_every, use_graph):
+    """What run_arena / run_duel report when the games are over after T ticks: they poll after every check_every ticks, and with
+    use_graph the 2 warm-up ticks (real ticks, counted) come before the first batch."""
+    warm = 2 if use_graph else 0
+    return warm + check_every * -(-(T - warm) // check_every)
+
+
+def _graph_and_eager_runs(play, check_every):
+    """play(use_graph, check_every) -> (ret0, prog, ex).  T, the ticks the games need, comes from an eager run that polls after
+    every tick; the eager and the graph run at check_every must then give the same games and exactly _ticks_expected.
+    The engines are built with chain_window_us=-1: the time window for chained playouts (az_engine.hip, "scheduling only") is
+    the one thing that lets the work of a tick, and so T, depend on timing."""
+    _, prog, _ = play(False, 1)
+    T = prog["ticks"]
+    assert T > 2 * check_every
+    runs = {g: play(g, check_every) for g in (False, True)}
+    for g, (ret0, prog, ex) in runs.items():
+        print("use_graph=%s: T=%d ticks=%d" % (g, T, prog["ticks"]))
+        assert prog["error_flags"] == 0
+        assert prog["ticks"] == _ticks_expected(T, check_every, g), (g, T, prog["ticks"])
+    assert (runs[True][0] == runs[False][0]).all() and (runs[True][2]["game_len"] == runs[False][2]["game_len"]).all()
+    assert (runs[True][2]["move"] == runs[False][2]["move"]).all()
+
+
+def test_arena_with_a_captured_graph_plays_the_eager_games_and_counts_its_warm_up_ticks():
+    from alphazero_openspiel_amd import arena, engine as E, fusednet
+    net = _ckpt("connect_four", [3, 6, 7], 7)
+    n_slots, n_games = 16, 40
+
+    def play(use_graph, check_every):
+        eng = E.SelfPlayEngine("connect_four", n_slots, max_games=n_games, device=0, seed=11, use_dirichlet=False, n_playouts=16,
+                               arena_agent="zero", opponent="uct", opponent_sims=20, chain_window_us=-1)  # = arena.arena_engine
+        ev = fusednet.FusedNet(net, "cuda:0", max_boards=n_slots, precision="f32x")
+        try:
+            ret0, prog, ex = arena.run_arena(eng, ev, n_games, use_graph=use_graph, check_every=check_every)
+        finally:
+            eng.close()
+            ev.close()
+        assert prog["games_done"] == n_games
+        return ret0, prog, ex
+
+    _graph_and_eager_runs(play, 8)
+
+
+def test_duel_with_a_captured_graph_plays_the_eager_games_and_counts_its_warm_up_ticks():
+    from alphazero_openspiel_amd import arena, engine as E, fusednet
+    from alphazero_openspiel_amd.network import Net
+    net = _ckpt("connect_four", [3, 6, 7], 7)
+    torch.manual_seed(0)
+    other = Net([3, 6, 7], 7)  # untrained
+    n_games = 16
+
+    def play(use_graph, check_every):
+        kw = dict(max_games=n_games, device=0, use_dirichlet=False, arena_agent="zero", opponent="external", chain_window_us=-1)
+        ea = E.SelfPlayEngine("connect_four", n_games, n_playouts=16, c_puct=2.5, seed=1, arena_flip=False, **kw)
+        eb = E.SelfPlayEngine("connect_four", n_games, n_playouts=12, c_puct=1.5, seed=2, arena_flip=True, **kw)
+        evs = [fusednet.FusedNet(m, "cuda:0", max_boards=n_games, precision="f32x") for m in (net, other)]
+        try:
+            return arena.run_duel(ea, eb, evs[0], evs[1], n_games, seed=5, use_graph=use_graph, check_every=check_every)
+        finally:
+            for x in (ea, eb, evs[0], evs[1]):
+                x.close()
+
+    _graph_and_eager_runs(play, 8)
