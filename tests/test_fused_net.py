@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from net_cases import drifted_net
 from alphazero_openspiel_amd import fusednet, games
 from alphazero_openspiel_amd.network import Net, load_npz_checkpoint, state_to_board
 
@@ -60,9 +61,27 @@ def _nets():
     }
 
 
-@pytest.mark.parametrize("tag", ["c4_ckpt", "bt6_ckpt", "c4_10block", "bt5x4_3block", "bt4x5_2block"])
+def _drifted_nets():
+    """Nets with per-channel BatchNorm statistics (net_cases.drifted_net): pack_net's (scale, shift) rows differ by channel."""
+    c4 = games.load_game("connect_four")
+    return {
+        "c4_2block_drifted": (c4, drifted_net([3, 6, 7], 7, 2, 50, seed=21)),
+        "bt4x5_2block_drifted": (games.load_game("breakthrough(rows=4,columns=5)"), drifted_net([3, 4, 5], 240, 2, 40, seed=22)),
+        # conv weights three times as large: tower maxima near 30
+        "c4_3block_w3_drifted": (c4, drifted_net([3, 6, 7], 7, 3, 50, seed=23, w_scale=3.0)),
+    }
+
+
+def _net(tag):
+    return (_drifted_nets() if tag.endswith("_drifted") else _nets())[tag]
+
+
+DRIFTED = ["c4_2block_drifted", "bt4x5_2block_drifted", "c4_3block_w3_drifted"]
+
+
+@pytest.mark.parametrize("tag", ["c4_ckpt", "bt6_ckpt", "c4_10block", "bt5x4_3block", "bt4x5_2block"] + DRIFTED)
 def test_packing_emulation_matches_torch(tag):
-    game, net = _nets()[tag]
+    game, net = _net(tag)
     boards = _random_boards(game, 5, 1)
     with torch.no_grad():
         p, v = net(torch.from_numpy(boards))
@@ -72,11 +91,11 @@ def test_packing_emulation_matches_torch(tag):
     assert np.abs(ve - v.numpy()[:, 0]).max() <= V_TOL
 
 
-@pytest.mark.parametrize("tag", ["c4_ckpt", "bt6_ckpt", "bt4x5_2block"])
+@pytest.mark.parametrize("tag", ["c4_ckpt", "bt6_ckpt", "bt4x5_2block"] + DRIFTED)
 def test_split_packing_emulation_is_fp32_grade(tag):
     """The (hi, lo) fp16 pairs of the f16x3 path carry the weights to ~22 bits: the numpy emulation of the kernel's data
     movement with those pairs agrees with torch fp64 about as well as torch fp32 does."""
-    game, net = _nets()[tag]
+    game, net = _net(tag)
     boards = _random_boards(game, 5, 1)
     import copy
     with torch.no_grad():
