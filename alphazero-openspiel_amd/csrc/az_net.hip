@@ -163,11 +163,28 @@ static inline uint16_t abi_weight(const uint16_t *src, int c, int co, int tap, i
     return src[(size_t)c * AZ_NET_KSTEPS * 2048 + ((((size_t)oks * 4 + mt) * 64 + olane) * 8) + (ch & 7)];
 }
 
+// K grouping of the device weight streams: which weight is element j of group q (= lane >> 4) of k-step ks of conv c - its tap
+// and input channel, or false: a zero.  Conv 0 sees the input planes only (channel octet 0): group g = 4 ks + q < 9 = tap g.
+// The 15-k-step convs (<= 50 filters): group g < 54: (tap, octet) = divmod(g, 6), the 48 channels of six full octets; 54, 55:
+// zero; k-step 14, the gather k-step: element j of group q < 3 is channel 48 + (j & 1) at tap 4 q + j / 2 (taps > 8: zero).
+static bool k_group(int c, int ks, int q, int j, int &tap, int &ch) {
+    const int g = 4 * ks + q;
+    if (c == 0) tap = g, ch = j;
+    else if (ks < X3B::NKS - 1) tap = g / 6, ch = 8 * (g % 6) + j;
+    else tap = 4 * q + (j >> 1), ch = 48 + (j & 1);
+    return (c && ks == X3B::NKS - 1) ? (q < 3 && tap < 9) : g < (c ? 54 : 9);
+}
+// its fp16 bits for output channel co, from the interchange layout
+static inline uint16_t grouped_weight(const uint16_t *src, int c, int co, int ks, int q, int j) {
+    int tap, ch;
+    return k_group(c, ks, q, j, tap, ch) ? abi_weight(src, c, co, tap, ch) : 0;
+}
+
 // Device weight stream of az_tower_kernel, az_tower_f16c_kernel and az_tower_x3_kernel: [conv 0 compacted to AZ_NET_K0STEPS
 // k-steps][conv 1 ..][..], one RECORD per k-step: output-channel tiles 0..2 as in the ABI layout (3 KiB), tile 3 with only its
-// stored rows (see WRec).  Conv 0 sees the input planes only (channel octet 0), i.e. ABI groups 7*tap; they become groups 0..8 of
-// its 4 k-steps.  <= 50 filters (r3 < 16): the K dimension is re-grouped into 15 k-steps - channels 48, 49 of the nine taps fit
-// ONE k-step instead of filling the seventh channel octet of every tap.
+// stored rows (see WRec).  Conv 0's ABI groups 7 * tap become groups 0..8 of its 4 k-steps.  <= 50 filters (r3 < 16): the K
+// dimension is re-grouped into 15 k-steps - channels 48, 49 of the nine taps fit ONE k-step instead of filling the seventh
+// channel octet of every tap (k_group).
 static void build_records(const unsigned char *src, int r3, int n_convs, std::vector<unsigned char> &dev) {
     const bool l15 = r3 < 16;
     const int nks = l15 ? 15 : AZ_NET_KSTEPS;
@@ -181,48 +198,20 @@ static void build_records(const unsigned char *src, int r3, int n_convs, std::ve
             for (int r = 0; r < (r3 < 16 ? r3 : 16); r++)
                 memcpy(dst + 3 * 1024 + (q * rows + r) * 16, ks4k + 3 * 1024 + (q * 16 + r) * 16, 16);
     };
-    // ABI: element j of group g = tap * 7 + c8 is channel 8 * c8 + j at that tap.  abi_half: one fp16 of a conv
-    auto abi_half = [&](int c, int mt, int l15_, int tap, int ch) -> uint16_t {
-        int g = tap * 7 + (ch >> 3), oks = g >> 2, olane = (g & 3) * 16 + l15_;
-        const uint16_t *w = (const uint16_t *)(src + (size_t)c * conv_b);
-        return w[((((size_t)oks * 4 + mt) * 64 + olane) * 8) + (ch & 7)];
-    };
-    std::vector<unsigned char> c0(AZ_NET_K0STEPS * 4096, 0); // conv 0 compacted, still in 4 KiB k-steps
-    for (int ks = 0; ks < AZ_NET_K0STEPS; ks++)
-        for (int mt = 0; mt < 4; mt++)
-            for (int lane = 0; lane < 64; lane++) {
-                int g = 4 * ks + (lane >> 4);
-                if (g >= 9) continue;
-                int go = 7 * g, oks = go >> 2, olane = (go & 3) * 16 + (lane & 15);
-                memcpy(&c0[(((size_t)ks * 4 + mt) * 64 + lane) * 16], src + (((size_t)oks * 4 + mt) * 64 + olane) * 16, 16);
-            }
-    size_t off = 0;
-    for (int ks = 0; ks < AZ_NET_K0STEPS; ks++, off += rec) put_record(&dev[off], &c0[(size_t)ks * 4096]);
     std::vector<uint16_t> k4(4096 / 2);
+    auto put_grouped = [&](unsigned char *dst, int c, int ks) { // k-step ks of conv c in k_group's grouping
+        for (int mt = 0; mt < 4; mt++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int j = 0; j < 8; j++)
+                    k4[((size_t)mt * 64 + lane) * 8 + j] = grouped_weight((const uint16_t *)src, c, 16 * mt + (lane & 15), ks, lane >> 4, j);
+        put_record(dst, (const unsigned char *)k4.data());
+    };
+    size_t off = 0;
+    for (int ks = 0; ks < AZ_NET_K0STEPS; ks++, off += rec) put_grouped(&dev[off], 0, ks);
     for (int c = 1; c < n_convs; c++)
         for (int ks = 0; ks < nks; ks++, off += rec) {
-            if (!l15) {
-                put_record(&dev[off], src + (size_t)c * conv_b + (size_t)ks * 4096);
-                continue;
-            }
-            // 15-k-step grouping: group g' = 4 ks + q.  g' < 54: (tap, octet) = divmod(g', 6), the 48 channels of six
-            // full octets; g' = 54, 55: zero; k-step 14: element j of group q < 3 is channel 48 + (j & 1) at tap
-            // 4 q + j / 2 (taps > 8: zero), group 3 zero.
-            std::fill(k4.begin(), k4.end(), (uint16_t)0);
-            for (int mt = 0; mt < 4; mt++)
-                for (int lane = 0; lane < 64; lane++) {
-                    const int q = lane >> 4, l = lane & 15, gp = 4 * ks + q;
-                    uint16_t *o = &k4[(((size_t)mt * 64) + lane) * 8];
-                    for (int j = 0; j < 8; j++) {
-                        if (ks < 14) {
-                            if (gp < 54) o[j] = abi_half(c, mt, l, gp / 6, 8 * (gp % 6) + j);
-                        } else if (q < 3) {
-                            int tap = 4 * q + (j >> 1);
-                            if (tap < 9) o[j] = abi_half(c, mt, l, tap, 48 + (j & 1));
-                        }
-                    }
-                }
-            put_record(&dev[off], (const unsigned char *)k4.data());
+            if (l15) put_grouped(&dev[off], c, ks);
+            else put_record(&dev[off], src + (size_t)c * conv_b + (size_t)ks * 4096);
         }
 }
 // the records of conv_w (f16x3: per k-step the hi record, then the lo record) + a chunk of padding: the last (short) chunk is
@@ -300,25 +289,11 @@ static bool build_x3_stream(const X3Stream &L, const uint16_t *hi_abi, const uin
         for (int lane = 0; lane < 64; lane++)
             for (int j = 0; j < 8; j++) o[lane * 8 + j] = f(lane >> 4, lane & 15, j);
     };
-    // K grouping of the 15-k-step convs: group 4 ks + q < 54 = (tap, octet) = divmod(., 6); 54, 55 zero; k-step 14 = the gather
-    // k-step: element j of group q < 3 is channel 48 + (j & 1) at tap 4 q + j / 2
-    auto main_val = [&](const uint16_t *src, int c, int co, int ks, int q, int j) -> uint16_t {
-        if (c == 0) { // conv 0: group g < 9 = tap g of octet 0 (the input planes)
-            const int g = 4 * ks + q;
-            return g < 9 ? abi_weight(src, 0, co, g, j) : 0;
-        }
-        if (ks < 14) {
-            const int gp = 4 * ks + q;
-            return gp < 54 ? abi_weight(src, c, co, gp / 6, 8 * (gp % 6) + j) : 0;
-        }
-        const int tap = 4 * q + (j >> 1);
-        return (q < 3 && tap < 9) ? abi_weight(src, c, co, tap, 48 + (j & 1)) : 0;
-    };
     auto put_record = [&](size_t off, int c, int ks) { // [hi mt 0..2][lo mt 0..2]
         for (int part = 0; part < 2; part++)
             for (int mt = 0; mt < 3; mt++)
                 put_frag(off + (size_t)(part * 3 + mt) * FR,
-                         [&](int q, int l, int j) { return main_val(part ? lo : hi, c, 16 * mt + l, ks, q, j); });
+                         [&](int q, int l, int j) { return grouped_weight(part ? lo : hi, c, 16 * mt + l, ks, q, j); });
     };
     // tile T: rows 0..3 = hi 48, hi 49, lo 48, lo 49 of a shifted-B k-step (conv 0's k-steps, the gather k-step);
     //         rows 4..7 = hi 48, hi 49, lo 48, lo 49 of the centre tap over input channels 0..47 (k-steps 6, 7)
@@ -329,7 +304,7 @@ static bool build_x3_stream(const X3Stream &L, const uint16_t *hi_abi, const uin
             if (l < l0 || l >= l0 + 4) return 0;
             const uint16_t *src = (l - l0) < 2 ? hi : lo;
             const int co = 48 + ((l - l0) & 1);
-            if (!centre) return main_val(src, c, co, ks, q, j);
+            if (!centre) return grouped_weight(src, c, co, ks, q, j);
             const int gp = 4 * ks + q; // groups 24..29 = (tap 4, octet 0..5); 30, 31 belong to tap 5: zero rows here
             return gp < 30 ? abi_weight(src, c, co, 4, 8 * (gp - 24) + j) : 0;
         });
@@ -435,6 +410,13 @@ static std::vector<uint16_t> repack_fc(const uint16_t *src, int n_ot, int fc_kst
     return dst;
 }
 
+// v_mfma instructions of one column tile in a conv on the x3b scheme (conv 0 / a later conv): what its k-steps multiply (X3BK)
+template <bool IS_FIRST> static constexpr int x3b_mfma_per_tile() {
+    int n = 0;
+    for (int ks = 0; ks < X3BK<IS_FIRST, 1>::NKSC; ks++) n += X3BK<IS_FIRST, 1>::n_mfma(ks);
+    return n;
+}
+static_assert(x3b_mfma_per_tile<false>() == 147, "az_tower_x3b.h: 147 against 180");
 // v_mfma instructions one wave (= one board) of az_tower_x3_kernel issues (az_tower_x3.h: 3 per product, every tile)
 static double x3_mfma_per_wave(int nt, int n_convs, int nks) { return 3.0 * (AZ_NET_K0STEPS + (double)(n_convs - 1) * nks) * 4 * nt; }
 
@@ -927,8 +909,7 @@ extern "C" int az_net_issued_mfma_per_board(const az_net *n, int32_t n_boards, d
     const ForwardPlan p = plan_forward(n, n_boards);
     const int n_convs = 2 * n->d.n_blocks, nks = n->r3 < 16 ? 15 : AZ_NET_KSTEPS;
     const double head = (double)n->n_ot * n->fc_ksteps / 16.0; // one MFMA per (output tile, k-step) per 16 boards
-    // a column tile on the x3b scheme: conv 0: 4 k-steps x (9 + 2 T); then 15 x 9 + 2 x (2 T + 3 X) + 2 T (gather k-step)
-    const double per_tile = AZ_NET_K0STEPS * 11 + (double)(n_convs - 1) * (15 * 9 + 2 * 5 + 2);
+    const double per_tile = x3b_mfma_per_tile<true>() + (double)(n_convs - 1) * x3b_mfma_per_tile<false>();
     switch (p.kind) {
     case TowerKind::F16: {
         const int nt = p.g.nt < 3 ? 3 : (p.g.nt > 3 ? 4 : 3);

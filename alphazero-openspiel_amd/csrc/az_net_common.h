@@ -189,6 +189,26 @@ struct X3B {
     static constexpr int OFF_ACT = OFF_S + 4 * S_WAVE;
     static constexpr int LDS = OFF_ACT + 4 * 2 * LO_OFF;
     static constexpr int tap_of_plane(int t) { return t < 4 ? t : t + 1; } // planes 0..7 = taps 0,1,2,3,5,6,7,8 (plane 8 = tap 4)
+    // the weight stream in DMA pieces of 1 KiB.  Chunk 0 = conv 0 (PART -1), chunk c >= 1 = part (c - 1) % PARTS of conv 1 + (c - 1) / PARTS
+    template <int PART> static constexpr int n_pieces() { return (PART < 0 ? C0_B : x3b_part_bytes(PART < 0 ? 0 : PART)) / 1024; }
+    template <int PART> static constexpr size_t chunk_off(int c) { // byte offset of chunk c (a chunk past the stream: its zero padding, az_net.hip)
+        return PART < 0 ? 0 : (size_t)C0_B + (size_t)((c - 1) / PARTS) * CONV_B + x3b_part_off(PART < 0 ? 0 : PART);
+    }
+    // in-chunk offset of the extra fragments (T, then X hi, X lo) of k-step ks: they sit behind the chunk's records
+    static constexpr int extra_off(bool is_first, int ks) {
+        return is_first ? AZ_NET_K0STEPS * REC2 + ks * FR : (ks / CK == 1 ? 4 * REC2 + (ks - 6) * 3 * FR : 3 * REC2);
+    }
+};
+// what k-step ks (index in its conv) of the x3b scheme multiplies besides tiles 0..2, how many MFMAs that is per column tile,
+// and how many fragment reads a wave that holds NT column tiles whole needs
+template <bool IS_FIRST, int NT> struct X3BK {
+    static constexpr int NKSC = IS_FIRST ? AZ_NET_K0STEPS : X3B::NKS;
+    static constexpr bool has_t(int ks) { return IS_FIRST || ks == 6 || ks == 7 || ks == X3B::NKS - 1; }
+    static constexpr bool has_x(int ks) { return !IS_FIRST && (ks == 6 || ks == 7); }
+    static constexpr bool is_gather(int ks) { return !IS_FIRST && ks == X3B::NKS - 1; }
+    static constexpr int n_mfma(int ks) { return 9 + (has_t(ks) ? 2 : 0) + (has_x(ks) ? 3 : 0); } // three per product of tiles 0..2, T x (B_hi, B_lo), X
+    static constexpr int n_a(int ks) { return 6 + (has_t(ks) ? 1 : 0) + (has_x(ks) ? 2 : 0); } // ah 0..2, al 0..2, T, X hi, X lo
+    static constexpr int n_b(int ks) { return is_gather(ks) ? 8 * NT : 2 * NT; }
 };
 static_assert(X3B::LDS <= 160 * 1024, "x3b LDS budget");
 static_assert(X3B::C0_B <= X3B::CHUNK_S, "conv 0 must fit a chunk buffer");
@@ -215,6 +235,7 @@ struct X3D {
     static constexpr int OFF_S = OFF_EPI + 2048 + 256 * 16; // scratch: [9 tap planes][columns][2 channels] fp32
     static constexpr int tap_of_plane(int t) { return t < 4 ? t : t + 1; }
 };
+static_assert(X3D::NKS == X3B::NKS && X3D::FR == X3B::FR, "one scheme (X3BK), two chunkings");
 static_assert(x3d_part_bytes(2) <= X3D::CHUNK_S && X3D::C0_PART_B <= X3D::CHUNK_S && X3D::CONV_B == 15 * 6144 + 7 * 1024, "every part fits a chunk buffer");
 
 // compile-time loop: f(std::integral_constant<int, 0>{}), ..., f(std::integral_constant<int, N - 1>{})

@@ -25,27 +25,20 @@
 // Since round 4 a tile has ONE accumulator (az_net_common.h: split_pair_planes): the device copy of the weights carries 2048 in both
 // halves and the planes keep the lo half unscaled, so the three MFMAs of a product add into the same registers; an accumulator
 // holds 2048 x the conv, the epilogue scales it back (exactly).
-// Everything else is az_tower_x3_kernel's: one workgroup = 4 waves (one per SIMD), one board per wave, hi and lo
+// The arithmetic of this scheme - prologue, the operands of every MFMA pass, the terms of channels 48, 49, the epilogue - is
+// az_tower_x3b_parts.h, the one copy az_tower_x3c_kernel and az_tower_x3d_kernel call too; this file is the schedule of a board per wave.
+// The shape is az_tower_x3_kernel's: one workgroup = 4 waves (one per SIMD), one board per wave, hi and lo
 // activation planes, fp32 residual stream in registers, fp32 epilogues that split their result into (hi, lo) again.
 // The compact plane of channels 48, 49 takes its real 4 bytes per cell (the scratch S lives in what that frees).
 #pragma once
 #include "az_net_common.h"
-
-// what k-step ks (index in its conv) multiplies besides tiles 0..2, and how many fragment reads it needs
-template <bool IS_FIRST, int NT> struct X3BK {
-    static constexpr bool has_t(int ks) { return IS_FIRST || ks == 6 || ks == 7 || ks == X3B::NKS - 1; }
-    static constexpr bool has_x(int ks) { return !IS_FIRST && (ks == 6 || ks == 7); }
-    static constexpr bool is_gather(int ks) { return !IS_FIRST && ks == X3B::NKS - 1; }
-    static constexpr int n_a(int ks) { return 6 + (has_t(ks) ? 1 : 0) + (has_x(ks) ? 2 : 0); } // ah 0..2, al 0..2, T, X hi, X lo
-    static constexpr int n_b(int ks) { return is_gather(ks) ? 8 * NT : 2 * NT; }
-};
+#include "az_tower_x3b_parts.h"
 
 template <int NT>
 __global__ __launch_bounds__(256, 1) void az_tower_x3b_kernel(TowerParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int WAVES = 4, FR = X3B::FR, REC2 = X3B::REC2, CK = X3B::CK, NKS = X3B::NKS, PARTS = X3B::PARTS;
     constexpr int CHUNK_S = X3B::CHUNK_S, LO_OFF = X3B::LO_OFF, S_PLANE = X3B::S_PLANE;
-    constexpr float INV_SPLIT = 1.0f / 2048.0f;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int q = lane >> 4, l15 = lane & 15;
     constexpr int plane_b = X3B::PLANE_B;
@@ -65,23 +58,8 @@ __global__ __launch_bounds__(256, 1) void az_tower_x3b_kernel(TowerParams p) {
     int (&pos_addr)[NT] = T.pos_addr, (&grow)[NT] = T.grow, (&p6_addr)[NT] = T.p6_addr;
     int (&koff)[AZ_NET_KSTEPS] = T.koff, (&ksp)[4] = T.ksp, (&koff0)[AZ_NET_K0STEPS] = T.koff0;
 
-    // scratch addresses.  Lane (q, l15) of tile X holds rows 4q..4q+3 = (plane 2q, c0), (2q, c1), (2q+1, c0), (2q+1, c1) at
-    // position (y, x) = (2 nt + (l15 >> 3), l15 & 7); plane t belongs to tap tap_of_plane(t) with d = (dy, dx): the value is
-    // a term of out[c, (y - dy, x - dx)].  Off-board destinations and padding lanes store to the trash slot.
-    int sdst[NT][2], scen[NT];
-#pragma unroll
-    for (int nt = 0; nt < NT; nt++) {
-        const int y = 2 * nt + (l15 >> 3), x = l15 & 7;
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const int t = 2 * q + k, tap = t < 4 ? t : t + 1;
-            const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
-            const int yd = y - dy, xd = x - dx;
-            const bool ok = grow[nt] >= 0 && yd >= 0 && yd < p.H && xd >= 0 && xd < p.W;
-            sdst[nt][k] = ok ? s_wave + t * S_PLANE + (yd * 8 + xd) * 8 : trash;
-        }
-        scen[nt] = (q == 1 && grow[nt] >= 0) ? s_wave + 8 * S_PLANE + (nt * 16 + l15) * 8 : trash;
-    }
+    int sdst[NT][2], scen[NT]; // scratch addresses of tile X's terms and of the centre tap
+    x3b_scratch_dst(p, grow, q, l15, s_wave, trash, sdst, scen);
     const unsigned sread = lds_base + s_wave + l15 * 8; // plane t, tile nt: + t * S_PLANE + nt * 128
 
     // x -> (hi, lo): hi = fp16(x), lo = fp16((x - hi) * 2048)
@@ -99,30 +77,18 @@ __global__ __launch_bounds__(256, 1) void az_tower_x3b_kernel(TowerParams p) {
         for (int nt = 0; nt < NT; nt++) {
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
             if (grow[nt] >= 0) {
-                int gb = grow[nt] / p.HW, pos = grow[nt] - gb * p.HW;
-#pragma unroll
-                for (int c = 0; c < 4; c++)
-                    if (c < p.cin) v[c] = p.obs[((size_t)gb * p.cin + c) * p.HW + pos];
+                v = x3b_load_obs(p, grow[nt]);
                 if (q == 0) {
-                    f32x4 a;
-#pragma unroll
-                    for (int c = 0; c < 4; c++) a[c] = c < p.cin ? lrelu(p.in_scale[c] * v[c] + p.in_shift[c]) : 0.f;
                     half4 hi, lo;
-                    split4_planes(a, hi, lo);
+                    split4_planes(x3b_input_planes(p, v), hi, lo);
                     *(half4 *)(lds + pos_addr[nt]) = hi;
                     *(half4 *)(lds + pos_addr[nt] + LO_OFF) = lo;
                 }
             }
 #pragma unroll
             for (int mt = 0; mt < 4; mt++) {
-                f32x4 x;
-#pragma unroll
-                for (int r = 0; r < 4; r++)
-                    x[r] = sw[mt][r][0] * v[0] + sw[mt][r][1] * v[1] + sw[mt][r][2] * v[2] + sw[mt][r][3] * v[3];
-                xres[mt][nt] = x;
-                // tile T: only channels 48, 49 (lanes q == 0, rows 0, 1) carry a bias; its other rows are lo / centre-tap rows
-                acc[mt][nt] = (mt < 3 || q == 0) ? *(const f32x4 *)(p.epi + 16 * mt + 4 * q) * X3_WSCALE : (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (mt == 3) acc[mt][nt][2] = acc[mt][nt][3] = 0.f;
+                xres[mt][nt] = x3b_skip(sw[mt], v);
+                acc[mt][nt] = mt < 3 ? x3b_bias0<false>(p, mt, q) : x3b_bias0<true>(p, mt, q);
             }
             accx[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
@@ -136,12 +102,12 @@ __global__ __launch_bounds__(256, 1) void az_tower_x3b_kernel(TowerParams p) {
     // through chunk boundaries without a bubble; only the conv boundary (epilogue, then the B fragments of k-step 0) breaks it.
     auto issue_piece = [&](int c, auto part_c, int i) { // piece 4 i + wave of chunk c (= part `part` of its conv; part -1: conv 0)
         constexpr int part = decltype(part_c)::value;
-        constexpr int NPIECES = (part < 0 ? X3B::C0_B : X3B::part_bytes(part < 0 ? 0 : part)) / 1024;
+        constexpr int NPIECES = X3B::n_pieces<part>();
         // branch-free: a wave whose piece index runs past the chunk re-fetches the chunk's last piece (same bytes, same place),
         // and a chunk index past the stream fetches its zero padding (az_net.hip)
         int piece = i * WAVES + wave;
         piece = piece < NPIECES ? piece : NPIECES - 1;
-        const size_t off = part < 0 ? 0 : (size_t)X3B::C0_B + (size_t)((c - 1) / PARTS) * X3B::CONV_B + X3B::part_off(part < 0 ? 0 : part);
+        const size_t off = X3B::chunk_off<part>(c);
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((const unsigned char *)p.conv_w + off + piece * 1024 + lane * 16),
                                          (__attribute__((address_space(3))) void *)(lds + (c & 1) * CHUNK_S + piece * 1024), 16, 0, 0);
     };
@@ -190,8 +156,7 @@ __global__ __launch_bounds__(256, 1) void az_tower_x3b_kernel(TowerParams p) {
             if constexpr (r < 3) READ_A(ah[buf][r], wb, ksl * REC2 + r * FR);
             else if constexpr (r < 6) READ_A(al[buf][r - 3], wb, ksl * REC2 + r * FR);
             else {
-                // the extra fragments sit behind the chunk's records
-                constexpr int xbase = IS_FIRST ? AZ_NET_K0STEPS * REC2 + ks * FR : (part == 1 ? 4 * REC2 + (ks - 6) * 3 * FR : 3 * REC2);
+                constexpr int xbase = X3B::extra_off(IS_FIRST, ks);
                 if constexpr (r == 6) READ_A(at[buf], wb, xbase);
                 else if constexpr (r == 7) READ_A(axh[buf], wb, xbase + FR);
                 else READ_A(axl[buf], wb, xbase + 2 * FR);
@@ -224,19 +189,15 @@ __global__ __launch_bounds__(256, 1) void az_tower_x3b_kernel(TowerParams p) {
             if constexpr (IS_FIRST) return;
             if constexpr (ks == 8 && j < 9 * NT) { // 9 slots per column tile: 4 combine, 2 centre, 3 stores
                 constexpr int nt = j / 9, i = j % 9;
-                if constexpr (i < 4) xv[i] = accx[nt][i] * INV_SPLIT;
-                else if constexpr (i < 6) // (lanes q == 1 hold rows 4..7 of tile T: hi c0, hi c1, lo c0, lo c1 of the centre tap)
-                    cv[i - 4] = (acc[3][nt][i - 4] + acc[3][nt][i - 2]) * INV_SPLIT;
+                if constexpr (i < 6) x3b_tx_term<i>(accx[nt], acc[3][nt], xv, cv);
                 else if constexpr (i == 6) lds_write64(lds_base + sdst[nt][0], (f32x2){xv[0], xv[1]});
                 else if constexpr (i == 7) lds_write64(lds_base + sdst[nt][1], (f32x2){xv[2], xv[3]});
                 else lds_write64(lds_base + scen[nt], cv);
             }
             if constexpr (ks >= 10 && ks <= 12 && j < 9) { // the planes of tile nt, read in the k-step before, have landed (k-step start wait)
                 constexpr int nt = ks - 10, t = j;
-                if constexpr (t == 0) {
-                    static_for<9>([&](auto t_c) { launder(pl[decltype(t_c)::value]); });
-                    s49[nt] = pl[0];
-                } else s49[nt] = s49[nt] + pl[t];
+                if constexpr (t == 0) static_for<9>([&](auto t_c) { launder(pl[decltype(t_c)::value]); });
+                x3b_add_plane<t>(s49[nt], pl);
             }
             if constexpr (ks >= 9 && ks <= 11 && j >= 9 && j < 18) { // (LDS operations of one wave execute in order: these reads see the stores)
                 constexpr int nt = ks - 9, t = j - 9;               // issued after the sums of the tile before, which still hold pl
@@ -253,8 +214,8 @@ __global__ __launch_bounds__(256, 1) void az_tower_x3b_kernel(TowerParams p) {
             constexpr int cur = ks & 1, nxt = cur ^ 1;
             constexpr int na_next = last_of_conv ? 6 : K::n_a(ks + 1); // across the conv boundary: ah0 / al0 of the next conv
             constexpr int n_next = last_of_conv ? 6 : na_next + K::n_b(ks + 1);
-            constexpr bool T_ON = K::has_t(ks), X_ON = K::has_x(ks), GATHER = K::is_gather(ks);
-            constexpr int NM = 9 * NT + (T_ON ? 2 * NT : 0) + (X_ON ? 3 * NT : 0);
+            constexpr bool T_ON = K::has_t(ks), GATHER = K::is_gather(ks);
+            constexpr int NM = K::n_mfma(ks) * NT;
             constexpr int RPS = (n_next + NM - 1) / NM > 1 ? (n_next + NM - 1) / NM : 1; // reads per MFMA slot (2 or 3 per slot measured 1-3 % slower)
             constexpr int part2 = IS_FIRST ? 1 : (part + 2) % PARTS;                      // the part chunk + 2 is
             static_assert(2 + 3 * (NPW - 1) < NM, "a DMA piece every third MFMA slot");
@@ -299,45 +260,15 @@ __global__ __launch_bounds__(256, 1) void az_tower_x3b_kernel(TowerParams p) {
                 if constexpr (last_of_chunk && j >= 2 && (j - 2) % 3 == 0 && (j - 2) / 3 < NPW) // buffer chunk & 1 is free: fetch chunk + 2
                     issue_piece(chunk + 2, std::integral_constant<int, part2>{}, (j - 2) / 3);
                 s_path(ks_c, j_c);
-                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-                auto b_hi = [&](auto nt_c) -> half8 {
-                    constexpr int nt = decltype(nt_c)::value;
-                    if constexpr (GATHER) {
-                        const u32x4 u = {sph[nt][0], sph[nt][1], sph[nt][2], sph[nt][3]};
-                        return __builtin_bit_cast(half8, u);
-                    } else return bh[cur][nt];
-                };
-                auto b_lo = [&](auto nt_c) -> half8 {
-                    constexpr int nt = decltype(nt_c)::value;
-                    if constexpr (GATHER) {
-                        const u32x4 u = {spl[nt][0], spl[nt][1], spl[nt][2], spl[nt][3]};
-                        return __builtin_bit_cast(half8, u);
-                    } else return bl[cur][nt];
-                };
-                // ONE accumulator per tile: the weights carry 2048 in both halves and the activations' lo half is unscaled, so hi'*hi,
-                // hi'*lo0 and lo*hi are all 2048 x their share of the product (az_net_common.h: split_pair_planes).  Order per accumulator
-                // and k-step - hi'*hi, hi'*lo0, lo*hi - is the same in az_tower_x3c_kernel and az_tower_x3d_kernel: same bits.
-                if constexpr (j < 9 * NT) { // tiles 0..2, pass-major over the (tile, column tile) pairs
-                    constexpr int pass = j / (3 * NT), nt = (j % (3 * NT)) / 3, mt = j % 3;
-                    constexpr auto ntc = std::integral_constant<int, nt>{};
-                    const half8 a_hi = ks == 0 ? ah0[mt] : ah[cur][mt], a_lo = ks == 0 ? al0[mt] : al[cur][mt];
-                    if constexpr (pass == 0) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, b_hi(ntc), acc[mt][nt], 0, 0, 0);
-                    else if constexpr (pass == 1) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, b_lo(ntc), acc[mt][nt], 0, 0, 0);
-                    else acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_lo, b_hi(ntc), acc[mt][nt], 0, 0, 0);
-                } else if constexpr (T_ON && j < 11 * NT) { // tile T (hi rows and lo rows in one fragment): x B_hi, then x B_lo0
-                    constexpr int jj = j - 9 * NT, nt = jj % NT;
-                    constexpr auto ntc = std::integral_constant<int, nt>{};
-                    const half8 a_t = ks == 0 ? at0 : at[cur];
-                    if constexpr (jj < NT) acc[3][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_t, b_hi(ntc), acc[3][nt], 0, 0, 0);
-                    else acc[3][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_t, b_lo(ntc), acc[3][nt], 0, 0, 0);
-                } else { // tile X: hi'*hi (from a literal 0 at k-step 6), hi'*lo0, lo*hi
-                    constexpr int jj = j - 11 * NT, nt = jj % NT;
-                    constexpr auto ntc = std::integral_constant<int, nt>{};
-                    if constexpr (jj < NT) accx[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(axh[cur], b_hi(ntc), ks == 6 ? zero4 : accx[nt], 0, 0, 0);
-                    else if constexpr (jj < 2 * NT) accx[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(axh[cur], b_lo(ntc), accx[nt], 0, 0, 0);
-                    else accx[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(axl[cur], b_hi(ntc), accx[nt], 0, 0, 0);
-                }
+                // the pass each slot issues: tiles 0..2 pass-major over the (tile, column tile) pairs, then T's two passes, then X's
+                // three.  Which operands a pass multiplies - and with it the order per accumulator that x3c and x3d share: same
+                // bits - is x3b_mfma_main / _t / _x (az_tower_x3b_parts.h)
+                constexpr int jt = j < 9 * NT ? j : j < 11 * NT ? j - 9 * NT : j - 11 * NT; // slot within its group
+                constexpr int nt = j < 9 * NT ? (j % (3 * NT)) / 3 : jt % NT, mt = j % 3, pass = j < 9 * NT ? j / (3 * NT) : jt / NT;
+                const half8 b_hi = GATHER ? x3b_gather_b(sph[nt]) : bh[cur][nt], b_lo = GATHER ? x3b_gather_b(spl[nt]) : bl[cur][nt];
+                if constexpr (j < 9 * NT) x3b_mfma_main<pass>(acc[mt][nt], ks == 0 ? ah0[mt] : ah[cur][mt], ks == 0 ? al0[mt] : al[cur][mt], b_hi, b_lo);
+                else if constexpr (T_ON && j < 11 * NT) x3b_mfma_t<pass>(acc[3][nt], ks == 0 ? at0 : at[cur], b_hi, b_lo);
+                else x3b_mfma_x<pass, ks == 6>(accx[nt], axh[cur], axl[cur], b_hi, b_lo);
                 __builtin_amdgcn_sched_barrier(0);
             });
             if constexpr (last_of_chunk) chunk++;
@@ -371,7 +302,7 @@ __global__ __launch_bounds__(256, 1) void az_tower_x3b_kernel(TowerParams p) {
             for (int nt = 0; nt < NT; nt++) {
                 pin_acc(acc[mt][nt]);
             }
-        // ---- epilogue, in fp32; the result is split into (hi, lo) again ------------------------------------------
+        // ---- epilogue, in fp32 (x3b_epilogue_value); the result is split into (hi, lo) again --------------------------
         auto epilogue = [&](auto kind) {
             constexpr int KIND = decltype(kind)::value; // 0: conv1, 1: conv2 (not last), 2: last conv
 #pragma unroll
@@ -381,36 +312,16 @@ __global__ __launch_bounds__(256, 1) void az_tower_x3b_kernel(TowerParams p) {
                 const f32x4 sc = ep_sc[mt], sh = ep_sh[mt], next_bias = ep_nb[mt];
 #pragma unroll
                 for (int nt = 0; nt < NT; nt++) {
-                    f32x4 v;
-                    if (mt < 3) {
-                        v = acc[mt][nt] * INV_SPLIT;
-                        acc[mt][nt] = next_bias; // (2048 x the next conv's bias: scaled on the host)
-                    } else { // tile T, lanes q == 0: rows hi 48, hi 49, lo 48, lo 49 of the gather k-step (+ bias), plus the tap planes
-                        v = (f32x4){(acc[3][nt][0] + acc[3][nt][2]) * INV_SPLIT, (acc[3][nt][1] + acc[3][nt][3]) * INV_SPLIT, 0.f, 0.f};
-                        if constexpr (!IS_FIRST) {
-                            v[0] += s49[nt][0];
-                            v[1] += s49[nt][1];
+                    const f32x4 o = mt < 3 ? x3b_epilogue_value<KIND, false, IS_FIRST>(acc[mt][nt], xres[mt][nt], s49[nt], sc, sh, next_bias, q)
+                                           : x3b_epilogue_value<KIND, true, IS_FIRST>(acc[mt][nt], xres[mt][nt], s49[nt], sc, sh, next_bias, q);
+                    if (KIND == 2) { // o: the tower output
+                        half4 hi, lo;
+                        split4(o, hi, lo);
+                        if (grow[nt] >= 0 && co0 < p.xout_c) {
+                            *(half4 *)(p.xout + (size_t)grow[nt] * p.xout_c + co0) = hi;
+                            *(half4 *)(p.xout_lo + (size_t)grow[nt] * p.xout_c + co0) = lo;
                         }
-                        if (q != 0) v = (f32x4){0.f, 0.f, 0.f, 0.f}; // (rows 4..15: centre-tap rows / unused)
-                        acc[3][nt] = q == 0 ? (f32x4){next_bias[0], next_bias[1], 0.f, 0.f} : (f32x4){0.f, 0.f, 0.f, 0.f};
-                    }
-                    f32x4 o;
-                    if (KIND == 0) {
-                        o = __builtin_elementwise_max(v, v * 0.01f);
-                    } else {
-                        f32x4 xv = xres[mt][nt] + v;
-                        xres[mt][nt] = xv;
-                        if (KIND == 2) {
-                            half4 hi, lo;
-                            split4(xv, hi, lo);
-                            if (grow[nt] >= 0 && co0 < p.xout_c) {
-                                *(half4 *)(p.xout + (size_t)grow[nt] * p.xout_c + co0) = hi;
-                                *(half4 *)(p.xout_lo + (size_t)grow[nt] * p.xout_c + co0) = lo;
-                            }
-                            continue;
-                        }
-                        f32x4 a = __builtin_elementwise_fma(sc, xv, sh);
-                        o = __builtin_elementwise_max(a, a * 0.01f);
+                        continue;
                     }
                     half4 hi, lo;
                     split4_planes(o, hi, lo); // (between convs the lo half is unscaled; the tower OUTPUT above keeps lo x 2048: the head's format)

@@ -16,13 +16,14 @@
 //     gather k-step's B fragments, fetched during k-step 13) has returned before it enters that barrier;
 //   * read-after-write: one more barrier per conv, between the epilogue stores and the next conv's first B reads.
 // Every accumulator sees the same MFMAs in the same order as in az_tower_x3b_kernel and the epilogue arithmetic is the same
-// code, so a board's outputs are the same BITS whichever kernel evaluates it (tests/test_fused_net.py) - the records of a
-// generation cannot depend on when its tail switches kernels.
+// code - both kernels call az_tower_x3b_parts.h for it and differ in schedule and stores only - so a board's outputs are the
+// same BITS whichever kernel evaluates it (tests/test_fused_net.py): the records of a generation cannot depend on when its
+// tail switches kernels.
 // Two boards per workgroup (BPW = 2, eight waves): the waves of one role land on one SIMD and fill each other's waits; the boards
 // use the planes and scratch of x3b's waves 0 and 1, the barriers and the weight stream are the workgroup's.  512 boards: 49 -> 39 us
 // (3-block net); as a replacement for x3b at 4096 boards it loses (202 vs 173 us): the T + X wave's SIMD idles three quarters of the time.
 #pragma once
-#include "az_tower_x3b.h"
+#include "az_tower_x3b.h" // (and with it az_tower_x3b_parts.h)
 #include "az_head_fused.h"
 
 // what a wave of az_tower_x3c_kernel reads for k-step ks (TX: the wave of tiles T and X, which multiplies only where they are on)
@@ -39,7 +40,6 @@ __global__ __launch_bounds__(256 * BPW, BPW) void az_tower_x3c_kernel(TowerParam
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     constexpr int WAVES = 4 * BPW, FR = X3B::FR, REC2 = X3B::REC2, CK = X3B::CK, NKS = X3B::NKS, PARTS = X3B::PARTS;
     constexpr int CHUNK_S = X3B::CHUNK_S, LO_OFF = X3B::LO_OFF, S_PLANE = X3B::S_PLANE;
-    constexpr float INV_SPLIT = 1.0f / 2048.0f;
     constexpr int plane_b = X3B::PLANE_B;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int q = lane >> 4, l15 = lane & 15;
@@ -66,8 +66,8 @@ __global__ __launch_bounds__(256 * BPW, BPW) void az_tower_x3c_kernel(TowerParam
     // ---- weight stream (az_tower_x3b.h): chunk c -> buffer c & 1; the four waves issue a chunk's pieces together
     auto issue_chunk = [&](int c, auto part_c) {
         constexpr int part = decltype(part_c)::value;
-        constexpr int NPIECES = (part < 0 ? X3B::C0_B : X3B::part_bytes(part < 0 ? 0 : part)) / 1024;
-        const size_t off = part < 0 ? 0 : (size_t)X3B::C0_B + (size_t)((c - 1) / PARTS) * X3B::CONV_B + X3B::part_off(part < 0 ? 0 : part);
+        constexpr int NPIECES = X3B::n_pieces<part>();
+        const size_t off = X3B::chunk_off<part>(c);
 #pragma unroll
         for (int i = 0; i < (NPIECES + WAVES - 1) / WAVES; i++) {
             int piece = i * WAVES + wave; // (branch-free: past the chunk -> its last piece again; past the stream -> zero padding)
@@ -78,8 +78,8 @@ __global__ __launch_bounds__(256 * BPW, BPW) void az_tower_x3c_kernel(TowerParam
     };
     auto issue_piece = [&](int c, auto part_c, int i) { // piece 4 i + wave of chunk c
         constexpr int part = decltype(part_c)::value;
-        constexpr int NPIECES = X3B::part_bytes(part) / 1024;
-        const size_t off = (size_t)X3B::C0_B + (size_t)((c - 1) / PARTS) * X3B::CONV_B + X3B::part_off(part);
+        constexpr int NPIECES = X3B::n_pieces<part>();
+        const size_t off = X3B::chunk_off<part>(c);
         int piece = i * WAVES + wave;
         piece = piece < NPIECES ? piece : NPIECES - 1;
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((const unsigned char *)p.conv_w + off + piece * 1024 + lane * 16),
@@ -106,46 +106,21 @@ __global__ __launch_bounds__(256 * BPW, BPW) void az_tower_x3c_kernel(TowerParam
             for (int nt = 0; nt < NT; nt++) {
                 f32x4 v = {0.f, 0.f, 0.f, 0.f};
                 if (grow[nt] >= 0) {
-                    int gb = grow[nt] / p.HW, pos = grow[nt] - gb * p.HW;
-#pragma unroll
-                    for (int c = 0; c < 4; c++)
-                        if (c < p.cin) v[c] = p.obs[((size_t)gb * p.cin + c) * p.HW + pos];
+                    v = x3b_load_obs(p, grow[nt]);
                     if (ROLE == 0 && q == 0) {
-                        f32x4 a;
-#pragma unroll
-                        for (int c = 0; c < 4; c++) a[c] = c < p.cin ? lrelu(p.in_scale[c] * v[c] + p.in_shift[c]) : 0.f;
                         half4 hi, lo;
-                        split4_planes(a, hi, lo);
+                        split4_planes(x3b_input_planes(p, v), hi, lo);
                         *(half4 *)(lds + pos_addr[nt]) = hi;
                         *(half4 *)(lds + pos_addr[nt] + LO_OFF) = lo;
                     }
                 }
-                f32x4 x;
-#pragma unroll
-                for (int r = 0; r < 4; r++) x[r] = sw[r][0] * v[0] + sw[r][1] * v[1] + sw[r][2] * v[2] + sw[r][3] * v[3];
-                xres[nt] = x;
-                acc[nt] = (!TX || q == 0) ? *(const f32x4 *)(p.epi + 16 * mt + 4 * q) * X3_WSCALE : (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (TX) acc[nt][2] = acc[nt][3] = 0.f;
+                xres[nt] = x3b_skip(sw, v);
+                acc[nt] = x3b_bias0<TX>(p, mt, q);
                 accx[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
         }
-        // scratch addresses (ROLE 3; az_tower_x3b.h)
-        int sdst[NT][2], scen[NT];
-        if constexpr (TX) {
-#pragma unroll
-            for (int nt = 0; nt < NT; nt++) {
-                const int y = 2 * nt + (l15 >> 3), x = l15 & 7;
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    const int t = 2 * q + k, tap = t < 4 ? t : t + 1;
-                    const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
-                    const int yd = y - dy, xd = x - dx;
-                    const bool ok = grow[nt] >= 0 && yd >= 0 && yd < p.H && xd >= 0 && xd < p.W;
-                    sdst[nt][k] = ok ? s_wave + t * S_PLANE + (yd * 8 + xd) * 8 : trash;
-                }
-                scen[nt] = (q == 1 && grow[nt] >= 0) ? s_wave + 8 * S_PLANE + (nt * 16 + l15) * 8 : trash;
-            }
-        }
+        int sdst[NT][2], scen[NT]; // scratch addresses (ROLE 3)
+        if constexpr (TX) x3b_scratch_dst(p, grow, q, l15, s_wave, trash, sdst, scen);
         const unsigned sread = lds_base + s_wave + l15 * 8;
 
         half8 ah0, al0, at0; // A fragments of a conv's k-step 0 (x3b: fetched during the last k-step of the conv before)
@@ -182,7 +157,7 @@ __global__ __launch_bounds__(256 * BPW, BPW) void az_tower_x3c_kernel(TowerParam
                     if constexpr (r == 0) READ_A(ah[buf], wb, ksl * REC2 + mt * FR);
                     else READ_A(al[buf], wb, ksl * REC2 + (3 + mt) * FR);
                 } else {
-                    constexpr int xbase = IS_FIRST ? AZ_NET_K0STEPS * REC2 + ks * FR : (part == 1 ? 4 * REC2 + (ks - 6) * 3 * FR : 3 * REC2);
+                    constexpr int xbase = X3B::extra_off(IS_FIRST, ks);
                     if constexpr (r == 0) READ_A(at[buf], wb, xbase);
                     else if constexpr (r == 1) READ_A(axh[buf], wb, xbase + FR);
                     else READ_A(axl[buf], wb, xbase + 2 * FR);
@@ -263,56 +238,23 @@ __global__ __launch_bounds__(256 * BPW, BPW) void az_tower_x3c_kernel(TowerParam
                     });
                     if constexpr (!TX && d >= 0 && j % 3 == 2 && 3 * d + j / 3 < (30 + WAVES - 1) / WAVES)
                         issue_piece(chunk_t, std::integral_constant<int, part_t>{}, 3 * d + j / 3);
-                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-                    auto b_hi = [&](auto nt_c) -> half8 {
-                        constexpr int nt = decltype(nt_c)::value;
-                        if constexpr (GATHER) {
-                            const u32x4 u = {sph[nt][0], sph[nt][1], sph[nt][2], sph[nt][3]};
-                            return __builtin_bit_cast(half8, u);
-                        } else return bh[cur][nt];
-                    };
-                    auto b_lo = [&](auto nt_c) -> half8 {
-                        constexpr int nt = decltype(nt_c)::value;
-                        if constexpr (GATHER) {
-                            const u32x4 u = {spl[nt][0], spl[nt][1], spl[nt][2], spl[nt][3]};
-                            return __builtin_bit_cast(half8, u);
-                        } else return bl[cur][nt];
-                    };
-                    if constexpr (!TX) { // one accumulator: hi'*hi, hi'*lo0, lo*hi (the order of az_tower_x3b_kernel per accumulator and k-step)
-                        constexpr int pass = j / NT, nt = j % NT;
-                        constexpr auto ntc = std::integral_constant<int, nt>{};
-                        const half8 a_hi = ks == 0 ? ah0 : ah[cur], a_lo = ks == 0 ? al0 : al[cur];
-                        if constexpr (pass == 0) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, b_hi(ntc), acc[nt], 0, 0, 0);
-                        else if constexpr (pass == 1) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, b_lo(ntc), acc[nt], 0, 0, 0);
-                        else acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_lo, b_hi(ntc), acc[nt], 0, 0, 0);
-                    } else if constexpr (T_ON && j < 2 * NT) {
-                        constexpr int nt = j % NT;
-                        constexpr auto ntc = std::integral_constant<int, nt>{};
-                        const half8 a_t = ks == 0 ? at0 : at[cur];
-                        if constexpr (j < NT) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_t, b_hi(ntc), acc[nt], 0, 0, 0);
-                        else acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_t, b_lo(ntc), acc[nt], 0, 0, 0);
-                    } else {
-                        constexpr int jj = j - 2 * NT, nt = jj % NT;
-                        constexpr auto ntc = std::integral_constant<int, nt>{};
-                        if constexpr (jj < NT) accx[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(axh[cur], b_hi(ntc), ks == 6 ? zero4 : accx[nt], 0, 0, 0);
-                        else if constexpr (jj < 2 * NT) accx[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(axh[cur], b_lo(ntc), accx[nt], 0, 0, 0);
-                        else accx[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(axl[cur], b_hi(ntc), accx[nt], 0, 0, 0);
-                    }
+                    // the pass each slot issues; which operands a pass multiplies is x3b_mfma_main / _t / _x (az_tower_x3b_parts.h)
+                    constexpr int nt = j % NT, pass = TX && j >= 2 * NT ? (j - 2 * NT) / NT : j / NT; // (ROLE 3: T's two passes, then X's three)
+                    const half8 b_hi = GATHER ? x3b_gather_b(sph[nt]) : bh[cur][nt], b_lo = GATHER ? x3b_gather_b(spl[nt]) : bl[cur][nt];
+                    if constexpr (!TX) x3b_mfma_main<pass>(acc[nt], ks == 0 ? ah0 : ah[cur], ks == 0 ? al0 : al[cur], b_hi, b_lo);
+                    else if constexpr (T_ON && j < 2 * NT) x3b_mfma_t<pass>(acc[nt], ks == 0 ? at0 : at[cur], b_hi, b_lo);
+                    else x3b_mfma_x<pass, ks == 6>(accx[nt], axh[cur], axl[cur], b_hi, b_lo);
                     __builtin_amdgcn_sched_barrier(0);
                 });
                 // channels 48, 49: tile X and the centre-tap rows of T are final after k-step 7; this wave has nothing to multiply
-                // until the gather k-step, so the shifted sum through the scratch runs here in one piece (the same arithmetic, in the
-                // same order, as x3b's interleaved version)
+                // until the gather k-step, so the shifted sum through the scratch runs here in one piece (x3b_tx_terms, x3b_sum_planes:
+                // the terms x3b spreads over its MFMA slots one at a time)
                 if constexpr (TX && !IS_FIRST && ks == 8) {
 #pragma unroll
                     for (int nt = 0; nt < NT; nt++) {
                         f32x4 xv;
-#pragma unroll
-                        for (int i = 0; i < 4; i++) xv[i] = accx[nt][i] * INV_SPLIT;
                         f32x2 cv;
-#pragma unroll
-                        for (int i = 0; i < 2; i++) cv[i] = (acc[nt][i] + acc[nt][i + 2]) * INV_SPLIT;
+                        x3b_tx_terms(accx[nt], acc[nt], xv, cv);
                         lds_write64(lds_base + sdst[nt][0], (f32x2){xv[0], xv[1]});
                         lds_write64(lds_base + sdst[nt][1], (f32x2){xv[2], xv[3]});
                         lds_write64(lds_base + scen[nt], cv);
@@ -323,10 +265,7 @@ __global__ __launch_bounds__(256 * BPW, BPW) void az_tower_x3c_kernel(TowerParam
                         static_for<9>([&](auto t_c) { lds_read64_off<decltype(t_c)::value * S_PLANE + nt * 128>(pl[decltype(t_c)::value], sread); });
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                         static_for<9>([&](auto t_c) { launder(pl[decltype(t_c)::value]); });
-                        f32x2 s = pl[0];
-#pragma unroll
-                        for (int t = 1; t < 9; t++) s = s + pl[t];
-                        s49[nt] = s;
+                        s49[nt] = x3b_sum_planes(pl);
                     });
                 }
                 if constexpr (last_of_chunk) chunk++;
@@ -344,7 +283,7 @@ __global__ __launch_bounds__(256 * BPW, BPW) void az_tower_x3c_kernel(TowerParam
                 launder(ep_sh);
             }
             launder(ep_nb);
-            // ---- epilogue of this wave's tile, in fp32; the result is split into (hi, lo) again (az_tower_x3b.h, same arithmetic)
+            // ---- epilogue of this wave's tile, in fp32; the result is split into (hi, lo) again (x3b_epilogue_value)
             auto epilogue = [&](auto kind) {
                 constexpr int KIND = decltype(kind)::value; // 0: conv1, 1: conv2 (not last), 2: last conv
                 const int co0 = 16 * mt + 4 * q;
@@ -352,38 +291,15 @@ __global__ __launch_bounds__(256 * BPW, BPW) void az_tower_x3c_kernel(TowerParam
                 const f32x4 sc = ep_sc, sh = ep_sh, next_bias = ep_nb;
 #pragma unroll
                 for (int nt = 0; nt < NT; nt++) {
-                    f32x4 v;
-                    if constexpr (!TX) {
-                        v = acc[nt] * INV_SPLIT;
-                        acc[nt] = next_bias; // (2048 x the next conv's bias: scaled on the host)
-                    } else {
-                        v = (f32x4){(acc[nt][0] + acc[nt][2]) * INV_SPLIT, (acc[nt][1] + acc[nt][3]) * INV_SPLIT, 0.f, 0.f};
-                        if constexpr (!IS_FIRST) {
-                            v[0] += s49[nt][0];
-                            v[1] += s49[nt][1];
+                    const f32x4 o = x3b_epilogue_value<KIND, TX, IS_FIRST>(acc[nt], xres[nt], s49[nt], sc, sh, next_bias, q);
+                    if (KIND == 2) { // o: the tower output
+                        half4 hi, lo;
+                        split4(o, hi, lo);
+                        if (grow[nt] >= 0 && co0 < p.xout_c) {
+                            *(half4 *)(p.xout + (size_t)grow[nt] * p.xout_c + co0) = hi;
+                            *(half4 *)(p.xout_lo + (size_t)grow[nt] * p.xout_c + co0) = lo;
                         }
-                        if (q != 0) v = (f32x4){0.f, 0.f, 0.f, 0.f};
-                        acc[nt] = q == 0 ? (f32x4){next_bias[0], next_bias[1], 0.f, 0.f} : (f32x4){0.f, 0.f, 0.f, 0.f};
-                    }
-                    f32x4 o;
-                    if (KIND == 0) {
-                        o = __builtin_elementwise_max(v, v * 0.01f);
-                    } else {
-                        f32x4 xv = xres[nt] + v;
-                        xres[nt] = xv;
-                        if (KIND == 2) {
-                            half4 hi, lo;
-                            split4(xv, hi, lo);
-                            if (grow[nt] >= 0 && co0 < p.xout_c) {
-                                *(half4 *)(p.xout + (size_t)grow[nt] * p.xout_c + co0) = hi;
-                                *(half4 *)(p.xout_lo + (size_t)grow[nt] * p.xout_c + co0) = lo;
-                            }
-                            if (!p.fc_w) continue;
-                            o = xv; // fused head: the tower output also goes into the planes (fc1 below reads it from there)
-                        } else {
-                            f32x4 a = __builtin_elementwise_fma(sc, xv, sh);
-                            o = __builtin_elementwise_max(a, a * 0.01f);
-                        }
+                        if (!p.fc_w) continue; // fused head: the tower output also goes into the planes (fc1 below reads it from there)
                     }
                     half4 hi, lo;
                     if (KIND == 2) split4(o, hi, lo); // (the tower OUTPUT in the planes, for the fused head: its format, lo x 2048)

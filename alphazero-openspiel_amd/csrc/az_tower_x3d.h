@@ -31,15 +31,16 @@
 //     since); A fragments of tiles 0..2 keep x3b's two-slot ring, those of T and X have one set; the per-k-step address offsets
 //     are compile-time constants selected per lane where they are used, not a table of registers.
 // Every accumulator sees the same MFMAs in the same order as in az_tower_x3b_kernel / az_tower_x3c_kernel and the epilogue is the
-// same arithmetic: on row-pair boards a board's outputs are the same BITS in all three (tests/test_fused_net.py).  The epilogue's plane
+// same code (az_tower_x3b_parts.h, called by all three): on row-pair boards a board's outputs are the same BITS in all three
+// (tests/test_fused_net.py).  Own code here where the packed tiles differ: the scratch destinations come from the host's table, the
+// compact-plane address is derived (p6_of), the stream addressing is X3D's chunking (X3DS::a_off), and the stores need no mask.  The epilogue's plane
 // stores need no mask here: every lane of a tile is a real position, and a board past the batch computes on zero planes.
 #pragma once
 #include "az_net_common.h"
+#include "az_tower_x3b_parts.h"
 
-template <bool IS_FIRST> struct X3DK {
-    static constexpr bool has_t(int ks) { return IS_FIRST || ks == 6 || ks == 7 || ks == X3D::NKS - 1; }
-    static constexpr bool has_x(int ks) { return !IS_FIRST && (ks == 6 || ks == 7); }
-    static constexpr bool is_gather(int ks) { return !IS_FIRST && ks == X3D::NKS - 1; }
+template <bool IS_FIRST> struct X3DK : X3BK<IS_FIRST, 1> { // (the k-steps of tiles T and X are the scheme's: az_net_common.h)
+    using X3BK<IS_FIRST, 1>::has_t, X3BK<IS_FIRST, 1>::has_x, X3BK<IS_FIRST, 1>::is_gather;
     static constexpr int n_tx(int ks) { return (has_t(ks) ? 1 : 0) + (has_x(ks) ? 2 : 0); } // fragments of tiles T, X hi, X lo
     // T and X have ONE register set (a ring for three k-steps of a conv would be twelve registers): where the k-step before uses
     // it too, the fetch waits for that k-step's last MFMA, and the k-step opens with a full wait (k-step 7; conv 0's k-steps 1..3)
@@ -108,7 +109,6 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
     using VV = X3DV<V>;
     constexpr int WAVES = 8, NKS = X3D::NKS, PARTS = X3D::PARTS;
     constexpr int CHUNK_S = X3D::CHUNK_S, LO_OFF = G::LO_OFF, S_PLANE = G::S_PLANE, plane_b = G::PLANE_B;
-    constexpr float INV_SPLIT = 1.0f / 2048.0f;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int q = lane >> 4, l15 = lane & 15;
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)lds;
@@ -202,31 +202,14 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
             f32x4 swe[4];
 #pragma unroll
             for (int r = 0; r < 4; r++) swe[r] = *(const f32x4 *)(p.skip_w + (16 * (EXM ? emt : 3) + 4 * q + r) * 4);
-            auto skip = [&](const f32x4 (&w)[4], const f32x4 &v) {
-                f32x4 x;
-#pragma unroll
-                for (int r = 0; r < 4; r++) x[r] = w[r][0] * v[0] + w[r][1] * v[1] + w[r][2] * v[2] + w[r][3] * v[3];
-                return x;
-            };
-            auto bias_t = [&]() { // tile T: only channels 48, 49 (lanes q == 0, rows 0, 1) carry a bias; its other rows are lo / centre-tap rows
-                f32x4 b = q == 0 ? *(const f32x4 *)(p.epi + 48) * X3_WSCALE : (f32x4){0.f, 0.f, 0.f, 0.f};
-                b[2] = b[3] = 0.f;
-                return b;
-            };
 #pragma unroll
             for (int nt = 0; nt < NTA; nt++) {
                 f32x4 v = {0.f, 0.f, 0.f, 0.f};
                 if (grow[nt] >= 0) {
-                    int gb = grow[nt] / p.HW, pos = grow[nt] - gb * p.HW;
-#pragma unroll
-                    for (int c = 0; c < 4; c++)
-                        if (c < p.cin) v[c] = p.obs[((size_t)gb * p.cin + c) * p.HW + pos];
+                    v = x3b_load_obs(p, grow[nt]);
                     if (q == 0 && (nt < NTW || EXT)) { // (the split tile's input planes: the wave that holds its T and X)
-                        f32x4 a;
-#pragma unroll
-                        for (int c = 0; c < 4; c++) a[c] = c < p.cin ? lrelu(p.in_scale[c] * v[c] + p.in_shift[c]) : 0.f;
                         half4 hi, lo;
-                        split4_planes(a, hi, lo);
+                        split4_planes(x3b_input_planes(p, v), hi, lo);
                         *(half4 *)(lds + (baseL[nt] - lds_base)) = hi;
                         *(half4 *)(lds + (baseL[nt] - lds_base) + LO_OFF) = lo;
                     }
@@ -234,21 +217,21 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
                 if (nt < NTW) {
 #pragma unroll
                     for (int mt = 0; mt < 3; mt++) {
-                        xres[mt][nt] = skip(sw[mt], v);
-                        acc[mt][nt] = *(const f32x4 *)(p.epi + 16 * mt + 4 * q) * X3_WSCALE;
+                        xres[mt][nt] = x3b_skip(sw[mt], v);
+                        acc[mt][nt] = x3b_bias0<false>(p, mt, q);
                     }
                 }
                 if (nt < NTT) {
-                    xresT[nt] = skip(sw[3], v);
-                    accT[nt] = bias_t();
+                    xresT[nt] = x3b_skip(sw[3], v);
+                    accT[nt] = x3b_bias0<true>(p, 3, q);
                     accx[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
                 } else if (EXM) {
-                    xrese = skip(swe, v);
-                    acce = *(const f32x4 *)(p.epi + 16 * emt + 4 * q) * X3_WSCALE;
+                    xrese = x3b_skip(swe, v);
+                    acce = x3b_bias0<false>(p, emt, q);
                 }
             }
         }
-        // scratch addresses.  Lane (q, l15) of tile X holds rows 4q..4q+3 = (plane 2q, c0), (2q, c1), (2q+1, c0), (2q+1, c1) of its
+        // scratch addresses (x3b_scratch_dst's, from the host's table: a tile's columns are no row pair here).  Lane (q, l15) of tile X holds rows 4q..4q+3 = (plane 2q, c0), (2q, c1), (2q+1, c0), (2q+1, c1) of its
         // column; plane t belongs to tap tap_of_plane(t) with d = (dy, dx): the value is a term of out[c, position - d], whose
         // column the host's table names (0xFFFF: off the board -> the trash slot).  Plane 8 = the centre tap (rows 4..7 of tile T).
         int sdst[NTT][2], scen[NTT];
@@ -276,7 +259,6 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
             half8 bh[NTA], bl[NTA];                          // B fragments (activations) of the CURRENT k-step, per tile
             f32x2 s49[NTT];                                  // (lanes q == 0) sum over the nine tap planes at this lane's column: channels 48, 49
             using SCH = X3DS<IS_FIRST, NTW, EXM, EXT>;
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
             unsigned gh[NTA][4], gl[NTA][4]; // the gather k-step's B fragments, dword by dword (assembled at the MFMA, behind the wait)
             auto read_a = [&](unsigned wb, auto ks_c, auto r_c) { // fragment r of k-step ks into ring slot ks & 1: ah 0..2, al 0..2, T, X hi, X lo
                 constexpr int ks = decltype(ks_c)::value, r = decltype(r_c)::value, buf = ks & 1;
@@ -348,10 +330,9 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
                 if constexpr (S_STORE) {
 #pragma unroll
                     for (int nt = 0; nt < NTT; nt++) {
-                        const f32x4 xv = accx[nt] * INV_SPLIT;
-                        f32x2 cv; // (lanes q == 1 hold rows 4..7 of tile T: hi c0, hi c1, lo c0, lo c1 of the centre tap)
-#pragma unroll
-                        for (int i = 0; i < 2; i++) cv[i] = (accT[nt][i] + accT[nt][i + 2]) * INV_SPLIT;
+                        f32x4 xv;
+                        f32x2 cv;
+                        x3b_tx_terms(accx[nt], accT[nt], xv, cv);
                         lds_write64(lds_base + sdst[nt][0], (f32x2){xv[0], xv[1]});
                         lds_write64(lds_base + sdst[nt][1], (f32x2){xv[2], xv[3]});
                         lds_write64(lds_base + scen[nt], cv);
@@ -369,13 +350,9 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
                         constexpr int nt = decltype(nt_c)::value;
                         wait_lgkm(9 * (NTT - 1 - nt) < 15 ? 9 * (NTT - 1 - nt) : 15);
                         static_for<9>([&](auto t_c) { launder(pl[nt][decltype(t_c)::value]); });
-                        f32x2 sm = pl[nt][0];
-#pragma unroll
-                        for (int t = 1; t < 9; t++) sm = sm + pl[nt][t];
-                        s49[nt] = sm;
+                        s49[nt] = x3b_sum_planes(pl[nt]);
                     });
                 }
-                const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
                 static_for<NTB>([&](auto nt_c) {
                     constexpr int nt = decltype(nt_c)::value;
                     constexpr bool OWN = nt < NTW;
@@ -389,8 +366,8 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
                             launder_u(gh[nt][decltype(i_c)::value]);
                             launder_u(gl[nt][decltype(i_c)::value]);
                         });
-                        b_hi = __builtin_bit_cast(half8, (u32x4){gh[nt][0], gh[nt][1], gh[nt][2], gh[nt][3]});
-                        b_lo = __builtin_bit_cast(half8, (u32x4){gl[nt][0], gl[nt][1], gl[nt][2], gl[nt][3]});
+                        b_hi = x3b_gather_b(gh[nt]);
+                        b_lo = x3b_gather_b(gl[nt]);
                     } else {
                         launder(bh[nt]);
                         launder(bl[nt]);
@@ -412,29 +389,14 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
                                             std::integral_constant<int, X3D::part_bytes(part2) / 1024>{}, (gslot - 2) / 3);
                             }
                         }
+                        // the pass each slot issues (which operands a pass multiplies: x3b_mfma_main / _t / _x, az_tower_x3b_parts.h - the
+                        // order per accumulator of x3b and x3c: same bits); within a tile pass-major, so that an accumulator's three MFMAs
+                        // are three slots apart
                         if constexpr (j < n_main) {
-                            // per accumulator and k-step: hi'*hi, hi'*lo0, lo*hi (the order of az_tower_x3b_kernel: same bits); within a tile
-                            // pass-major, so that an accumulator's three MFMAs are three slots apart
-                            constexpr int pass = OWN ? j / 3 : j, mt = OWN ? j % 3 : 0;
-                            if constexpr (OWN) {
-                                const half8 a_hi = ah[cur][mt], a_lo = al[cur][mt];
-                                if constexpr (pass == 0) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, b_hi, acc[mt][nt], 0, 0, 0);
-                                else if constexpr (pass == 1) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, b_lo, acc[mt][nt], 0, 0, 0);
-                                else acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_lo, b_hi, acc[mt][nt], 0, 0, 0);
-                            } else { // the split tile's output-channel tile mt = emt
-                                if constexpr (pass == 0) acce = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[cur][emt], b_hi, acce, 0, 0, 0);
-                                else if constexpr (pass == 1) acce = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[cur][emt], b_lo, acce, 0, 0, 0);
-                                else acce = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[cur][emt], b_hi, acce, 0, 0, 0);
-                            }
-                        } else if constexpr (j < n_main + n_t) { // tile T (hi rows and lo rows in one fragment): x B_hi, then x B_lo0
-                            if constexpr (j == n_main) accT[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(at, b_hi, accT[nt], 0, 0, 0);
-                            else accT[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(at, b_lo, accT[nt], 0, 0, 0);
-                        } else { // tile X: hi'*hi (from a literal 0 at k-step 6), hi'*lo0, lo*hi
-                            constexpr int jj = j - n_main - n_t;
-                            if constexpr (jj == 0) accx[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(axh, b_hi, ks == 6 ? zero4 : accx[nt], 0, 0, 0);
-                            else if constexpr (jj == 1) accx[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(axh, b_lo, accx[nt], 0, 0, 0);
-                            else accx[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(axl, b_hi, accx[nt], 0, 0, 0);
-                        }
+                            if constexpr (OWN) x3b_mfma_main<j / 3>(acc[j % 3][nt], ah[cur][j % 3], al[cur][j % 3], b_hi, b_lo);
+                            else x3b_mfma_main<j>(acce, ah[cur][emt], al[cur][emt], b_hi, b_lo); // the split tile's output-channel tile mt = emt
+                        } else if constexpr (j < n_main + n_t) x3b_mfma_t<j - n_main>(accT[nt], at, b_hi, b_lo);
+                        else x3b_mfma_x<j - n_main - n_t, ks == 6>(accx[nt], axh, axl, b_hi, b_lo);
                         __builtin_amdgcn_sched_barrier(0);
                     });
                 });
@@ -450,7 +412,7 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (last_of_chunk) chunk++;
             });
-            // ---- epilogue, in fp32; the result is split into (hi, lo) again (az_tower_x3b.h: the same arithmetic) -------------
+            // ---- epilogue, in fp32; the result is split into (hi, lo) again (x3b_epilogue_value) -------------
             const unsigned ep_base = lds_base + X3D::OFF_EPI + (conv & 1) * 1024 + q * 16;
             // sa_hi / sa_lo: LDS address of the lane's quarter-octet (q) of output-channel tile 0 in the tile's cell, hi and lo planes (the
             // output-channel tile is an immediate offset of the store: one address per tile and plane set, not three instructions per store)
@@ -460,43 +422,18 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
                 constexpr bool TT = decltype(tt_c)::value;  // tile T
                 constexpr int mt = decltype(mt_c)::value;
                 const int co0 = 16 * mt + 4 * q;
-                f32x4 v;
-                const f32x4 a_in = a;
-                if constexpr (!TT) {
-                    v = a * INV_SPLIT;
-                    a = next_bias; // (2048 x the next conv's bias: scaled on the host)
-                } else { // lanes q == 0: rows hi 48, hi 49, lo 48, lo 49 of the gather k-step (+ bias), plus the tap planes
-                    v = (f32x4){(a[0] + a[2]) * INV_SPLIT, (a[1] + a[3]) * INV_SPLIT, 0.f, 0.f};
-                    if constexpr (!IS_FIRST) {
-                        v[0] += s[0];
-                        v[1] += s[1];
+                const f32x4 o = x3b_epilogue_value<KIND, TT, IS_FIRST>(a, xr, s, sc, sh, next_bias, q);
+                if constexpr (KIND == 2) { // o: the tower output
+                    half4 hi, lo;
+                    split4(o, hi, lo);
+                    if (((opaque((int)livem) >> nt) & 1) && co0 < p.xout_c) { // a board of the batch (the column's global row, looked up again: once per
+                                                                            // forward); channels past the stride (tile T, q > 0) are not stored
+                        const int e = p.xd_pos[tile[nt] * 16 + l15];
+                        const size_t gr = (size_t)(blockIdx.x * p.xd_nb + (e >> 8)) * p.HW + (e & 255);
+                        *(half4 *)(p.xout + gr * p.xout_c + co0) = hi;
+                        *(half4 *)(p.xout_lo + gr * p.xout_c + co0) = lo;
                     }
-                    if (q != 0) v = (f32x4){0.f, 0.f, 0.f, 0.f}; // (rows 4..15: centre-tap rows / unused)
-                    a = q == 0 ? (f32x4){next_bias[0], next_bias[1], 0.f, 0.f} : (f32x4){0.f, 0.f, 0.f, 0.f};
-                }
-                f32x4 o;
-                if constexpr (KIND == 0) {
-                    o = __builtin_elementwise_max(v, v * 0.01f);
-                } else {
-                    // xr + a / 2048 in one instruction: a / 2048 is exact (a power of two), so the fma has the bits of multiply-then-add
-                    f32x4 xv;
-                    if constexpr (!TT) xv = __builtin_elementwise_fma(a_in, (f32x4){INV_SPLIT, INV_SPLIT, INV_SPLIT, INV_SPLIT}, xr);
-                    else xv = xr + v;
-                    xr = xv;
-                    if constexpr (KIND == 2) {
-                        half4 hi, lo;
-                        split4(xv, hi, lo);
-                        if (((opaque((int)livem) >> nt) & 1) && co0 < p.xout_c) { // a board of the batch (the column's global row, looked up again: once per
-                                                                                // forward); channels past the stride (tile T, q > 0) are not stored
-                            const int e = p.xd_pos[tile[nt] * 16 + l15];
-                            const size_t gr = (size_t)(blockIdx.x * p.xd_nb + (e >> 8)) * p.HW + (e & 255);
-                            *(half4 *)(p.xout + gr * p.xout_c + co0) = hi;
-                            *(half4 *)(p.xout_lo + gr * p.xout_c + co0) = lo;
-                        }
-                        return;
-                    }
-                    f32x4 t = __builtin_elementwise_fma(sc, xv, sh);
-                    o = __builtin_elementwise_max(t, t * 0.01f);
+                    return;
                 }
                 half4 hi, lo;
                 split4_planes(o, hi, lo); // (between convs the lo half is unscaled; the tower OUTPUT above keeps lo x 2048: the head's format)
