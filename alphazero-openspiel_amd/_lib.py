@@ -113,6 +113,10 @@ PROTOTYPES = [
     ("az_engine_export", C.c_int, [_vp, C.POINTER(AzExampleView), _vp]),
     ("az_engine_export_device_bytes", C.c_int64, [_vp]),
     ("az_engine_export_device", C.c_int, [_vp, _vp, C.c_int64, _vp]),
+    ("az_engine_stream_begin", C.c_int, [_vp, C.c_uint64, _vp]),
+    ("az_engine_stream_ready", C.c_int64, [_vp, _vp]),
+    ("az_engine_stream_take_bytes", C.c_int64, [_vp, C.c_int64]),
+    ("az_engine_stream_take_device", C.c_int, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _vp]),
     ("az_engine_roots_device_bytes", C.c_int64, [_vp]),
     ("az_engine_export_roots_device", C.c_int, [_vp, _vp, C.c_int64, _vp]),
     ("az_engine_read_root", C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double),

@@ -565,27 +565,35 @@ __device__ void compact_jobs(const Params &p, const int wg, const int n_wg, cons
     }
 }
 
-// The slot's game is over: publish its length and result, take the next game id of the generation (device counter).
-// Returns false when no game is left (the slot is stored idle).
-__device__ __forceinline__ bool finish_game_take_next(const Params &p, int g, int lane, SlotRegs &sr, float ret0,
-                                                      unsigned long long st_moves) {
-    unsigned long long nxt = 0;
+// Row of the rec_* arrays that holds game `gid`: the id itself in a closed generation (gid < n_games <= max_games), the id
+// modulo the store's capacity in stream mode (the store is a ring).  Cold path only: move_step and game turnover.
+__device__ __forceinline__ size_t rec_row(const Params &p, int gid) {
+    return p.stream_mode ? (size_t)((unsigned long long)gid % (unsigned long long)p.max_games) : (size_t)gid;
+}
+// The next game id for a slot (lane 0's result, broadcast); false when none may be handed out.  A closed generation counts
+// next_game up to n_games (overshooting is harmless: nothing reads the counter's excess).  A stream takes an id only while it
+// is below *hand_limit, by compare-and-swap: no id is skipped when the limit rises later, none is handed out twice.
+__device__ __forceinline__ bool take_next_game(const Params &p, int lane, SlotRegs &sr) {
+    unsigned long long nxt = ~0ull;
     if (lane == 0) {
-        p.rec_len[sr.gid] = sr.rs.ply - p.start.ply;
-        p.rec_ret0[sr.gid] = ret0;
-        __threadfence(); // records before the done-count
-        atomicAdd(p.games_done, 1ull);
-        nxt = atomicAdd(p.next_game, 1ull);
+        if (p.stream_mode) {
+            const unsigned long long lim = __hip_atomic_load(p.hand_limit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            unsigned long long cur = __hip_atomic_load(p.next_game, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            while (cur < lim) { // (bounded: every failed exchange means another slot took an id, and there are < lim of them)
+                const unsigned long long seen = atomicCAS(p.next_game, cur, cur + 1ull);
+                if (seen == cur) {
+                    nxt = cur;
+                    break;
+                }
+                cur = seen;
+            }
+        } else {
+            nxt = atomicAdd(p.next_game, 1ull);
+            if ((long long)nxt >= p.n_games) nxt = ~0ull;
+        }
     }
     nxt = ((unsigned long long)rflu((uint32_t)(nxt >> 32)) << 32) | rflu((uint32_t)nxt);
-    if ((long long)nxt >= p.n_games) {
-        sr.gid = -1;
-        if (lane == 0) {
-            slot_store(p, g, sr, PH_IDLE);
-            p.stats[(size_t)g * ST_N + ST_MOVES] += st_moves;
-        }
-        return false;
-    }
+    if (nxt == ~0ull) return false;
     sr.gid = (int)nxt;
     sr.rs = p.start;
     if (p.starts) { // a start position per game id (az_engine_set_start_positions)
@@ -595,6 +603,28 @@ __device__ __forceinline__ bool finish_game_take_next(const Params &p, int g, in
         sr.rs.ply = rfl(s->ply);
     }
     sr.sims = 0;
+    return true;
+}
+// The slot's game is over: publish its length and result, take the next game id (device counter).
+// Returns false when no game is left, or - in stream mode - none may be handed out yet: the slot is stored idle with game id -1
+// (a stream's slot asks again at the start of each of its ticks: move_step).
+__device__ __forceinline__ bool finish_game_take_next(const Params &p, int g, int lane, SlotRegs &sr, float ret0,
+                                                      unsigned long long st_moves) {
+    if (lane == 0) {
+        const size_t row = rec_row(p, sr.gid);
+        p.rec_ret0[row] = ret0;
+        p.rec_len[row] = sr.rs.ply - p.start.ply; // (stream mode: a non-zero length marks the row finished - read after the launch)
+        __threadfence(); // records before the done-count
+        atomicAdd(p.games_done, 1ull);
+    }
+    if (!take_next_game(p, lane, sr)) {
+        sr.gid = -1;
+        if (lane == 0) {
+            slot_store(p, g, sr, PH_IDLE);
+            p.stats[(size_t)g * ST_N + ST_MOVES] += st_moves;
+        }
+        return false;
+    }
     return true;
 }
 // Rule of the tree a game's first search runs on, when the agent is the first to move from p.start.  A bot that keeps its
@@ -649,6 +679,12 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
         rsv_np = -1;
     };
 
+    if (ph == PH_IDLE) { // stream mode: the slot finished a game while no id could be handed out; the limit may have risen since
+        if (!take_next_game(p, lane, sr)) return; // (nothing was changed: still idle, game id -1)
+        reroot(p, g, sr, t, -1, true, start_rule(p), lane, fault, st_compact);
+        ph = p.use_dirichlet ? PH_NEED_ROOT : PH_RUN;
+    }
+
     if (ph == PH_OPP_DONE) { // arena: apply the move the opponent bot chose; the agent's tree follows it (alphazerobot.py:60-64)
         const int action = rfl(p.opp_action[g]);
         uint32_t c0 = rflu(t.nd[sr.root].C0);
@@ -656,9 +692,9 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
         int cact = lane < nc ? (int)(t.nd[c0 + lane].META & 0xFFFFu) : -1;
         unsigned long long hit = __ballot(cact == action);
         const int sel = (p.keep_tree && hit) ? __ffsll(hit) - 1 : -1;
-        if (sr.rs.ply >= p.max_plies || sr.gid >= p.max_games || sr.gid < 0) fault |= AZ_FAULT_PLY_OVERFLOW;
+        if (sr.rs.ply >= p.max_plies || (!p.stream_mode && sr.gid >= p.max_games) || sr.gid < 0) fault |= AZ_FAULT_PLY_OVERFLOW;
         else if (lane == 0) { // the ply is recorded (state, move; no search statistics: n_children = 0)
-            size_t ri = (size_t)sr.gid * p.max_plies + sr.rs.ply;
+            size_t ri = rec_row(p, sr.gid) * p.max_plies + sr.rs.ply;
             p.rec_states[ri * 2] = sr.rs.bb0;
             p.rec_states[ri * 2 + 1] = sr.rs.bb1;
             p.rec_move[ri] = (uint16_t)action;
@@ -704,7 +740,7 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
         }
         long long tot = wave_sum_ll((long long)cn);
         if (nc == 0 || (tot <= 0 && p.arena_agent != AZ_ARENA_NET)) fault |= AZ_FAULT_NO_VISITS;
-        if (sr.rs.ply >= p.max_plies || sr.gid >= p.max_games || sr.gid < 0) fault |= AZ_FAULT_PLY_OVERFLOW;
+        if (sr.rs.ply >= p.max_plies || (!p.stream_mode && sr.gid >= p.max_games) || sr.gid < 0) fault |= AZ_FAULT_PLY_OVERFLOW;
         if (fault) {
             release_rsv();
             if (lane == 0) {
@@ -788,7 +824,7 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
         }
         int action = rfl(__shfl(cact, sel));
         // the example record (game_utils.py:169): state + root child visits; pi = N/sum is formed on the host
-        size_t ri = (size_t)sr.gid * p.max_plies + sr.rs.ply;
+        size_t ri = rec_row(p, sr.gid) * p.max_plies + sr.rs.ply;
         if (lane == 0) {
             p.rec_states[ri * 2] = sr.rs.bb0;
             p.rec_states[ri * 2 + 1] = sr.rs.bb1;
@@ -886,8 +922,9 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
     const float value_raw = (values && !MAPPED) ? values[g] : 0.f;
     slot_load(p, g, sr);
     const int ph = rfl(ph_raw);
-    if (ph == PH_MOVE || ph == PH_NEED_ROOT || ph == PH_OPP_DONE) { // the agent's move / the opponent's move / the next search's
-                                                                    // root request: ends this slot's tick
+    if (ph == PH_MOVE || ph == PH_NEED_ROOT || ph == PH_OPP_DONE || (ph == PH_IDLE && p.stream_mode && sr.gid < 0)) {
+        // the agent's move / the opponent's move / the next search's root request / a stream's stalled slot asking for a game id
+        // again: ends this slot's tick
         if (MAPPED && lane == 0) p.req_row[g] = row;
         move_step<GAME>(p, g, lane, ph, sr, obs_row, row);
         return;
@@ -1408,6 +1445,7 @@ __global__ void az_reset_kernel(Params p) {
         *p.next_game = (unsigned long long)(p.n_games < p.G ? p.n_games : p.G);
         *p.games_done = 0;
         *p.faults = 0;
+        *p.hand_limit = (unsigned long long)(p.stream_mode ? p.max_games : p.n_games);
     }
 }
 
@@ -1626,7 +1664,7 @@ extern "C" int az_engine_create(const az_config *cfg, az_engine **out) {
     DA(p.root, G); DA(p.alloc, G); DA(p.leaf_node, G); DA(p.path, G * p.pstride);
     DA(p.bb0, G); DA(p.bb1, G); DA(p.leaf_bb0, G); DA(p.leaf_bb1, G);
     DA(p.stats, G * ST_N); DA(p.eta_buf, G * p.maxc);
-    DA(p.next_game, 1); DA(p.games_done, 1); DA(p.faults, 1);
+    DA(p.next_game, 1); DA(p.games_done, 1); DA(p.faults, 1); DA(p.hand_limit, 1);
     if (c.arena_agent != AZ_ARENA_SELF_PLAY) DA(p.opp_action, G);
     double *d_log = nullptr;
     // log(n) table: the UCT opponent's explore counts stay <= opponent_sims; an AZ_SELECT_UCT tree's root gains n_playouts
@@ -1672,6 +1710,27 @@ extern "C" int az_engine_sizes(const az_engine *e, az_sizes *out) {
     return AZ_OK;
 }
 
+// az_engine_reset and az_engine_stream_begin: arm every slot (closed generation of n_games, or an open-ended stream)
+static int reset_common(az_engine *e, uint64_t seed, int64_t n_games, bool streaming, void *stream) {
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    e->p.seed = seed;
+    e->p.n_games = n_games;
+    e->p.stream_mode = streaming ? 1 : 0;
+    e->n_games = n_games;
+    e->streaming = streaming;
+    e->read_pos = 0;
+    e->ready_known = 0;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(e, hipMemsetAsync(e->p.rec_len, 0, sizeof(int) * (size_t)e->cfg.max_games, st));
+    hipLaunchKernelGGL(az_reset_kernel, dim3((e->p.G + 255) / 256), dim3(256), 0, st, e->p);
+    HIPCHK(e, hipGetLastError());
+    e->reset_done = true;
+    e->ticks = 0;
+    e->rows_mapped = false;
+    e->rows_live = 0;
+    return AZ_OK;
+}
+
 extern "C" int az_engine_reset(az_engine *e, uint64_t seed, int64_t n_games, void *stream) {
     if (!e) return AZ_E_INVALID;
     if (n_games < 1 || n_games > e->cfg.max_games) {
@@ -1682,18 +1741,156 @@ extern "C" int az_engine_reset(az_engine *e, uint64_t seed, int64_t n_games, voi
         e->err = "n_games exceeds the games given to az_engine_set_start_positions";
         return AZ_E_INVALID;
     }
+    return reset_common(e, seed, n_games, false, stream);
+}
+
+// ---- stream mode: an open-ended run over a record store used as a ring (include/az_engine.h) ---------------------------------
+#define AZ_STREAM_MAX_ID 0x7FFFFFFFll // a slot keeps its game id in an int32 (and Philox keys on 32 bits of it)
+
+extern "C" int az_engine_stream_begin(az_engine *e, uint64_t seed, void *stream) {
+    if (!e) return AZ_E_INVALID;
+    const char *why = nullptr;
+    if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) why = "an arena engine (game id i fixes the agent's side, records are read by id)";
+    else if (e->cfg.manual_moves) why = "a manual_moves engine (its slots are re-armed by the caller)";
+    else if (e->cfg.rng_mode == AZ_RNG_INJECTED) why = "rng_mode = AZ_RNG_INJECTED (injected draws are tables indexed by game id)";
+    else if (e->has_prefix) why = "a start prefix is set (az_engine_set_start_prefix)";
+    else if (e->p.starts) why = "a start-position table is set (az_engine_set_start_positions)";
+    else if (e->cfg.max_games < e->cfg.n_slots) why = "max_games < n_slots (slots 0..G-1 start ids 0..G-1, each needs a row of the ring)";
+    if (why) {
+        e->err = std::string("az_engine_stream_begin is for plain self-play engines: refused for ") + why;
+        return AZ_E_INVALID;
+    }
+    return reset_common(e, seed, AZ_STREAM_MAX_ID, true, stream);
+}
+
+static int stream_checks(az_engine *e, const char *what) {
+    if (!e) return AZ_E_INVALID;
+    if (!e->reset_done || !e->streaming) {
+        e->err = std::string(what) + " needs az_engine_stream_begin first";
+        return AZ_E_STATE;
+    }
+    return AZ_OK;
+}
+// what a stream-mode engine refuses: the entry reads records by game id, or ticks / lists slots outside the one stream
+static int refuse_in_stream(az_engine *e, const char *what) {
+    if (e && e->streaming) {
+        e->err = std::string(what) + " is refused in stream mode (az_engine_stream_begin): records live in a ring and leave through "
+                 "az_engine_stream_take_device, and the engine is ticked whole, on one stream; az_engine_reset returns to a closed generation";
+        return AZ_E_STATE;
+    }
+    return AZ_OK;
+}
+
+extern "C" int64_t az_engine_stream_ready(az_engine *e, void *stream) {
+    int rc = stream_checks(e, "az_engine_stream_ready");
+    if (rc != AZ_OK) return rc;
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    e->p.seed = seed;
-    e->p.n_games = n_games;
-    e->n_games = n_games;
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(e, hipMemsetAsync(e->p.rec_len, 0, sizeof(int) * (size_t)e->cfg.max_games, st));
-    hipLaunchKernelGGL(az_reset_kernel, dim3((e->p.G + 255) / 256), dim3(256), 0, st, e->p);
+    const size_t M = (size_t)e->cfg.max_games;
+    e->h_ring.resize(M);
+    HIPCHK(e, hipMemcpyAsync(e->h_ring.data(), e->p.rec_len, M * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    // (a row is written by the game whose id maps to it, and only after the row's previous game was taken and the row cleared:
+    //  the hand-out limit - so a non-zero length at row (read_pos + k) % M is game read_pos + k's)
+    size_t k = 0;
+    while (k < M && e->h_ring[(size_t)((uint64_t)(e->read_pos + (int64_t)k) % M)] != 0) k++;
+    e->ready_known = (int64_t)k;
+    return (int64_t)k;
+}
+
+static void export_offsets(size_t n, size_t mp, size_t mc, size_t off[9]);
+
+extern "C" int64_t az_engine_stream_take_bytes(const az_engine *e, int64_t n_games) {
+    if (!e || n_games < 1 || n_games > e->cfg.max_games) return AZ_E_INVALID;
+    size_t off[9];
+    export_offsets((size_t)n_games, (size_t)e->p.max_plies, (size_t)e->p.maxc, off);
+    return (int64_t)off[8];
+}
+
+// One game's share of one record array: `bytes` contiguous bytes, by the threads of a workgroup, in the widest unit that the two
+// addresses and the length allow (16 bytes for the states and - connect_four - the value rows; ring row and packed row of a game
+// differ, so the narrower arrays' alignment depends on both indices).
+__device__ __forceinline__ void take_copy(char *__restrict__ dst, const char *__restrict__ src, const size_t bytes, const int tid,
+                                          const int n_threads) {
+    const size_t bits = (size_t)dst | (size_t)src | bytes;
+    if (!(bits & 15)) {
+        for (size_t i = (size_t)tid; i < bytes / 16; i += n_threads) ((uint4 *)dst)[i] = ((const uint4 *)src)[i];
+    } else if (!(bits & 3)) {
+        for (size_t i = (size_t)tid; i < bytes / 4; i += n_threads) ((uint32_t *)dst)[i] = ((const uint32_t *)src)[i];
+    } else {
+        for (size_t i = (size_t)tid; i < bytes; i += n_threads) dst[i] = src[i];
+    }
+}
+struct TakeOut { // the eight arrays of the packed layout, inside the caller's buffer
+    int *game_len;
+    float *game_ret0;
+    char *states, *move, *nchild, *child_action, *child_visits;
+    double *value;
+};
+// az_engine_stream_take_device: a workgroup per game.  Game first + j leaves row (first + j) % max_games of the ring for row j
+// of the packed arrays; its on-policy value targets are formed here from the result (game_utils.py:200-204: z_i = returns()[0] *
+// (-1)^i); the row's length is cleared (the mark of a finished game: az_engine_stream_ready), and the hand-out limit rises to
+// new_limit - the tick kernels that follow on the stream may hand out the ids whose rows this launch has just freed.
+#define TAKE_THREADS 256
+__global__ __launch_bounds__(TAKE_THREADS) void az_stream_take_kernel(Params p, TakeOut o, unsigned long long first, int n,
+                                                                      unsigned long long new_limit, int on_policy) {
+    const int j = blockIdx.x, tid = threadIdx.x;
+    if (j >= n) return;
+    const size_t r = (size_t)((first + (unsigned long long)j) % (unsigned long long)p.max_games);
+    const size_t mp = (size_t)p.max_plies, mc = (size_t)p.maxc;
+    const int len = p.rec_len[r];
+    const float ret0 = p.rec_ret0[r];
+    take_copy(o.states + (size_t)j * mp * 16, (const char *)p.rec_states + r * mp * 16, mp * 16, tid, TAKE_THREADS);
+    take_copy(o.move + (size_t)j * mp * 2, (const char *)p.rec_move + r * mp * 2, mp * 2, tid, TAKE_THREADS);
+    take_copy(o.nchild + (size_t)j * mp, (const char *)p.rec_nchild + r * mp, mp, tid, TAKE_THREADS);
+    take_copy(o.child_action + (size_t)j * mp * mc * 2, (const char *)p.rec_child_action + r * mp * mc * 2, mp * mc * 2, tid, TAKE_THREADS);
+    take_copy(o.child_visits + (size_t)j * mp * mc * 4, (const char *)p.rec_child_visits + r * mp * mc * 4, mp * mc * 4, tid, TAKE_THREADS);
+    const int p0 = p.start.ply;
+    for (int i = tid; i < (int)mp; i += TAKE_THREADS) {
+        double v = p.rec_value[r * mp + i];
+        if (on_policy && i >= p0 && i < p0 + len) v = (i & 1) ? -(double)ret0 : (double)ret0;
+        o.value[(size_t)j * mp + i] = v;
+    }
+    __syncthreads(); // every thread has read the row's length
+    if (tid == 0) {
+        o.game_len[j] = len;
+        o.game_ret0[j] = ret0;
+        p.rec_len[r] = 0;
+        if (j == 0) __hip_atomic_store(p.hand_limit, new_limit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+extern "C" int az_engine_stream_take_device(az_engine *e, int64_t n_games, void *dev_buf, int64_t bytes, int64_t *first_game_out,
+                                            void *stream) {
+    int rc = stream_checks(e, "az_engine_stream_take_device");
+    if (rc != AZ_OK) return rc;
+    if (!dev_buf || n_games < 1 || n_games > e->cfg.max_games || ((size_t)dev_buf & 15)) {
+        e->err = "az_engine_stream_take_device: n_games must be in [1, max_games], dev_buf non-null and 16-byte aligned";
+        return AZ_E_INVALID;
+    }
+    size_t off[9];
+    export_offsets((size_t)n_games, (size_t)e->p.max_plies, (size_t)e->p.maxc, off);
+    if (bytes < (int64_t)off[8]) {
+        e->err = "az_engine_stream_take_device: buffer of " + std::to_string(bytes) + " bytes is smaller than az_engine_stream_take_bytes(" +
+                 std::to_string(n_games) + ") = " + std::to_string(off[8]);
+        return AZ_E_INVALID;
+    }
+    if (n_games > e->ready_known) {
+        e->err = "az_engine_stream_take_device: " + std::to_string(n_games) + " games asked for, " + std::to_string(e->ready_known) +
+                 " were ready at the last az_engine_stream_ready (ask it first)";
+        return AZ_E_STATE;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    char *b = (char *)dev_buf;
+    TakeOut o = {(int *)(b + off[0]), (float *)(b + off[1]), b + off[2], b + off[3], b + off[4], b + off[5], b + off[6], (double *)(b + off[7])};
+    int64_t limit = e->read_pos + n_games + e->cfg.max_games;
+    if (limit > AZ_STREAM_MAX_ID) limit = AZ_STREAM_MAX_ID;
+    hipLaunchKernelGGL(az_stream_take_kernel, dim3((unsigned)n_games), dim3(TAKE_THREADS), 0, (hipStream_t)stream, e->p, o,
+                       (unsigned long long)e->read_pos, (int)n_games, (unsigned long long)limit, e->cfg.backup == AZ_BACKUP_ON_POLICY ? 1 : 0);
     HIPCHK(e, hipGetLastError());
-    e->reset_done = true;
-    e->ticks = 0;
-    e->rows_mapped = false;
-    e->rows_live = 0;
+    if (first_game_out) *first_game_out = e->read_pos;
+    e->read_pos += n_games;
+    e->ready_known -= n_games;
     return AZ_OK;
 }
 
@@ -1753,6 +1950,7 @@ extern "C" int az_engine_set_start_prefix(az_engine *e, const int32_t *actions, 
         return AZ_E_INVALID;
     }
     e->p.start = s;
+    e->has_prefix = n > 0;
     e->p.starts = nullptr; // one prefix for every game again
     e->starts_n = 0;
     e->reset_done = false; // caller must reset again so that slots pick the new start up
@@ -1887,6 +2085,7 @@ extern "C" int az_engine_advance(az_engine *e, const float *priors, const float 
 
 extern "C" int az_engine_compact_rows(az_engine *e, int32_t *n_live_out, void *stream) {
     if (!e || !n_live_out) return AZ_E_INVALID;
+    if (refuse_in_stream(e, "az_engine_compact_rows")) return AZ_E_STATE;
     if (!e->reset_done || e->ticks == 0) {
         e->err = "az_engine_compact_rows before the first tick";
         return AZ_E_STATE;
@@ -1918,6 +2117,7 @@ extern "C" int az_engine_compact_rows(az_engine *e, int32_t *n_live_out, void *s
 extern "C" int az_engine_advance_rows(az_engine *e, int32_t n_rows, const float *priors, const float *values, float *obs_out, void *stream) {
     int rc = advance_checks(e, obs_out);
     if (rc != AZ_OK) return rc;
+    if (refuse_in_stream(e, "az_engine_advance_rows")) return AZ_E_STATE;
     if (!e->rows_mapped || !priors || !values) {
         e->err = "az_engine_advance_rows needs az_engine_compact_rows first, and priors / values";
         return AZ_E_STATE;
@@ -1936,6 +2136,7 @@ extern "C" int az_engine_advance_slots(az_engine *e, int32_t first_slot, int32_t
                                        float *obs_out, void *stream) {
     int rc = advance_checks(e, obs_out);
     if (rc != AZ_OK) return rc;
+    if (refuse_in_stream(e, "az_engine_advance_slots")) return AZ_E_STATE;
     if (first_slot < 0 || n_slots < 1 || first_slot + n_slots > e->p.G || !priors || !values) {
         e->err = "az_engine_advance_slots: slot range outside [0, n_slots) or NULL priors/values";
         return AZ_E_INVALID;
@@ -2060,7 +2261,7 @@ extern "C" int az_engine_progress(az_engine *e, az_progress *out, void *stream) 
         if (phase[g] == PH_IDLE) out->slots_idle++;
         if (phase[g] == PH_SEARCH_DONE) out->slots_search_done++;
     }
-    out->games_started = (int64_t)(next_game < (unsigned long long)e->n_games ? next_game : (unsigned long long)e->n_games);
+    out->games_started = (int64_t)(next_game < (unsigned long long)e->n_games ? next_game : (unsigned long long)e->n_games); // (a closed generation's counter overshoots)
     out->games_done = (int64_t)done;
     out->error_flags = faults;
     if (faults) {
@@ -2095,6 +2296,7 @@ extern "C" int az_engine_poll(az_engine *e, int64_t *games_done, uint32_t *error
 
 extern "C" int az_engine_export(az_engine *e, az_example_view *out, void *stream) {
     if (!e || !out) return AZ_E_INVALID;
+    if (refuse_in_stream(e, "az_engine_export")) return AZ_E_STATE;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
     size_t ng = (size_t)e->n_games, mp = (size_t)e->p.max_plies, mc = (size_t)e->p.maxc;
@@ -2152,6 +2354,7 @@ __global__ void fill_on_policy_values_kernel(const int *len, const float *ret0, 
 
 extern "C" int64_t az_engine_export_device_bytes(const az_engine *e) {
     if (!e) return AZ_E_INVALID;
+    if (refuse_in_stream(const_cast<az_engine *>(e), "az_engine_export_device_bytes")) return AZ_E_STATE; // (only the error text is written)
     size_t off[9];
     export_offsets((size_t)e->n_games, (size_t)e->p.max_plies, (size_t)e->p.maxc, off);
     return (int64_t)off[8];
@@ -2159,6 +2362,7 @@ extern "C" int64_t az_engine_export_device_bytes(const az_engine *e) {
 
 extern "C" int az_engine_export_device(az_engine *e, void *dev_buf, int64_t bytes, void *stream) {
     if (!e || !dev_buf) return AZ_E_INVALID;
+    if (refuse_in_stream(e, "az_engine_export_device")) return AZ_E_STATE;
     size_t n = (size_t)e->n_games, mp = (size_t)e->p.max_plies, mc = (size_t)e->p.maxc, off[9];
     export_offsets(n, mp, mc, off);
     if (bytes < (int64_t)off[8]) {

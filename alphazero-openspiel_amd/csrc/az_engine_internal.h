@@ -70,6 +70,11 @@ struct Params {
     int *row_slot, *req_row, *n_rows_live;
     // global counters
     unsigned long long *next_game, *games_done;
+    // stream mode (az_engine_stream_begin): game ids are open-ended, id i records into row i % max_games of the rec_* arrays, and
+    // an id may be handed out only while it is below *hand_limit (device memory: a captured tick graph bakes Params, and
+    // az_engine_stream_take_device raises the limit between replays)
+    int stream_mode;
+    unsigned long long *hand_limit;
     unsigned int *faults;
     // injected randomness
     const double *etas, *us;
@@ -114,6 +119,11 @@ struct az_engine {
     int64_t starts_cap = 0, starts_n = 0;
     bool rows_mapped = false; // az_engine_compact_rows has been called since the last reset
     int rows_live = 0;
+    bool streaming = false;   // az_engine_stream_begin since the last az_engine_reset
+    bool has_prefix = false;  // az_engine_set_start_prefix gave a non-empty prefix
+    int64_t read_pos = 0;     // stream mode: the first game id not yet taken
+    int64_t ready_known = 0;  // ... and how many consecutive finished games the last az_engine_stream_ready found from there
+    std::vector<int32_t> h_ring; // ... host copy of the rec_len ring for that scan
     bool may_compact = false; // a pool cannot hold a whole game: re-rooting may have to compact (launches carry extra workgroups)
     // host mirrors for export
     std::vector<int32_t> h_len;

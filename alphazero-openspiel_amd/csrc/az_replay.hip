@@ -346,6 +346,11 @@ extern "C" int az_replay_append_engine(az_replay *r, az_engine *e, void *stream)
         r->err = "engine and replay store were created for different games / devices";
         return AZ_E_INVALID;
     }
+    if (e->streaming) {
+        r->err = "az_replay_append_engine is refused for an engine in stream mode (az_engine_stream_begin): it reads the records by game "
+                 "id; append what az_engine_stream_take_device packs with az_replay_append_device";
+        return AZ_E_STATE;
+    }
     hipStream_t st = (hipStream_t)stream;
     RCHK(r, hipSetDevice(r->cfg.device));
     RCHK(r, hipStreamSynchronize(st));

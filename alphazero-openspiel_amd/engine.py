@@ -276,6 +276,35 @@ class SelfPlayEngine:
         return buf
 
 
+    # ------------------------------------------------------------------ stream mode (include/az_engine.h)
+    def stream_begin(self, seed=None):
+        """Start an open-ended run instead of reset(n_games): game ids 0, 1, 2, ..., records in a ring of max_games rows.
+        Plain self-play engines only (EngineError names the reason otherwise); reset() returns to a closed generation."""
+        if seed is None:
+            seed = self.cfg.seed
+        self._check(self.lib.az_engine_stream_begin(self._h, int(seed) & (2 ** 64 - 1), self._stream()))
+        self.n_games = 0
+
+    def stream_ready(self):
+        """Finished games in id order that have not been taken yet (at most max_games); synchronises the current stream."""
+        return int(self._check(self.lib.az_engine_stream_ready(self._h, self._stream())))
+
+    def stream_take_bytes(self, n_games):
+        return int(self._check(self.lib.az_engine_stream_take_bytes(self._h, int(n_games))))
+
+    def stream_take(self, n_games, out=None):
+        """The next n_games finished games -> (uint8 device tensor in the packed layout of export_device() for a generation of
+        n_games games, id of the first one).  One kernel on the current stream; call stream_ready() first.
+        out: a uint8 device tensor to pack into (at least stream_take_bytes(n_games) bytes) instead of a fresh one."""
+        if out is None:
+            out = torch.empty(self.stream_take_bytes(n_games), dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.device != self.device:
+            raise EngineError("expected a contiguous uint8 tensor on %s" % (self.device,))
+        first = C.c_int64(-1)
+        self._check(self.lib.az_engine_stream_take_device(self._h, int(n_games), C.c_void_p(out.data_ptr()), int(out.numel()),
+                                                          C.byref(first), self._stream()))
+        return out, int(first.value)
+
     def roots_device_bytes(self):
         return int(self._check(self.lib.az_engine_roots_device_bytes(self._h)))
 
@@ -598,6 +627,106 @@ def tick_until(driver, check_every, done, max_ticks, what, *engines):
         if max_ticks is not None and driver.ticks >= max_ticks:
             raise EngineError("%s did not finish within %d ticks: %s"
                               % (what, max_ticks, " / ".join(repr(e.progress()) for e in engines)))
+
+
+def stream_take_layout(n_games, max_plies, max_children):
+    """(name, dtype, shape, byte offset) of every array in a take of n_games games off a stream + total bytes: the packed
+    device export of a generation of n_games games (device_export_layout), by construction."""
+    return device_export_layout(n_games, max_plies, max_children)
+
+
+class SelfPlayStream:
+    """Continuous self-play: an engine in stream mode (az_engine_stream_begin), its request buffers and ONE tick driver.
+    Slots never wait for the end of a generation: a finished slot takes the next game id at once, and take(n) hands the next n
+    finished games over, in id order, while the others play on.  With an unchanged net the games are, id for id, those of the
+    closed generation run_selfplay plays from the same seed.
+
+    set_evaluator(ev) swaps the network between takes.  Games in flight go on under the new network from the next tick and
+    keep their search trees - a game that straddles the swap was searched partly with the old and partly with the new net
+    (the usual semantics of asynchronous self-play, and the one place where a streamed game is not what a closed generation
+    would have played)."""
+
+    def __init__(self, engine, evaluator, seed=None, use_graph=True, ticks_per_graph=16, check_every=32):
+        self.engine, self.evaluator = engine, evaluator
+        self.use_graph, self.check_every = bool(use_graph), max(1, int(check_every))
+        self.ticks_per_graph = min(max(1, int(ticks_per_graph)), self.check_every)
+        engine.stream_begin(seed)
+        self.obs, self.pri, self.val = engine.alloc_io()
+        self.taken = 0          # games handed over so far = the id of the next one
+        self.idle_sum = 0       # sum over the checks of the slots found stalled (only counted when count_idle)
+        self.checks = 0
+        self.count_idle = False  # measurement aid: a full progress() per check
+        self.captures = 0
+        self.driver = TickDriver(engine.device, self._tick)
+        if self.use_graph:
+            self.driver.capture(self.ticks_per_graph)
+            self.captures += 1
+
+    def _tick(self):
+        self.engine.advance(self.pri, self.val, self.obs)
+        self.evaluator(self.obs, self.pri, self.val)
+
+    @property
+    def ticks(self):
+        return self.driver.ticks
+
+    def set_evaluator(self, evaluator):
+        """Play on with another network.  Synchronises the device and captures the tick graph again (a graph holds the
+        evaluator's kernels and buffers); the caller closes the old evaluator afterwards."""
+        torch.cuda.synchronize(self.engine.device)
+        self.evaluator = evaluator
+        if self.driver.graph is not None:
+            self.driver.graph = None
+            self.driver.recapture()
+            self.captures += 1
+
+    def take(self, n_games, max_ticks=None, out=None):
+        """Tick in batches of check_every until n_games games are ready, then -> (packed uint8 device tensor, id of the first
+        game): SelfPlayEngine.stream_take.  max_ticks bounds the ticks spent in THIS call (EngineError with the engine's
+        progress beyond it)."""
+        e, n = self.engine, int(n_games)
+        if n < 1 or n > e.sizes.max_games:
+            raise ValueError("take(%d): a take holds between 1 and max_games = %d games" % (n, e.sizes.max_games))
+        start = self.driver.ticks
+
+        def ready():  # the two-word poll first: the ring is scanned only once enough games have finished
+            self.checks += 1
+            if self.count_idle:
+                self.idle_sum += e.progress()["slots_idle"]
+            return e.games_done() - self.taken >= n and e.stream_ready() >= n
+
+        if not ready():  # (games may be waiting already: after a larger capacity filled up, or when taking a few at a time)
+            tick_until(self.driver, self.check_every, ready, None if max_ticks is None else start + int(max_ticks),
+                       "take(%d) off the self-play stream" % n, e)
+        buf, first = e.stream_take(n, out)
+        self.taken = first + n
+        return buf, first
+
+    def close(self):
+        """Drain the stream (the ticks in flight use the request buffers and the evaluator); the caller closes engine and
+        evaluator afterwards."""
+        if self.engine is not None:
+            torch.cuda.synchronize(self.engine.device)
+        self.driver = None
+        self.engine = self.evaluator = None
+        self.obs = self.pri = self.val = None
+
+
+def stream_capacity(n_local, n_slots, capacity=None):
+    """Rows of the record ring behind ExampleGenerator(continuous=True): by default the n_local games a call takes plus two
+    per slot (one in play, one finished and waiting for the take); never fewer than the slots or than one call's games."""
+    cap = int(n_local) + 2 * int(n_slots) if capacity is None else int(capacity)
+    if cap < max(int(n_local), int(n_slots)):
+        raise ValueError("stream capacity %d is smaller than a call's %d games or the %d slots" % (cap, n_local, n_slots))
+    return cap
+
+
+def check_stream_request(n_local, capacity):
+    """A later call may ask for another number of games while it fits the ring."""
+    if int(n_local) > int(capacity):
+        raise ValueError("continuous=True: %d games per call exceed the stream's capacity of %d games (fixed by the first call)"
+                         % (n_local, capacity))
+    return int(n_local)
 
 
 def slot_groups(n_slots, k):

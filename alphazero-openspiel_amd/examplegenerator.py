@@ -12,8 +12,8 @@ import copy
 import numpy as np
 import torch
 
-from .engine import (EngineError, SelfPlayEngine, close_all, examples_from_export, make_evaluator, run_selfplay,
-                     run_selfplay_pools, slot_groups, unpack_device_export)
+from .engine import (EngineError, SelfPlayEngine, SelfPlayStream, check_stream_request, close_all, examples_from_export,
+                     make_evaluator, run_selfplay, run_selfplay_pools, slot_groups, stream_capacity, unpack_device_export)
 from .games import Game
 from . import distributed as azdist
 
@@ -70,6 +70,20 @@ class ExampleGenerator:
         self.overlap = int(kwargs.get("overlap", 1))  # slot groups ticking on their own HIP streams (engine.run_selfplay)
         self.last_progress = None
         self._generation = 0
+        # continuous=True: ONE engine in stream mode (engine.SelfPlayStream) lives across the calls; a call takes its games off
+        # the stream while the slots play on, instead of building an engine and playing a closed generation to its last game.
+        # stream_capacity: rows of the record ring (default: engine.stream_capacity - a call's games + 2 per slot)
+        self.continuous = bool(kwargs.get("continuous", False))
+        self.stream_capacity = kwargs.get("stream_capacity")
+        self._stream = self._stream_engine = self._stream_evaluator = None
+        self._stream_net = None  # the weights and buffers the stream's evaluator was built from
+        if self.continuous:
+            if self.n_pools > 1 or self.pool_devices is not None:
+                raise ValueError("continuous=True drives one engine per process: n_pools > 1 / pool_devices are not supported with it")
+            if self.overlap > 1:
+                raise ValueError("continuous=True ticks the engine on one stream: overlap > 1 is not supported with it")
+            if self.eval_backend != "fused":
+                raise ValueError("continuous=True needs eval_backend=\"fused\" (got %r)" % (self.eval_backend,))
 
     def _engine_kwargs(self):
         return {k: self.kwargs[k] for k in _ENGINE_KW if k in self.kwargs}
@@ -119,9 +133,75 @@ class ExampleGenerator:
         self._generation += 1
         return torch.cat(bufs), bufs[0].numel(), n_each, len(devices), dims
 
+    @staticmethod
+    def _net_tensors(net):
+        return list(net.parameters()) + list(net.buffers())
+
+    def _take_and_gather(self, n_games):
+        """continuous=True: this rank's int(n_games / world) games off its stream (built by the first call), then the same
+        exchange as _play_and_gather - one generation's payload.  self.net is read again at every call: broadcast from rank 0
+        when distributed, and when its weights or buffers differ from what the stream's evaluator was built from, a new
+        evaluator takes over (SelfPlayStream.set_evaluator: games in flight go on under the new net)."""
+        world, rank = azdist.world_size(), azdist.rank()
+        n_local = int(n_games) if world == 1 else int(n_games / world)
+        if n_local < 1:
+            raise ValueError("n_games=%d is fewer than the %d ranks" % (n_games, world))
+        if world > 1 or not azdist._single():
+            self.net = self.net.to(self.device)
+            azdist.broadcast_net(self.net, src=0)
+        now = self._net_tensors(self.net)
+        if self._stream is None:
+            n_slots = int(self.n_slots or min(n_local, 4096))
+            cap = stream_capacity(n_local, n_slots, self.stream_capacity)
+            engine = SelfPlayEngine(self.game, n_slots, max_games=cap, device=self.device, seed=self.seed + 7919 * rank,
+                                    **self._engine_kwargs())  # (the seed of a first closed generation: same games, id for id)
+            evaluator = None
+            try:
+                evaluator = make_evaluator(self.net, self.device, self.eval_backend, self.eval_precision, n_slots, self.eval_dtype)
+                self._stream = SelfPlayStream(engine, evaluator, use_graph=self.use_graph)
+            except Exception:
+                close_all(engine, evaluator, drain=True)
+                raise
+            self._stream_engine, self._stream_evaluator = engine, evaluator
+            self._stream_net = [t.detach().clone() for t in now]
+        else:
+            check_stream_request(n_local, self._stream_engine.sizes.max_games)
+            same = len(now) == len(self._stream_net) and all(
+                a.shape == b.shape and torch.equal(a.detach().to(b.device), b) for a, b in zip(now, self._stream_net))
+            if not same:
+                old = self._stream_evaluator
+                self._stream_evaluator = make_evaluator(self.net, self.device, self.eval_backend, self.eval_precision,
+                                                        self._stream_engine.G, self.eval_dtype)
+                self._stream.set_evaluator(self._stream_evaluator)
+                close_all(old)
+                self._stream_net = [t.detach().clone() for t in now]
+        engine = self._stream_engine
+        buf, _ = self._stream.take(n_local)
+        prog = engine.progress()
+        prog["ticks"] = self._stream.ticks
+        self.last_progress = prog
+        self._generation += 1
+        return azdist.all_gather_device_exports(buf), buf.numel(), n_local, world, (engine.max_plies, engine.max_children)
+
+    def close(self):
+        """Release the stream of continuous=True (drained first), its engine and its evaluator."""
+        stream, self._stream = self._stream, None
+        if stream is not None:
+            stream.close()
+            close_all(self._stream_engine, self._stream_evaluator)
+        self._stream_engine = self._stream_evaluator = self._stream_net = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
     def _play_and_gather(self, n_games):
         """This rank's shard of the generation on the HIP engine, then the generation-end exchange on DEVICE buffers.
         -> (gathered uint8 device tensor [world * nbytes], nbytes per rank, games per rank, world, (max_plies, max_children))"""
+        if self.continuous:
+            return self._take_and_gather(n_games)
         pool_devs = self._pool_device_list()
         if pool_devs is not None:
             return self._play_pools(n_games, pool_devs)

@@ -20,6 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from alphazero_openspiel_amd import arena, engine as E, games, replay  # noqa: E402
+from alphazero_openspiel_amd.examplegenerator import ExampleGenerator  # noqa: E402
 from alphazero_openspiel_amd.fusednet import FusedNet  # noqa: E402
 from alphazero_openspiel_amd.network import Net  # noqa: E402
 
@@ -37,6 +38,9 @@ def main():
     ap.add_argument("--precision", default="f32x", choices=["f32x", "f16"], help="fused-net arithmetic (f32x = fp32-grade)")
     ap.add_argument("--eval-every", type=int, default=0, help="run test_agent every N generations (0 = never)")
     ap.add_argument("--tests", type=int, default=200, help="n_tests (train.py:30)")
+    ap.add_argument("--continuous", action="store_true",
+                    help="self-play as ONE stream across the generations (ExampleGenerator(continuous=True)): the slots never wait "
+                         "for a generation's longest game, and games in flight go on under each updated net")
     a = ap.parse_args()
 
     dev = torch.device("cuda:0")
@@ -46,17 +50,29 @@ def main():
     n_buffer, n_buffer_max = 4 * a.games, 40 * a.games                     # train.py:38-41
     store = replay.DeviceReplay(game, max_games=n_buffer_max, device=dev)
     trainer = None
+    generator, before = None, {"moves": 0, "sims": 0}
+    if a.continuous:
+        generator = ExampleGenerator(net, a.game, dev, continuous=True, n_slots=min(a.games, 4096), n_playouts=a.playouts,
+                                     backup=a.backup, eval_precision=a.precision, seed=1)
     for gen in range(1, a.generations + 1):
         t0 = time.perf_counter()
         net.eval()
-        eng = E.SelfPlayEngine(game, min(a.games, 4096), n_playouts=a.playouts, backup=a.backup, max_games=a.games,
-                               device=dev, seed=gen)
-        prog = E.run_selfplay(eng, FusedNet(net, dev, max_boards=eng.G, precision=a.precision), a.games, use_graph=True)
+        if generator is not None:
+            generator.net = net                                            # read again at every call: the stream takes the new weights over
+            generator.generate_into(store, a.games)
+            total = generator.last_progress                                # (counters since the stream began, games in flight included)
+            prog = {k: total[k] - before[k] for k in before}
+            before = {k: total[k] for k in before}
+        else:
+            eng = E.SelfPlayEngine(game, min(a.games, 4096), n_playouts=a.playouts, backup=a.backup, max_games=a.games,
+                                   device=dev, seed=gen)
+            prog = E.run_selfplay(eng, FusedNet(net, dev, max_boards=eng.G, precision=a.precision), a.games, use_graph=True)
         t_play = time.perf_counter() - t0
+        if generator is None:
+            store.append_engine(eng)
+            eng.close()
         if gen % 2 == 0 and n_buffer < n_buffer_max:                       # Trainer.update_buffer_size
             n_buffer += a.games
-        store.append_engine(eng)
-        eng.close()
         store.set_capacity(n_buffer)
         n_unique = store.dedupe()
         net.train()
@@ -88,6 +104,8 @@ def main():
         if a.save:
             os.makedirs(a.save, exist_ok=True)
             torch.save(net.state_dict(), os.path.join(a.save, "%d.pth" % gen))
+    if generator is not None:
+        generator.close()
 
 
 if __name__ == "__main__":

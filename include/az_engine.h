@@ -288,6 +288,39 @@ int az_engine_export(az_engine *e, az_example_view *out, void *stream);
 int64_t az_engine_export_device_bytes(const az_engine *e);
 int az_engine_export_device(az_engine *e, void *dev_buf, int64_t bytes, void *stream);
 
+/*
+ * Stream mode: continuous self-play over a record store of FIXED size.  az_engine_reset starts a closed generation: once its
+ * last id is handed out the slots go idle one by one, and the records are indexed by game id into max_games rows.  A stream
+ * never ends: game ids are 0, 1, 2, ... (below 2^31: a slot keeps its id in an int32), id i uses RNG stream (seed, i) exactly
+ * as in a closed generation - a game depends on (seed, id, network) alone, so the games a stream delivers, in id order, ARE the
+ * closed generation of the same seed cut into pieces - and id i records into row i % max_games of the store, a ring.
+ *
+ * az_engine_stream_begin replaces az_engine_reset (slots 0..G-1 start ids 0..G-1).  Plain self-play engines only: an arena
+ * engine, manual_moves, AZ_RNG_INJECTED, a start prefix, a start-position table or max_games < n_slots return AZ_E_INVALID and
+ * az_last_error names the reason.  A later az_engine_reset returns the engine to a closed generation.
+ *
+ * An id is handed out only while id < read_pos + max_games, read_pos = the first id not yet taken: a row is never overwritten
+ * before its game has been taken.  A slot that finishes a game while no id may be handed out goes idle (az_progress.slots_idle
+ * counts them) and asks again at the start of each of its ticks, so it comes back by itself once a take has raised the limit;
+ * no id is skipped or handed out twice.  The engine is ticked with az_engine_advance on ONE stream, and the stream_* calls are
+ * given the same stream; az_engine_advance_slots, az_engine_compact_rows, az_engine_advance_rows, az_engine_export,
+ * az_engine_export_device and az_replay_append_engine return AZ_E_STATE in stream mode.  az_progress.games_done and
+ * az_engine_poll count every game finished since az_engine_stream_begin; fault flags work as in a closed generation.
+ *
+ * az_engine_stream_ready (synchronises `stream`): the number of consecutive finished games starting at read_pos, at most max_games.
+ * az_engine_stream_take_bytes(n): the size of a take of n games = az_engine_export_device_bytes of a generation of n games.
+ * az_engine_stream_take_device: packs games [read_pos, read_pos + n) into dev_buf (16-byte aligned) in exactly the layout of
+ *   az_engine_export_device for a generation of n games - az_replay_append_device and the generation-end all-gather consume it
+ *   unchanged; on-policy value targets are filled in on the device.  One kernel, asynchronous on `stream`: it gathers the rows
+ *   from the ring (wraparound included), frees them and raises the hand-out limit for the ticks that follow on the stream.
+ *   *first_game_out (may be NULL) receives read_pos, which then advances by n.  AZ_E_STATE if more games are asked for than
+ *   the last az_engine_stream_ready found (ask it first); AZ_E_INVALID if n < 1, n > max_games or the buffer is too small.
+ */
+int az_engine_stream_begin(az_engine *e, uint64_t seed, void *stream);
+int64_t az_engine_stream_ready(az_engine *e, void *stream);
+int64_t az_engine_stream_take_bytes(const az_engine *e, int64_t n_games);
+int az_engine_stream_take_device(az_engine *e, int64_t n_games, void *dev_buf, int64_t bytes, int64_t *first_game_out, void *stream);
+
 /* Every slot's root, packed into ONE caller-owned device buffer by one kernel: asynchronous on `stream`, no host
  * synchronisation, usable inside a captured graph - what az_engine_read_root / az_engine_read_slot give for one slot per
  * synchronising call.  The values are the node records' own (no arithmetic), so they equal az_engine_read_root's.
