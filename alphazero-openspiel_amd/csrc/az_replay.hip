@@ -245,7 +245,7 @@ __global__ void replay_append_kernel(AppendArgs a) {
     }
     a.z[dst] = zz;
     // pi: float(visit)/sum(visits) -> remove_illegal_actions (np.sum pairwise, divide) (mcts.py:161-162, alphazerobot.py:13-14)
-    int nc = a.nchild[src];
+    int nc = a.nchild[src] < a.maxc ? a.nchild[src] : a.maxc; // nv / act hold maxc <= 64 children
     double nv[64];
     int act[64];
     long long tot = 0;
@@ -374,10 +374,39 @@ extern "C" int az_replay_append_engine(az_replay *r, az_engine *e, void *stream)
     return append_common(r, a, lens, st);
 }
 
+// A game length the kernels may run with: rows [start_ply, start_ply + len) of a record array with max_plies rows per game.
+static bool game_len_ok(az_replay *r, int64_t g, int32_t len, int32_t max_plies, int32_t start_ply) {
+    if (len >= 0 && len <= max_plies - start_ply) return true;
+    r->err = "game_len[" + std::to_string(g) + "] = " + std::to_string(len) + " is outside [0, max_plies - start_ply = " +
+             std::to_string(max_plies - start_ply) + "]";
+    return false;
+}
+
 extern "C" int az_replay_append_host(az_replay *r, const az_example_view *v, int32_t start_ply, void *stream) {
-    if (!r || !v || v->n_games < 1 || v->max_children != r->maxc || v->max_plies > r->max_plies || start_ply < 0) {
-        if (r) r->err = "bad example view (max_children / max_plies must match the game)";
+    if (!r || !v || v->n_games < 1 || v->max_children != r->maxc || v->max_plies < 1 || v->max_plies > r->max_plies ||
+        start_ply < 0 || start_ply > v->max_plies) {
+        if (r) r->err = "bad example view (max_children / max_plies must match the game, 0 <= start_ply <= max_plies)";
         return AZ_E_INVALID;
+    }
+    // everything the kernels index with is checked here, before any copy or launch: the store stays as it was
+    for (int64_t g = 0; g < v->n_games; g++) {
+        int32_t len = v->game_len[g];
+        if (!game_len_ok(r, g, len, v->max_plies, start_ply)) return AZ_E_INVALID;
+        for (int32_t i = 0; i < len; i++) {
+            size_t src = (size_t)g * v->max_plies + start_ply + i;
+            int nc = v->n_children[src];
+            if (nc > v->max_children) {
+                r->err = "n_children = " + std::to_string(nc) + " at game " + std::to_string(g) + ", ply " + std::to_string(start_ply + i) +
+                         " is above max_children = " + std::to_string(v->max_children);
+                return AZ_E_INVALID;
+            }
+            for (int k = 0; k < nc; k++)
+                if (v->child_action[src * v->max_children + k] >= r->A) {
+                    r->err = "child_action at game " + std::to_string(g) + ", ply " + std::to_string(start_ply + i) +
+                             " is not an action of the game";
+                    return AZ_E_INVALID;
+                }
+        }
     }
     hipStream_t st = (hipStream_t)stream;
     RCHK(r, hipSetDevice(r->cfg.device));
@@ -414,7 +443,10 @@ extern "C" int az_replay_append_host(az_replay *r, const az_example_view *v, int
 }
 
 extern "C" int az_replay_append_device(az_replay *r, const void *dev_buf, int64_t n_games, int32_t start_ply, void *stream) {
-    if (!r || !dev_buf || n_games < 1 || start_ply < 0) return AZ_E_INVALID;
+    if (!r || !dev_buf || n_games < 1 || start_ply < 0 || start_ply > r->max_plies) {
+        if (r) r->err = "bad device export (null buffer, n_games < 1 or start_ply outside [0, max_plies])";
+        return AZ_E_INVALID;
+    }
     hipStream_t st = (hipStream_t)stream;
     RCHK(r, hipSetDevice(r->cfg.device));
     size_t ng = (size_t)n_games, mp = (size_t)r->max_plies, mc = (size_t)r->maxc;
@@ -440,6 +472,8 @@ extern "C" int az_replay_append_device(az_replay *r, const void *dev_buf, int64_
     std::vector<int32_t> lens(ng);
     RCHK(r, hipMemcpyAsync(lens.data(), a.game_len, ng * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     RCHK(r, hipStreamSynchronize(st));
+    for (size_t g = 0; g < ng; g++) // before any launch: a length outside the record rows would run the kernels off the arrays
+        if (!game_len_ok(r, (int64_t)g, lens[g], r->max_plies, start_ply)) return AZ_E_INVALID;
     return append_common(r, a, lens, st);
 }
 

@@ -66,12 +66,17 @@ int az_replay_set_capacity(az_replay *r, int64_t n_games);
  * Synchronises `stream`. */
 int az_replay_append_engine(az_replay *r, az_engine *e, void *stream);
 
-/* Append games given as host arrays in the layout of az_example_view (used by tests and by the multi-rank gather). */
+/* Append games given as host arrays in the layout of az_example_view (used by tests and by the multi-rank gather).
+ * The view is validated before anything is copied or launched: max_children must be the game's, every game_len must lie
+ * in [0, max_plies - start_ply], every n_children of a recorded ply must be <= max_children and every child action an
+ * action of the game; otherwise AZ_E_INVALID and the store is unchanged. */
 int az_replay_append_host(az_replay *r, const az_example_view *v, int32_t start_ply, void *stream);
 
 /* Append n_games games from a DEVICE buffer in the packed layout of az_engine_export_device (this rank's own export,
  * or one rank's section of the all-gathered buffer): engine -> RCCL all-gather -> replay store without touching the
- * host.  The board geometry (max_plies, max_children) is the store's.  Synchronises `stream`. */
+ * host.  The board geometry (max_plies, max_children) is the store's.  The game lengths are read back and checked as in
+ * az_replay_append_host before any kernel runs (AZ_E_INVALID, store unchanged); child counts are clamped to max_children
+ * on the device.  Synchronises `stream`. */
 int az_replay_append_device(az_replay *r, const void *dev_buf, int64_t n_games, int32_t start_ply, void *stream);
 
 /* Trainer.remove_duplicates over the whole (flattened) buffer.  Synchronises `stream`.  Records are grouped by the
@@ -83,7 +88,8 @@ int az_replay_dedupe(az_replay *r, void *stream);
 /* The sampling of net_step (train.py:108-120): gather `batch` examples of the de-duplicated list into
  * x [batch][4][H][W] float32, pi [batch][A] float32, z [batch] float32 (all device).  `indices` (device int64
  * [batch], values in [0, n_unique)) are the `np.random.randint(len(flattened_buffer), size=batch_size)` draw;
- * pass NULL to draw them on the device (Philox, stream (seed, call counter)).  An index outside [0, n_unique) fills its
+ * pass NULL to draw them on the device (one splitmix64 draw per row over (seed, call counter, row), scaled to
+ * [0, n_unique) by the high half of a 64x64-bit product).  An index outside [0, n_unique) fills its
  * row with NaN and raises AZ_REPLAY_FAULT_BAD_INDEX (asynchronous: reported by az_replay_stats_get). */
 int az_replay_sample(az_replay *r, const int64_t *indices, int32_t batch, uint64_t seed, float *x, float *pi,
                      float *z, void *stream);
