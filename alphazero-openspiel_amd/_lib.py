@@ -15,6 +15,9 @@ SELECT_PUCT, SELECT_UCT = 0, 1
 ACTION_NONE, ACTION_SEARCH_AGAIN = -1, -2
 ARENA_AGENTS = {None: 0, "zero": 1, "net": 2}
 OPPONENTS = {None: 0, "random": 1, "uct": 2, "external": 3}
+REPLAY_FAULTS = {1: "KEY_COLLISION", 2: "BAD_INDEX", 4: "ROOT_MISMATCH"}
+REFRESH_KEEP_Z, REFRESH_SOFT_Z, REFRESH_A0C = 0, 1, 2
+REFRESH_MODES = {None: REFRESH_KEEP_Z, "soft-Z": REFRESH_SOFT_Z, "A0C": REFRESH_A0C}  # the value targets a root alone gives
 
 
 class AzConfig(C.Structure):
@@ -101,6 +104,7 @@ PROTOTYPES = [
     ("az_engine_set_injected_rng", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64]),
     ("az_engine_set_start_prefix", C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int32]),
     ("az_engine_set_start_positions", C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.c_int64]),
+    ("az_engine_set_start_states_device", C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),
     ("az_engine_advance", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     ("az_engine_advance_slots", C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     ("az_engine_compact_rows", C.c_int, [_vp, C.POINTER(C.c_int32), _vp]),
@@ -143,6 +147,8 @@ PROTOTYPES = [
     ("az_replay_append_device", C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp]),
     ("az_replay_dedupe", C.c_int, [_vp, _vp]),
     ("az_replay_sample", C.c_int, [_vp, _vp, C.c_int32, C.c_uint64, _vp, _vp, _vp, _vp]),
+    ("az_replay_gather_states", C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp]),
+    ("az_replay_refresh_from_roots", C.c_int64, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp]),
     ("az_replay_stats_get", C.c_int, [_vp, C.POINTER(AzReplayStats)]),
     ("az_replay_read_unique", C.c_int64, [_vp, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_double),
                                           C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_uint64),

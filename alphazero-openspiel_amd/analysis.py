@@ -88,6 +88,7 @@ class Analyzer:
                                      use_dirichlet=use_dirichlet, manual_moves=True, max_games=int(n_slots),
                                      device=self.device, seed=self.seed, **kwargs)
         self.evaluator, self._owns_evaluator = None, False
+        self._eval_backend, self._eval_precision = eval_backend, eval_precision
         try:
             if policy_fn is not None:
                 self.evaluator, self._owns_evaluator = _make_evaluator(policy_fn, self.engine.device, eval_backend,
@@ -106,6 +107,14 @@ class Analyzer:
         close_all(self.evaluator if self._owns_evaluator else None, self.engine)
         self.evaluator = None
 
+    def set_evaluator(self, policy_fn):
+        """Search on with another network (or evaluator object): the engine stays, an evaluator this Analyzer made is closed."""
+        new, owned = _make_evaluator(policy_fn, self.engine.device, self._eval_backend, self._eval_precision, self.engine.G)
+        torch.cuda.synchronize(self.engine.device)
+        if self._owns_evaluator:
+            close_all(self.evaluator)
+        self.evaluator, self._owns_evaluator = new, owned
+
     def __enter__(self):
         return self
 
@@ -120,6 +129,17 @@ class Analyzer:
         self.engine.set_start_positions(histories)
         self.engine.reset(len(histories), self.seed if seed is None else seed)
         self.n = len(histories)
+        self.roots = None
+
+    def load_states_device(self, bb, ply, seed=None):
+        """The device twin of load: start a search from each of the n <= n_slots states (bb int64 [n, 2], ply int32 [n] device
+        tensors, e.g. DeviceReplay.gather_states); nothing goes through the host."""
+        n = int(ply.numel())
+        if not 1 <= n <= self.engine.G:
+            raise ValueError("%d positions for an engine of %d slots" % (n, self.engine.G))
+        self.engine.set_start_states_device(bb, ply)
+        self.engine.reset(n, self.seed if seed is None else seed)
+        self.n = n
         self.roots = None
 
     def update_root(self, actions, keep_subtree=True):
@@ -143,6 +163,14 @@ class Analyzer:
 
     def search(self, max_ticks=None):
         """Tick (advance + forward) until every slot has finished its search; -> engine.read_roots() of that moment."""
+        with torch.cuda.device(self.engine.device):
+            self.search_device(max_ticks)
+            self.roots = self.engine.read_roots(self.roots_buf)
+        return self.roots
+
+    def search_device(self, max_ticks=None):
+        """search() without the read-back: -> roots_buf, the packed root export of the finished searches (device).  The host
+        sees only the 16-byte header the loop polls."""
         if self.evaluator is None:
             raise EngineError("Analyzer has no evaluator: pass the network, or set .evaluator")
         e = self.engine
@@ -164,8 +192,8 @@ class Analyzer:
                     raise EngineError("analysis did not finish within %d ticks: %r" % (limit, e.progress()))
                 drv.run(self.check_every)
             self.ticks += drv.ticks
-            self.roots = e.read_roots(self.roots_buf)
-        return self.roots
+        self.roots = None
+        return self.roots_buf
 
     def results(self):
         """The loaded positions' roots as dense arrays: visits [n, A] int64, q / priors [n, A] float64 (zero where there is

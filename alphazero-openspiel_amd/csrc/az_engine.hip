@@ -1501,6 +1501,7 @@ extern "C" int az_engine_destroy(az_engine *e) {
     if (e->d_us) (void)hipFree(e->d_us);
     if (e->d_actions) (void)hipFree(e->d_actions);
     if (e->d_starts) (void)hipFree(e->d_starts);
+    if (e->d_start_check) (void)hipFree(e->d_start_check);
     delete e;
     return AZ_OK;
 }
@@ -1549,7 +1550,9 @@ extern "C" int az_engine_create(const az_config *cfg, az_engine **out) {
                        "spare_pools >= 0";
         return AZ_E_INVALID;
     }
-    if (!c.use_dirichlet && c.n_playouts < 2 && c.arena_agent != AZ_ARENA_NET) {
+    // (a manual_moves engine never forms pi itself: its caller reads the root, and the replay store's refresh gives a root
+    // without a visited child the uniform 1 / n_children of remove_illegal_actions, alphazerobot.py:15-17)
+    if (!c.use_dirichlet && c.n_playouts < 2 && c.arena_agent != AZ_ARENA_NET && !c.manual_moves) {
         g_create_err = "n_playouts must be >= 2 without root Dirichlet expansion (mcts.py:162 divides by zero)";
         return AZ_E_INVALID;
     }
@@ -1957,6 +1960,27 @@ extern "C" int az_engine_set_start_prefix(az_engine *e, const int32_t *actions, 
     return AZ_OK;
 }
 
+// The table behind Params::starts holds at least n_games states (a table that has to grow is out of force until it is filled).
+static int starts_reserve(az_engine *e, int64_t n_games) {
+    if (n_games <= e->starts_cap) return AZ_OK;
+    if (e->d_starts) (void)hipFree(e->d_starts);
+    e->d_starts = nullptr;
+    e->starts_cap = 0;
+    e->p.starts = nullptr;
+    e->starts_n = 0;
+    HIPCHK(e, hipMalloc((void **)&e->d_starts, (size_t)n_games * sizeof(AzState)));
+    e->starts_cap = n_games;
+    return AZ_OK;
+}
+// ... and its first n_games entries are the start positions from now on.
+static void starts_in_force(az_engine *e, int64_t n_games) {
+    if (e->cfg.game == AZ_GAME_CONNECT_FOUR) az_init_state<AZG_CONNECT_FOUR>(e->p.start, e->p.geom); // supersedes a single prefix
+    else az_init_state<AZG_BREAKTHROUGH>(e->p.start, e->p.geom);
+    e->p.starts = e->d_starts;
+    e->starts_n = n_games;
+    e->reset_done = false; // caller must reset again so that slots pick the new starts up
+}
+
 extern "C" int az_engine_set_start_positions(az_engine *e, const int32_t *actions, const int32_t *lengths, int64_t stride,
                                              int64_t n_games) {
     if (!e) return AZ_E_INVALID;
@@ -1986,21 +2010,77 @@ extern "C" int az_engine_set_start_positions(az_engine *e, const int32_t *action
     }
     HIPCHK(e, hipSetDevice(e->cfg.device));
     HIPCHK(e, hipDeviceSynchronize()); // a reset of the previous chunk may still be reading the table
-    if (n_games > e->starts_cap) {
-        if (e->d_starts) (void)hipFree(e->d_starts);
-        e->d_starts = nullptr;
-        e->starts_cap = 0;
-        e->p.starts = nullptr;
-        e->starts_n = 0;
-        HIPCHK(e, hipMalloc((void **)&e->d_starts, (size_t)n_games * sizeof(AzState)));
-        e->starts_cap = n_games;
-    }
+    int rc = starts_reserve(e, n_games);
+    if (rc != AZ_OK) return rc;
     HIPCHK(e, hipMemcpy(e->d_starts, tab.data(), (size_t)n_games * sizeof(AzState), hipMemcpyHostToDevice));
-    if (e->cfg.game == AZ_GAME_CONNECT_FOUR) az_init_state<AZG_CONNECT_FOUR>(e->p.start, e->p.geom); // supersedes a single prefix
-    else az_init_state<AZG_BREAKTHROUGH>(e->p.start, e->p.geom);
-    e->p.starts = e->d_starts;
-    e->starts_n = n_games;
-    e->reset_done = false; // caller must reset again so that slots pick the new starts up
+    starts_in_force(e, n_games);
+    return AZ_OK;
+}
+
+// The device form: the states come as bitboards and plies in device memory (az_replay_gather_states writes them).  One thread
+// per state runs az_check_state; the lowest offending index and its rule reach the host as one word, (index << 8) | rule, through
+// a 64-bit atomicMin, and only a clean pass is followed by the kernel that fills the table.
+#define START_CHECK_CLEAN ~0ull
+template <int GAME>
+__global__ void az_check_start_states_kernel(AzGeom geom, int max_plies, const uint64_t *bb, const int32_t *ply, long long n,
+                                             unsigned long long *result) {
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    AzState s;
+    s.bb0 = bb[2 * i];
+    s.bb1 = bb[2 * i + 1];
+    s.ply = ply[i];
+    int rule = az_check_state<GAME>(s, geom, max_plies);
+    if (rule != AZ_STATE_OK) atomicMin(result, ((unsigned long long)i << 8) | (unsigned long long)rule);
+}
+__global__ void az_fill_start_states_kernel(const uint64_t *bb, const int32_t *ply, long long n, AzState *tab) {
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    AzState s;
+    s.bb0 = bb[2 * i];
+    s.bb1 = bb[2 * i + 1];
+    s.ply = ply[i];
+    tab[i] = s;
+}
+
+extern "C" int az_engine_set_start_states_device(az_engine *e, const uint64_t *bb_dev, const int32_t *ply_dev, int64_t n_games,
+                                                 void *stream) {
+    if (!e) return AZ_E_INVALID;
+    if (!e->cfg.manual_moves) {
+        e->err = "az_engine_set_start_states_device needs an engine created with manual_moves = 1: self-play and arena engines keep "
+                 "ONE start ply for the record offset, the value targets, the replay append and the side assignment";
+        return AZ_E_INVALID;
+    }
+    if (!bb_dev || !ply_dev || n_games < 1 || n_games > e->cfg.max_games) {
+        e->err = "az_engine_set_start_states_device: n_games must be in [1, max_games], bb_dev and ply_dev non-null";
+        return AZ_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, hipDeviceSynchronize()); // the states are written, and a reset of the previous chunk has read the table
+    if (!e->d_start_check) HIPCHK(e, hipMalloc((void **)&e->d_start_check, sizeof(unsigned long long)));
+    unsigned long long res = START_CHECK_CLEAN;
+    HIPCHK(e, hipMemcpyAsync(e->d_start_check, &res, sizeof res, hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)((n_games + 255) / 256)), block(256);
+    if (e->cfg.game == AZ_GAME_CONNECT_FOUR)
+        hipLaunchKernelGGL(az_check_start_states_kernel<AZG_CONNECT_FOUR>, grid, block, 0, st, e->p.geom, e->p.max_plies, bb_dev, ply_dev,
+                           (long long)n_games, e->d_start_check);
+    else
+        hipLaunchKernelGGL(az_check_start_states_kernel<AZG_BREAKTHROUGH>, grid, block, 0, st, e->p.geom, e->p.max_plies, bb_dev, ply_dev,
+                           (long long)n_games, e->d_start_check);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(&res, e->d_start_check, sizeof res, hipMemcpyDeviceToHost, st));
+    HIPCHK(e, hipStreamSynchronize(st));
+    if (res != START_CHECK_CLEAN) {
+        e->err = "az_engine_set_start_states_device: game " + std::to_string(res >> 8) + ": " + az_state_rule_name((int)(res & 0xFF));
+        return AZ_E_INVALID;
+    }
+    int rc = starts_reserve(e, n_games);
+    if (rc != AZ_OK) return rc;
+    hipLaunchKernelGGL(az_fill_start_states_kernel, grid, block, 0, st, bb_dev, ply_dev, (long long)n_games, e->d_starts);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipStreamSynchronize(st));
+    starts_in_force(e, n_games);
     return AZ_OK;
 }
 
@@ -2390,20 +2470,6 @@ extern "C" int az_engine_export_device(az_engine *e, void *dev_buf, int64_t byte
 // children are one contiguous run of 32-byte nodes, lane i takes child i (two 16-byte loads per lane, a wave reads the run end
 // to end) and the four child arrays are written lane-contiguously.  Rows beyond n_children are written too (action -1, zeros),
 // so the buffer's contents depend on the trees alone.  Runs once per search (or every few ticks), not per tick.
-#define AZ_ROOTS_ARRAYS 12
-static void roots_offsets(size_t G, size_t mc, size_t off[AZ_ROOTS_ARRAYS + 1]) {
-    const size_t sizes[AZ_ROOTS_ARRAYS] = {16, G * 4, G * 4, G * 4, G * 4, G * 4, G * 4, G * 8, G * mc * 4, G * mc * 4, G * mc * 8, G * mc * 8};
-    off[0] = 0;
-    for (int i = 0; i < AZ_ROOTS_ARRAYS; i++) off[i + 1] = off[i] + ((sizes[i] + 15) & ~(size_t)15);
-}
-struct RootsOut {
-    int *header, *game_id, *phase, *ply, *sims_done, *n_children;
-    uint32_t *root_n;
-    double *root_q;
-    int *child_action;
-    uint32_t *child_n;
-    double *child_q, *child_p;
-};
 
 __global__ __launch_bounds__(256) void az_export_roots_kernel(Params p, RootsOut o) {
     const int lane = threadIdx.x & 63;
@@ -2497,20 +2563,7 @@ extern "C" int az_engine_export_roots_device(az_engine *e, void *dev_buf, int64_
     }
     HIPCHK(e, hipSetDevice(e->cfg.device));
     hipStream_t st = (hipStream_t)stream;
-    char *b = (char *)dev_buf;
-    RootsOut o;
-    o.header = (int *)(b + off[0]);
-    o.game_id = (int *)(b + off[1]);
-    o.phase = (int *)(b + off[2]);
-    o.ply = (int *)(b + off[3]);
-    o.sims_done = (int *)(b + off[4]);
-    o.n_children = (int *)(b + off[5]);
-    o.root_n = (uint32_t *)(b + off[6]);
-    o.root_q = (double *)(b + off[7]);
-    o.child_action = (int *)(b + off[8]);
-    o.child_n = (uint32_t *)(b + off[9]);
-    o.child_q = (double *)(b + off[10]);
-    o.child_p = (double *)(b + off[11]);
+    RootsOut o = roots_arrays(dev_buf, (size_t)e->p.G, (size_t)e->p.maxc);
     hipLaunchKernelGGL(az_export_roots_kernel, dim3((e->p.G + 3) / 4), dim3(256), 0, st, e->p, o);
     HIPCHK(e, hipGetLastError());
     hipLaunchKernelGGL(az_roots_header_kernel, dim3(1), dim3(1024), 0, st, e->p, o);

@@ -98,7 +98,8 @@ struct Params {
     uint8_t *rec_nchild;
     uint32_t *rec_child_visits;
     double *rec_value;
-    // start position per GAME ID (az_engine_set_start_positions; manual_moves engines only): null = every game starts from `start`
+    // start position per GAME ID (az_engine_set_start_positions / az_engine_set_start_states_device; manual_moves engines only):
+    // null = every game starts from `start`
     const AzState *starts;
 };
 
@@ -117,6 +118,7 @@ struct az_engine {
     int64_t inj_games = 0;
     AzState *d_starts = nullptr; // the table behind p.starts (kept across az_engine_set_start_positions calls)
     int64_t starts_cap = 0, starts_n = 0;
+    unsigned long long *d_start_check = nullptr; // result record of az_engine_set_start_states_device's validity pass
     bool rows_mapped = false; // az_engine_compact_rows has been called since the last reset
     int rows_live = 0;
     bool streaming = false;   // az_engine_stream_begin since the last az_engine_reset
@@ -135,3 +137,38 @@ struct az_engine {
     std::vector<double> h_value;
 };
 
+// The packed root export (layout: include/az_engine.h, az_engine_export_roots_device): written by az_engine.hip, read by the
+// replay store's az_replay_refresh_from_roots.
+#define AZ_ROOTS_ARRAYS 12
+static inline void roots_offsets(size_t G, size_t mc, size_t off[AZ_ROOTS_ARRAYS + 1]) {
+    const size_t sizes[AZ_ROOTS_ARRAYS] = {16, G * 4, G * 4, G * 4, G * 4, G * 4, G * 4, G * 8, G * mc * 4, G * mc * 4, G * mc * 8, G * mc * 8};
+    off[0] = 0;
+    for (int i = 0; i < AZ_ROOTS_ARRAYS; i++) off[i + 1] = off[i] + ((sizes[i] + 15) & ~(size_t)15);
+}
+struct RootsOut {
+    int *header, *game_id, *phase, *ply, *sims_done, *n_children;
+    uint32_t *root_n;
+    double *root_q;
+    int *child_action;
+    uint32_t *child_n;
+    double *child_q, *child_p;
+};
+static inline RootsOut roots_arrays(void *dev_buf, size_t G, size_t mc) {
+    size_t off[AZ_ROOTS_ARRAYS + 1];
+    roots_offsets(G, mc, off);
+    char *b = (char *)dev_buf;
+    RootsOut o;
+    o.header = (int *)(b + off[0]);
+    o.game_id = (int *)(b + off[1]);
+    o.phase = (int *)(b + off[2]);
+    o.ply = (int *)(b + off[3]);
+    o.sims_done = (int *)(b + off[4]);
+    o.n_children = (int *)(b + off[5]);
+    o.root_n = (uint32_t *)(b + off[6]);
+    o.root_q = (double *)(b + off[7]);
+    o.child_action = (int *)(b + off[8]);
+    o.child_n = (uint32_t *)(b + off[9]);
+    o.child_q = (double *)(b + off[10]);
+    o.child_p = (double *)(b + off[11]);
+    return o;
+}

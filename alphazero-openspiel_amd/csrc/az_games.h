@@ -203,6 +203,49 @@ template <int GAME> AZ_HD int az_nth_legal(const AzState &s, const AzGeom &g, in
     return -1;
 }
 
+// Can a search start from (bb0, bb1, ply)?  0 = yes; otherwise the first rule, in this order, that the state breaks.  The
+// dynamics above assume every one of them (the sentinel bits of az_c4_has_four, shifts that stay on the board, a side to move
+// that can move), so a state that did not come from az_apply is checked with this before it reaches a search.
+enum {
+    AZ_STATE_OK = 0,
+    AZ_STATE_BAD_PLY,    // ply outside [0, max_plies)
+    AZ_STATE_OVERLAP,    // a cell held by both sides
+    AZ_STATE_OFF_BOARD,  // a bit that is no cell
+    AZ_STATE_SENTINEL,   // connect_four: bit 6 of a column
+    AZ_STATE_FLOATING,   // connect_four: a stone above an empty cell
+    AZ_STATE_COUNT,      // connect_four: stone counts that do not follow from ply
+    AZ_STATE_EMPTY_SIDE, // breakthrough: a side without a piece
+    AZ_STATE_GOAL_ROW,   // breakthrough: a piece on the row that wins the game for its side
+    AZ_STATE_TERMINAL,   // the game is over
+    AZ_STATE_NO_MOVE,    // the side to move has no legal move
+    AZ_STATE_N_RULES
+};
+static inline const char *az_state_rule_name(int rule) {
+    static const char *const names[AZ_STATE_N_RULES] = {
+        "ok", "ply outside [0, max_plies)", "a cell held by both sides", "a bit outside the board", "a sentinel bit (bit 6 of a column) is set",
+        "a stone above an empty cell", "stone counts do not match ply", "a side has no piece", "a piece on its goal row",
+        "the position is terminal", "the side to move has no legal move"};
+    return rule >= 0 && rule < AZ_STATE_N_RULES ? names[rule] : "?";
+}
+template <int GAME> AZ_HD int az_check_state(const AzState &s, const AzGeom &g, int max_plies) {
+    if (s.ply < 0 || s.ply >= max_plies) return AZ_STATE_BAD_PLY;
+    if (s.bb0 & s.bb1) return AZ_STATE_OVERLAP;
+    const uint64_t occ = s.bb0 | s.bb1;
+    if (GAME == AZG_CONNECT_FOUR) {
+        const uint64_t bottom = 0x0000040810204081ull; // row 0 of the 7 columns (bits 0, 7, ..., 42)
+        if (occ >> 49) return AZ_STATE_OFF_BOARD;
+        if (occ & (bottom << 6)) return AZ_STATE_SENTINEL;
+        if (occ & ~bottom & ~(occ << 1)) return AZ_STATE_FLOATING;
+        if (az_popc64(s.bb0) != (s.ply + 1) / 2 || az_popc64(s.bb1) != s.ply / 2) return AZ_STATE_COUNT;
+        if (az_c4_has_four(s.bb0) || az_c4_has_four(s.bb1)) return AZ_STATE_TERMINAL;
+    } else {
+        if (occ & ~g.board_mask) return AZ_STATE_OFF_BOARD;
+        if (!s.bb0 || !s.bb1) return AZ_STATE_EMPTY_SIDE;
+        if ((s.bb0 & g.row_last) || (s.bb1 & g.row_first)) return AZ_STATE_GOAL_ROW;
+    }
+    return az_count_legal<GAME>(s, g) > 0 ? AZ_STATE_OK : AZ_STATE_NO_MOVE;
+}
+
 // Observation element idx of state_to_board's (C+1,H,W) tensor (network.py:9-18), C = 3.
 //   connect_four planes: 0 empty, 1 player-1 stones, 2 player-0 stones, 3 current player
 //   breakthrough planes: 0 black,  1 white,          2 empty,           3 current player

@@ -32,12 +32,19 @@ struct az_replay {
     std::deque<int32_t> game_len;     // FIFO of games (lengths), oldest first
     int64_t capacity_games = 0, dropped = 0, n_unique = 0;
     uint64_t sample_calls = 0;
+    int64_t epoch = 0, gather_epoch = -1; // epoch: appends, dedupes and capacity changes so far; ... at the last az_replay_gather_states
     // device
     uint64_t *key = nullptr, *key2 = nullptr, *bb0 = nullptr, *bb1 = nullptr; // key2: an independent second hash of the history
     unsigned int *faults = nullptr;                                             // AZ_REPLAY_FAULT_* bits
     int32_t *ply = nullptr;
     double *z = nullptr, *pi = nullptr;
     int64_t *unique = nullptr; // [n_unique] logical indices of the first occurrences, ascending
+    // az_replay_refresh_from_roots: claim[phys] = the lowest slot that refreshes the example in the running call (REFRESH_FREE
+    // between calls), sel[slot] = the example a slot refreshes (-1: none), refreshed = the call's count
+    unsigned int *claim = nullptr;
+    long long *sel = nullptr;
+    int64_t sel_cap = 0;
+    unsigned long long *refreshed = nullptr;
     // staging for append
     void *stage = nullptr;
     size_t stage_bytes = 0;
@@ -67,6 +74,9 @@ extern "C" int az_replay_destroy(az_replay *r) {
     (void)hipFree(r->z);
     (void)hipFree(r->pi);
     (void)hipFree(r->unique);
+    (void)hipFree(r->claim);
+    (void)hipFree(r->sel);
+    (void)hipFree(r->refreshed);
     (void)hipFree(r->stage);
     delete r;
     return AZ_OK;
@@ -129,7 +139,8 @@ extern "C" int az_replay_create(const az_replay_config *cfg, az_replay **out) {
               hipMalloc((void **)&r->bb0, n * 8) == hipSuccess &&
               hipMalloc((void **)&r->bb1, n * 8) == hipSuccess && hipMalloc((void **)&r->ply, n * 4) == hipSuccess &&
               hipMalloc((void **)&r->z, n * 8) == hipSuccess && hipMalloc((void **)&r->pi, n * 8 * (size_t)r->A) == hipSuccess &&
-              hipMalloc((void **)&r->unique, n * 8) == hipSuccess;
+              hipMalloc((void **)&r->unique, n * 8) == hipSuccess && hipMalloc((void **)&r->claim, n * 4) == hipSuccess &&
+              hipMemset(r->claim, 0xFF, n * 4) == hipSuccess && hipMalloc((void **)&r->refreshed, 8) == hipSuccess;
     if (!ok) {
         g_replay_err = "hipMalloc of the replay store failed";
         az_replay_destroy(r);
@@ -142,6 +153,7 @@ extern "C" int az_replay_create(const az_replay_config *cfg, az_replay **out) {
 extern "C" int az_replay_set_capacity(az_replay *r, int64_t n_games) {
     if (!r || n_games < 1 || n_games > r->cfg.max_games) return AZ_E_INVALID;
     r->capacity_games = n_games;
+    r->epoch++;
     return AZ_OK;
 }
 
@@ -162,6 +174,7 @@ extern "C" int az_replay_stats_get(az_replay *r, az_replay_stats *out) {
         r->err = "device fault flags set:";
         if (f & AZ_REPLAY_FAULT_KEY_COLLISION) r->err += " KEY_COLLISION";
         if (f & AZ_REPLAY_FAULT_BAD_INDEX) r->err += " BAD_INDEX";
+        if (f & AZ_REPLAY_FAULT_ROOT_MISMATCH) r->err += " ROOT_MISMATCH";
         return AZ_E_DEVICE;
     }
     return AZ_OK;
@@ -225,6 +238,24 @@ __device__ double np_sum_sparse_serial(const PwPlan &pw, const double *v, const 
     return stack[0];
 }
 
+// The dense pi [A] of one example from its root's child visit counts (children in ascending-action order, nc <= 64 = the
+// capacity of nv / act), one thread: float(visit)/sum(visits) -> remove_illegal_actions (np.sum pairwise, divide; 1/nc when no
+// child has a visit) (mcts.py:161-162, alphazerobot.py:13-14).  The append kernel and the refresh kernel both store what THIS gives.
+template <typename ActT>
+__device__ void pi_from_root_visits(const PwPlan &pw, int A, int nc, const uint32_t *visits, const ActT *actions, double *out) {
+    double nv[64];
+    int act[64];
+    long long tot = 0;
+    for (int k = 0; k < nc; k++) tot += visits[k];
+    for (int k = 0; k < nc; k++) {
+        nv[k] = (double)visits[k] / (double)tot;
+        act[k] = actions[k];
+    }
+    double s = np_sum_sparse_serial(pw, nv, act, nc);
+    for (int x = 0; x < A; x++) out[x] = 0.0;
+    for (int k = 0; k < nc; k++) out[act[k]] = s > 1e-6 ? nv[k] / s : 1.0 / (double)nc;
+}
+
 // one thread per (game, ply) example: state, z, dense pi from the recorded root visits
 __global__ void replay_append_kernel(AppendArgs a) {
     long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -244,20 +275,8 @@ __global__ void replay_append_kernel(AppendArgs a) {
         if ((a.start_ply + i) & 1) zz = -zz;
     }
     a.z[dst] = zz;
-    // pi: float(visit)/sum(visits) -> remove_illegal_actions (np.sum pairwise, divide) (mcts.py:161-162, alphazerobot.py:13-14)
-    int nc = a.nchild[src] < a.maxc ? a.nchild[src] : a.maxc; // nv / act hold maxc <= 64 children
-    double nv[64];
-    int act[64];
-    long long tot = 0;
-    for (int k = 0; k < nc; k++) tot += a.child_visits[src * a.maxc + k];
-    for (int k = 0; k < nc; k++) {
-        nv[k] = (double)a.child_visits[src * a.maxc + k] / (double)tot;
-        act[k] = a.child_action[src * a.maxc + k];
-    }
-    double s = np_sum_sparse_serial(a.pw, nv, act, nc);
-    double *out = a.pi + (size_t)dst * a.A;
-    for (int x = 0; x < a.A; x++) out[x] = 0.0;
-    for (int k = 0; k < nc; k++) out[act[k]] = s > 1e-6 ? nv[k] / s : 1.0 / (double)nc;
+    int nc = a.nchild[src] < a.maxc ? a.nchild[src] : a.maxc;
+    pi_from_root_visits(a.pw, a.A, nc, a.child_visits + src * a.maxc, a.child_action + src * a.maxc, a.pi + (size_t)dst * a.A);
 }
 
 // one thread per game: key chain over its moves (key of ply i = hash of the first i actions)
@@ -296,6 +315,7 @@ static int append_common(az_replay *r, AppendArgs &a, const std::vector<int32_t>
         r->err = "one generation holds more examples than max_examples";
         return AZ_E_INVALID;
     }
+    r->epoch++; // from here on the indices of an earlier az_replay_gather_states may name other records
     // make room in the example ring first (evict oldest games if the ring would overflow)
     while (r->n + add > r->cap && !r->game_len.empty()) {
         r->head = (r->head + r->game_len.front()) % r->cap;
@@ -535,6 +555,7 @@ extern "C" int az_replay_dedupe(az_replay *r, void *stream) {
     RCHK(r, hipSetDevice(r->cfg.device));
     long long n = r->n;
     r->n_unique = 0;
+    r->epoch++;
     // the collision flag describes THIS pass (an earlier one may have tripped on examples that have since been evicted)
     hipLaunchKernelGGL(clear_fault_kernel, dim3(1), dim3(1), 0, st, r->faults, AZ_REPLAY_FAULT_KEY_COLLISION);
     if (n == 0) return AZ_OK;
@@ -685,6 +706,180 @@ extern "C" int az_replay_sample(az_replay *r, const int64_t *indices, int32_t ba
     hipLaunchKernelGGL(replay_sample_kernel, dim3(batch), dim3(128), 0, (hipStream_t)stream, a);
     RCHK(r, hipGetLastError());
     return AZ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ reanalyse
+// Stored positions -> a search (az_engine_set_start_states_device) -> refreshed targets, device to device.
+__global__ void replay_gather_states_kernel(const int64_t *indices, long long n, long long n_unique, const int64_t *unique, long long head,
+                                            long long cap, const uint64_t *bb0, const uint64_t *bb1, const int32_t *ply, uint64_t *bb_out,
+                                            int32_t *ply_out, unsigned int *faults) {
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    long long u = indices[i];
+    if (u < 0 || u >= n_unique) { // as az_replay_sample: a fault flag, and a state no search accepts
+        atomicOr(faults, AZ_REPLAY_FAULT_BAD_INDEX);
+        bb_out[2 * i] = bb_out[2 * i + 1] = 0;
+        ply_out[i] = -1;
+        return;
+    }
+    long long phys = (head + unique[u]) % cap;
+    bb_out[2 * i] = bb0[phys];
+    bb_out[2 * i + 1] = bb1[phys];
+    ply_out[i] = ply[phys];
+}
+
+extern "C" int az_replay_gather_states(az_replay *r, const int64_t *indices, int64_t n, uint64_t *bb_out, int32_t *ply_out, void *stream) {
+    if (!r || !indices || !bb_out || !ply_out || n < 1) return AZ_E_INVALID;
+    if (r->n_unique < 1) {
+        r->err = "az_replay_gather_states before az_replay_dedupe (or the buffer is empty)";
+        return AZ_E_STATE;
+    }
+    RCHK(r, hipSetDevice(r->cfg.device));
+    hipLaunchKernelGGL(replay_gather_states_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, indices,
+                       (long long)n, (long long)r->n_unique, r->unique, (long long)r->head, (long long)r->cap, r->bb0, r->bb1, r->ply, bb_out,
+                       ply_out, r->faults);
+    RCHK(r, hipGetLastError());
+    r->gather_epoch = r->epoch;
+    return AZ_OK;
+}
+
+#define REFRESH_FREE 0xFFFFFFFFu
+struct RefreshArgs {
+    RootsOut roots; // (read only here)
+    int G, mc, A, value_mode;
+    long long n, n_unique, head, cap;
+    const int64_t *indices, *unique;
+    PwPlan pw;
+    const int32_t *ply;
+    double *z, *pi;
+    unsigned int *claim, *faults;
+    long long *sel;
+    unsigned long long *refreshed;
+};
+// One thread per slot of the root export, three passes on one stream.  claim: which example the slot refreshes (sel[g], -1 =
+// none: not a finished search of this call, a bad index, another ply, a child that is no action of the game), and the lowest
+// such slot per example wins it, so duplicate indices store ONE of their results whole.
+__global__ void replay_refresh_claim_kernel(RefreshArgs a) {
+    int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= a.G) return;
+    a.sel[g] = -1;
+    int gid = a.roots.game_id[g];
+    if (a.roots.phase[g] != PH_SEARCH_DONE || gid < 0 || gid >= a.n) return;
+    long long u = a.indices[gid];
+    if (u < 0 || u >= a.n_unique) {
+        atomicOr(a.faults, AZ_REPLAY_FAULT_BAD_INDEX);
+        return;
+    }
+    long long phys = (a.head + a.unique[u]) % a.cap;
+    int nc = a.roots.n_children[g];
+    bool ok = a.roots.ply[g] == a.ply[phys] && nc >= 0 && nc <= a.mc;
+    for (int k = 0; ok && k < nc; k++) {
+        int act = a.roots.child_action[(size_t)g * a.mc + k];
+        ok = act >= 0 && act < a.A;
+    }
+    if (!ok) {
+        atomicOr(a.faults, AZ_REPLAY_FAULT_ROOT_MISMATCH);
+        return;
+    }
+    a.sel[g] = phys;
+    atomicMin(a.claim + phys, (unsigned int)g);
+}
+__global__ void replay_refresh_write_kernel(RefreshArgs a) {
+    int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= a.G) return;
+    long long phys = a.sel[g];
+    if (phys < 0 || a.claim[phys] != (unsigned int)g) return;
+    const size_t row = (size_t)g * a.mc;
+    int nc = a.roots.n_children[g];
+    pi_from_root_visits(a.pw, a.A, nc, a.roots.child_n + row, a.roots.child_action + row, a.pi + (size_t)phys * a.A);
+    if (a.value_mode == AZ_REFRESH_SOFT_Z) { // game_utils.py:172-174
+        a.z[phys] = -a.roots.root_q[g];
+    } else if (a.value_mode == AZ_REFRESH_A0C) { // game_utils.py:177-179; a root without children keeps its z
+        double best = 0.0;
+        for (int k = 0; k < nc; k++) {
+            double v = a.roots.child_n[row + k] > 0 ? a.roots.child_q[row + k] : -99.0;
+            if (k == 0 || v > best) best = v;
+        }
+        if (nc > 0) a.z[phys] = best;
+    }
+    atomicAdd(a.refreshed, 1ull);
+}
+__global__ void replay_refresh_release_kernel(RefreshArgs a) {
+    int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < a.G && a.sel[g] >= 0) a.claim[a.sel[g]] = REFRESH_FREE;
+}
+
+extern "C" int64_t az_replay_refresh_from_roots(az_replay *r, const int64_t *indices, int64_t n, const void *roots, int64_t roots_bytes,
+                                                int32_t value_mode, void *stream) {
+    if (!r) return AZ_E_INVALID;
+    if (!indices || !roots || n < 1 || ((uintptr_t)roots & 15) != 0 ||
+        (value_mode != AZ_REFRESH_KEEP_Z && value_mode != AZ_REFRESH_SOFT_Z && value_mode != AZ_REFRESH_A0C)) {
+        r->err = "az_replay_refresh_from_roots: null / unaligned argument, n < 1 or an unknown value_mode";
+        return AZ_E_INVALID;
+    }
+    if (roots_bytes < 16) {
+        r->err = "az_replay_refresh_from_roots: roots_bytes does not hold the header";
+        return AZ_E_INVALID;
+    }
+    if (r->n_unique < 1 || r->gather_epoch != r->epoch) {
+        r->err = "az_replay_refresh_from_roots: the store has changed (append, dedupe or capacity) since az_replay_gather_states - the "
+                 "indices may name other records";
+        return AZ_E_STATE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    RCHK(r, hipSetDevice(r->cfg.device));
+    int32_t hdr[4] = {0, 0, 0, 0};
+    RCHK(r, hipMemcpyAsync(hdr, roots, 16, hipMemcpyDeviceToHost, st));
+    RCHK(r, hipStreamSynchronize(st));
+    size_t off[AZ_ROOTS_ARRAYS + 1];
+    if (hdr[1] >= 1 && hdr[2] == r->maxc) roots_offsets((size_t)hdr[1], (size_t)hdr[2], off);
+    if (hdr[1] < 1 || hdr[2] != r->maxc || (int64_t)off[AZ_ROOTS_ARRAYS] > roots_bytes) {
+        r->err = "az_replay_refresh_from_roots: the header says " + std::to_string(hdr[1]) + " slots x " + std::to_string(hdr[2]) +
+                 " children: not a root export of this game that fits roots_bytes = " + std::to_string(roots_bytes);
+        return AZ_E_INVALID;
+    }
+    if (hdr[3] != 0) {
+        r->err = "az_replay_refresh_from_roots: the root export carries engine fault flags " + std::to_string((uint32_t)hdr[3]);
+        return AZ_E_DEVICE;
+    }
+    const int G = hdr[1];
+    if (G > r->sel_cap) {
+        (void)hipFree(r->sel);
+        r->sel = nullptr;
+        r->sel_cap = 0;
+        RCHK(r, hipMalloc((void **)&r->sel, (size_t)G * sizeof(long long)));
+        r->sel_cap = G;
+    }
+    RefreshArgs a;
+    a.roots = roots_arrays(const_cast<void *>(roots), (size_t)G, (size_t)r->maxc);
+    a.G = G;
+    a.mc = r->maxc;
+    a.A = r->A;
+    a.value_mode = value_mode;
+    a.n = n;
+    a.n_unique = r->n_unique;
+    a.head = r->head;
+    a.cap = r->cap;
+    a.indices = indices;
+    a.unique = r->unique;
+    a.pw = r->pw;
+    a.ply = r->ply;
+    a.z = r->z;
+    a.pi = r->pi;
+    a.claim = r->claim;
+    a.faults = r->faults;
+    a.sel = r->sel;
+    a.refreshed = r->refreshed;
+    RCHK(r, hipMemsetAsync(r->refreshed, 0, 8, st));
+    const dim3 grid((unsigned)((G + 255) / 256)), block(256);
+    hipLaunchKernelGGL(replay_refresh_claim_kernel, grid, block, 0, st, a);
+    hipLaunchKernelGGL(replay_refresh_write_kernel, grid, block, 0, st, a);
+    hipLaunchKernelGGL(replay_refresh_release_kernel, grid, block, 0, st, a);
+    RCHK(r, hipGetLastError());
+    unsigned long long count = 0;
+    RCHK(r, hipMemcpyAsync(&count, r->refreshed, 8, hipMemcpyDeviceToHost, st));
+    RCHK(r, hipStreamSynchronize(st));
+    return (int64_t)count;
 }
 
 // ------------------------------------------------------------------------------------------------ read-back

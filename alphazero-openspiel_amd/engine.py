@@ -143,6 +143,21 @@ class SelfPlayEngine:
         self.start_history = []  # injected draws are indexed by absolute ply (set_injected_rng(absolute_ply=True))
         self.start_histories = [[int(a) for a in h] for h in histories]
 
+    def set_start_states_device(self, bb, ply):
+        """The device form of set_start_positions: game i starts from the state (bb[i, 0], bb[i, 1], ply[i]) - bb an int64
+        device tensor [n, 2] holding the 64-bit boards (torch has no uint64 arithmetic; the bits are what counts), ply int32 [n],
+        as DeviceReplay.gather_states returns them.  Every state is checked on the device; a bad one raises EngineError
+        naming the lowest offending game and the rule it breaks, and the previous table stays.  reset(n) afterwards."""
+        n = int(ply.numel())
+        for t, dt, shape in ((bb, torch.int64, (n, 2)), (ply, torch.int32, (n,))):
+            if t.dtype != dt or not t.is_contiguous() or t.device != self.device or tuple(t.shape) != shape:
+                raise EngineError("expected a contiguous %s %s tensor on %s, got %s %s on %s"
+                                  % (dt, shape, self.device, t.dtype, tuple(t.shape), t.device))
+        self._check(self.lib.az_engine_set_start_states_device(self._h, C.c_void_p(bb.data_ptr()), C.c_void_p(ply.data_ptr()), n,
+                                                               self._stream()))
+        self.start_history = []
+        self.start_histories = None  # the histories are not known: the states came as positions
+
     def set_injected_rng(self, etas, us, absolute_ply=False):
         """etas: per game, per ply, the Dirichlet draw (ragged lists ok); us: per game, per ply uniforms.  Lists are
         indexed by plies played since the start position unless absolute_ply (then by the state's ply number)."""

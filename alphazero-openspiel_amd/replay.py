@@ -120,6 +120,39 @@ class DeviceReplay:
             torch.cuda.current_stream(self.device).synchronize()  # idx must outlive the kernel
         return x, pi, z
 
+    # ------------------------------------------------------------------ reanalyse (include/az_replay.h)
+    def _indices(self, indices):
+        idx = indices if torch.is_tensor(indices) else torch.as_tensor(np.asarray(indices, dtype=np.int64))
+        return idx.to(device=self.device, dtype=torch.int64).contiguous().reshape(-1)
+
+    def gather_states(self, indices):
+        """Positions of the de-duplicated list (indices: int64 tensor / array, the index space of sample()) -> (bb int64 [n, 2],
+        ply int32 [n]) device tensors, the arguments of SelfPlayEngine.set_start_states_device.  bb holds the 64-bit boards bit
+        for bit (`.cpu().numpy().view(np.uint64)` shows them).  Asynchronous; an index outside the list raises the BAD_INDEX
+        fault flag (stats()) and gives a state with ply -1, which no engine accepts."""
+        idx = self._indices(indices)
+        n = int(idx.numel())
+        bb = torch.empty((n, 2), dtype=torch.int64, device=self.device)
+        ply = torch.empty((n,), dtype=torch.int32, device=self.device)
+        self._check(self.lib.az_replay_gather_states(self._h, C.c_void_p(idx.data_ptr()), n, C.c_void_p(bb.data_ptr()),
+                                                     C.c_void_p(ply.data_ptr()), self._stream()))
+        return bb, ply
+
+    def refresh_from_roots(self, indices, roots_buf, value_target="soft-Z"):
+        """Overwrite the targets of the examples gather_states(indices) named from the finished searches in roots_buf (the packed
+        root export of an engine whose game j searched indices[j]; SelfPlayEngine.export_roots_device): pi = the normalised root
+        visit counts, z by value_target ("soft-Z", "A0C", None = keep).  -> the number of examples refreshed.  RuntimeError
+        (AZ_E_STATE) if the store has changed since gather_states."""
+        if value_target not in _lib.REFRESH_MODES:
+            raise ValueError("value_target must be one of %s: on-policy needs the game's outcome, off-policy a tree descent"
+                             % sorted(map(str, _lib.REFRESH_MODES)))
+        if roots_buf.dtype != torch.uint8 or not roots_buf.is_contiguous() or roots_buf.device != self.device:
+            raise RuntimeError("refresh_from_roots expects a contiguous uint8 tensor on %s" % (self.device,))
+        idx = self._indices(indices)
+        return int(self._check(self.lib.az_replay_refresh_from_roots(
+            self._h, C.c_void_p(idx.data_ptr()), int(idx.numel()), C.c_void_p(roots_buf.data_ptr()), int(roots_buf.numel()),
+            _lib.REFRESH_MODES[value_target], self._stream())))
+
     def read_unique(self):
         n = self.stats()["n_unique"]
         key = np.zeros(n, np.uint64)
@@ -140,6 +173,66 @@ class DeviceReplay:
         self._check(self.lib.az_replay_read_example(self._h, int(index), pi.ctypes.data_as(C.POINTER(C.c_double)),
                                                     C.byref(z)))
         return pi, z.value
+
+
+class Reanalyser:
+    """Refresh stored targets by searching stored positions again with the current network ("Reanalyse").
+
+        re = Reanalyser(store, net, n_slots=4096, n_playouts=400, value_target="soft-Z")
+        store.dedupe(); re.reanalyse(n=8192, seed=gen)      # 8192 distinct positions of the de-duplicated list, in chunks of 4096
+        re.set_evaluator(net)                               # after training: the next call searches with the new weights
+
+    One Analyzer (a manual_moves engine and an evaluator) lives across the calls.  A chunk goes gather_states ->
+    load_states_device -> search_device -> refresh_from_roots: positions and roots stay in HBM, the host sees the 16-byte
+    headers of the root export and the refreshed count.  value_target: "soft-Z", "A0C" or None (pi only) - the targets that
+    are functions of a search root; further keywords go to the Analyzer (c_puct, use_dirichlet, eval_precision, ...).
+    The store must not change between the calls made here (it is the caller's between reanalyse() calls); the next dedupe()
+    averages a refreshed first occurrence with its stale duplicates, as the reference's aliasing does."""
+
+    def __init__(self, store, policy_fn, n_slots, n_playouts, value_target="soft-Z", **kwargs):
+        from .analysis import Analyzer
+        if value_target not in _lib.REFRESH_MODES:
+            raise ValueError("value_target must be one of %s: on-policy needs the game's outcome, off-policy a tree descent"
+                             % sorted(map(str, _lib.REFRESH_MODES)))
+        self.store, self.value_target = store, value_target
+        kwargs.setdefault("device", store.device)
+        kwargs.setdefault("seed", 0)  # (keys the root noise only, and that is off unless use_dirichlet is asked for)
+        self.analyzer = Analyzer(policy_fn, store.game, int(n_slots), n_playouts=int(n_playouts), **kwargs)
+        self.n_slots = self.analyzer.engine.G
+
+    def set_evaluator(self, policy_fn):
+        self.analyzer.set_evaluator(policy_fn)
+
+    def close(self):
+        self.analyzer.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def draw(self, n=None, seed=0):
+        """n distinct indices of the de-duplicated list, drawn on the device (None, or more than there are: all of them)."""
+        n_unique = self.store.stats()["n_unique"]
+        if n_unique < 1:
+            raise RuntimeError("Reanalyser: the store has no de-duplicated list (dedupe() first)")
+        if n is None or int(n) >= n_unique:
+            return torch.arange(n_unique, dtype=torch.int64, device=self.store.device)
+        gen = torch.Generator(device=self.store.device)
+        gen.manual_seed(int(seed))
+        return torch.randperm(n_unique, generator=gen, device=self.store.device)[:int(n)].contiguous()
+
+    def reanalyse(self, n=None, indices=None, seed=0):
+        """Search the positions `indices` (default: draw(n, seed)) and overwrite their targets -> the number refreshed."""
+        idx = self.draw(n, seed) if indices is None else self.store._indices(indices)
+        an, done = self.analyzer, 0
+        for first in range(0, int(idx.numel()), self.n_slots):
+            chunk = idx[first:first + self.n_slots]
+            bb, ply = self.store.gather_states(chunk)
+            an.load_states_device(bb, ply, seed=an.seed + first)
+            done += self.store.refresh_from_roots(chunk, an.search_device(), self.value_target)
+        return done
 
 
 def net_step(net, optimizer, x, pi_target, z_target):

@@ -41,6 +41,9 @@ def main():
     ap.add_argument("--continuous", action="store_true",
                     help="self-play as ONE stream across the generations (ExampleGenerator(continuous=True)): the slots never wait "
                          "for a generation's longest game, and games in flight go on under each updated net")
+    ap.add_argument("--reanalyse", type=int, default=0,
+                    help="before training, search N sampled positions of the de-duplicated buffer again with the current net and "
+                         "overwrite their pi (and z, when --backup is soft-Z or A0C: the targets a search root alone gives)")
     a = ap.parse_args()
 
     dev = torch.device("cuda:0")
@@ -49,7 +52,7 @@ def main():
     net = Net(game.information_state_normalized_vector_shape(), game.num_distinct_actions()).to(dev)
     n_buffer, n_buffer_max = 4 * a.games, 40 * a.games                     # train.py:38-41
     store = replay.DeviceReplay(game, max_games=n_buffer_max, device=dev)
-    trainer = None
+    trainer = reanalyser = None
     generator, before = None, {"moves": 0, "sims": 0}
     if a.continuous:
         generator = ExampleGenerator(net, a.game, dev, continuous=True, n_slots=min(a.games, 4096), n_playouts=a.playouts,
@@ -75,6 +78,17 @@ def main():
             n_buffer += a.games
         store.set_capacity(n_buffer)
         n_unique = store.dedupe()
+        t_re = time.perf_counter()
+        if a.reanalyse:                                                    # stale targets of older generations -> the current net's
+            if reanalyser is None:
+                reanalyser = replay.Reanalyser(store, net, min(a.reanalyse, 4096), a.playouts,
+                                               value_target=a.backup if a.backup in ("soft-Z", "A0C") else None,
+                                               eval_precision=a.precision)
+            else:
+                reanalyser.set_evaluator(net)
+            n_re = reanalyser.reanalyse(n=a.reanalyse, seed=gen)
+            print("gen %d: reanalysed %d of %d unique positions in %.2f s" % (gen, n_re, n_unique, time.perf_counter() - t_re),
+                  flush=True)
         net.train()
         if trainer is None:
             trainer = replay.GraphedNetStep(net, a.batch_size, store)
@@ -106,6 +120,8 @@ def main():
             torch.save(net.state_dict(), os.path.join(a.save, "%d.pth" % gen))
     if generator is not None:
         generator.close()
+    if reanalyser is not None:
+        reanalyser.close()
 
 
 if __name__ == "__main__":

@@ -212,6 +212,21 @@ int az_engine_set_start_prefix(az_engine *e, const int32_t *actions, int32_t n);
  * Injected Dirichlet draws are indexed by the state's ply number, as everywhere.  Synchronises the device. */
 int az_engine_set_start_positions(az_engine *e, const int32_t *actions, const int32_t *lengths, int64_t stride, int64_t n_games);
 
+/* The device form of az_engine_set_start_positions: game id i starts from the state (bb[i][0], bb[i][1], ply[i]), bit
+ * layouts of az_games.h - what az_replay_gather_states writes.  bb_dev: device u64 [n_games][2], ply_dev: device i32 [n_games].
+ * manual_moves engines only, 1 <= n_games <= max_games; it fills the same table, supersedes a prefix or an earlier table, and
+ * the caller resets afterwards (as the host form).  A search depends on a state only through these three words (player to
+ * move = ply & 1, no history), so a position given this way searches exactly as the same position reached by a prefix.
+ * Every state is checked ON THE DEVICE before the table changes (az_check_state of az_games.h, one thread per state):
+ *   both games     0 <= ply < max_plies; no cell held by both sides; no bit outside the board; the position is not
+ *                  terminal; the side to move has a legal move
+ *   connect_four   the sentinel bit 6 of every column is clear; every column is filled from the bottom without holes;
+ *                  popc(bb0) == (ply + 1) / 2 and popc(bb1) == ply / 2
+ *   breakthrough   both sides have a piece; no black piece on the last row, no white piece on the first
+ * A bad state -> AZ_E_INVALID, az_last_error names the lowest offending index ("game <i>") and the first rule it breaks;
+ * nothing is changed then.  Synchronises the device.  There is no host-state form: host callers give prefixes. */
+int az_engine_set_start_states_device(az_engine *e, const uint64_t *bb_dev, const int32_t *ply_dev, int64_t n_games, void *stream);
+
 /*
  * One tick = MCTS.playout's select + expand + backup (mcts.py:126-153) for all slots, fused with the
  * agent's move step when a slot has finished its S playouts (alphazerobot.py:71-93,

@@ -50,7 +50,14 @@ typedef struct az_replay_stats {
 } az_replay_stats;
 
 #define AZ_REPLAY_FAULT_KEY_COLLISION 1u /* remove_duplicates met two different histories with one 64-bit key */
-#define AZ_REPLAY_FAULT_BAD_INDEX 2u     /* az_replay_sample was given an index outside [0, n_unique) */
+#define AZ_REPLAY_FAULT_BAD_INDEX 2u     /* az_replay_sample / az_replay_gather_states / az_replay_refresh_from_roots were given an
+                                            index outside [0, n_unique) */
+#define AZ_REPLAY_FAULT_ROOT_MISMATCH 4u /* az_replay_refresh_from_roots skipped a root that does not belong to its example */
+
+/* value_mode of az_replay_refresh_from_roots: the value targets that are functions of a search root alone */
+#define AZ_REFRESH_KEEP_Z 0 /* pi only */
+#define AZ_REFRESH_SOFT_Z 1 /* z = -root.Q                                         game_utils.py:172-174 */
+#define AZ_REFRESH_A0C 2    /* z = max(child.Q if child.N > 0 else -99.0)          game_utils.py:177-179 */
 
 int az_replay_create(const az_replay_config *cfg, az_replay **out);
 int az_replay_destroy(az_replay *r);
@@ -93,6 +100,35 @@ int az_replay_dedupe(az_replay *r, void *stream);
  * row with NaN and raises AZ_REPLAY_FAULT_BAD_INDEX (asynchronous: reported by az_replay_stats_get). */
 int az_replay_sample(az_replay *r, const int64_t *indices, int32_t batch, uint64_t seed, float *x, float *pi,
                      float *z, void *stream);
+
+/*
+ * Reanalyse: search stored positions again with the current network and overwrite their targets, device to device:
+ *   az_replay_gather_states -> az_engine_set_start_states_device -> reset, tick -> az_engine_export_roots_device ->
+ *   az_replay_refresh_from_roots
+ * The store counts its appends, dedupes and capacity changes (an epoch); az_replay_gather_states records the epoch and a
+ * refresh under another one returns AZ_E_STATE: after a FIFO eviction or a new dedupe the indices may name other records.
+ *
+ * az_replay_gather_states: indices = device int64 [n], the index space of az_replay_sample (the de-duplicated list,
+ * [0, n_unique)).  Writes bb_out u64[n][2], ply_out i32[n]: the inputs of az_engine_set_start_states_device.  Asynchronous.
+ * An index outside the list raises AZ_REPLAY_FAULT_BAD_INDEX and gives the state ply = -1, which the engine's check refuses.
+ *
+ * az_replay_refresh_from_roots: roots = a device buffer (16-byte aligned) in the layout of az_engine_export_roots_device, of an
+ * engine whose game id j searched indices[j].  For every slot with phase 5 and 0 <= game_id < n: pi of the stored example (the
+ * FIRST occurrence the unique entry points at; its duplicates are left alone) becomes the normalised root visit counts - the
+ * arithmetic of the append path, 1/n_children each when no child has a visit - and z follows value_mode.  A slot whose ply
+ * differs from the stored example's, or with a child action outside [0, A), is skipped and raises
+ * AZ_REPLAY_FAULT_ROOT_MISMATCH; a bad index is skipped and raises AZ_REPLAY_FAULT_BAD_INDEX.  The 16-byte header is read
+ * first: AZ_E_INVALID when its slot / child counts do not fit roots_bytes or the store's game, AZ_E_DEVICE when it carries
+ * engine fault flags; nothing is written then.  Synchronises `stream`; returns the number of examples refreshed, or < 0.
+ *
+ * Duplicate indices in one call: the result of the lowest slot is stored (without root noise all of them are the same bits).
+ * The next az_replay_dedupe averages a refreshed first occurrence with its stale duplicates, exactly as the reference's
+ * aliasing treats any first occurrence (train.py:191-197).  On-policy targets (the game's outcome) and off-policy targets
+ * (a descent of the tree) are not functions of a root and cannot be refreshed this way.
+ */
+int az_replay_gather_states(az_replay *r, const int64_t *indices, int64_t n, uint64_t *bb_out, int32_t *ply_out, void *stream);
+int64_t az_replay_refresh_from_roots(az_replay *r, const int64_t *indices, int64_t n, const void *roots, int64_t roots_bytes,
+                                     int32_t value_mode, void *stream);
 
 /* Counters and device fault flags; synchronises the device.  Returns AZ_E_DEVICE when a fault flag is set; the flags are
  * reported ONCE (cleared by this call).  az_replay_dedupe clears AZ_REPLAY_FAULT_KEY_COLLISION when it starts, leaves a group
