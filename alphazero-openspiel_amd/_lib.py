@@ -18,6 +18,8 @@ OPPONENTS = {None: 0, "random": 1, "uct": 2, "external": 3}
 REPLAY_FAULTS = {1: "KEY_COLLISION", 2: "BAD_INDEX", 4: "ROOT_MISMATCH"}
 REFRESH_KEEP_Z, REFRESH_SOFT_Z, REFRESH_A0C = 0, 1, 2
 REFRESH_MODES = {None: REFRESH_KEEP_Z, "soft-Z": REFRESH_SOFT_Z, "A0C": REFRESH_A0C}  # the value targets a root alone gives
+REFRESH_OFF_POLICY = 3
+SEARCH_REFRESH_MODES = {**REFRESH_MODES, "off-policy": REFRESH_OFF_POLICY}  # ... and the one that needs the greedy line as well
 
 
 class AzConfig(C.Structure):
@@ -123,6 +125,8 @@ PROTOTYPES = [
     ("az_engine_stream_take_device", C.c_int, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), _vp]),
     ("az_engine_roots_device_bytes", C.c_int64, [_vp]),
     ("az_engine_export_roots_device", C.c_int, [_vp, _vp, C.c_int64, _vp]),
+    ("az_engine_lines_device_bytes", C.c_int64, [_vp, C.c_int32]),
+    ("az_engine_export_lines_device", C.c_int, [_vp, C.c_int32, _vp, C.c_int64, _vp]),
     ("az_engine_read_root", C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double)]),
@@ -149,6 +153,7 @@ PROTOTYPES = [
     ("az_replay_sample", C.c_int, [_vp, _vp, C.c_int32, C.c_uint64, _vp, _vp, _vp, _vp]),
     ("az_replay_gather_states", C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp]),
     ("az_replay_refresh_from_roots", C.c_int64, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp]),
+    ("az_replay_refresh_from_search", C.c_int64, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp]),
     ("az_replay_stats_get", C.c_int, [_vp, C.POINTER(AzReplayStats)]),
     ("az_replay_read_unique", C.c_int64, [_vp, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_double),
                                           C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_uint64),

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from .engine import (DeviceEvaluator, EngineError, HostPolicyEvaluator, SelfPlayEngine, TickDriver, close_all, default_device,
-                     make_evaluator)
+                     make_evaluator, read_lines)
 from .games import Game, State
 
 PHASE_IDLE, PHASE_SEARCH_DONE = 0, 5
@@ -60,6 +60,10 @@ class Analyzer:
         roots = an.search()                      # engine.read_roots(): every slot's root, one copy
         res = an.results()                       # visits / q / priors [n, A], root_q, root_n, best_action [n]
 
+    With pv_depth = D > 0 every root export is followed by a line export (engine.export_lines_device, one more kernel), and
+    results() also holds the principal variation of every search: pv_actions [n, D] (-1 padded), pv_n, pv_q [n, D], pv_len
+    (the whole line's length, which may exceed D) and greedy_value (the off-policy value target A0GB at the line's end).
+
     Play the best move in 4096 games at once, to the end (a slot whose game is over goes idle and is left alone):
 
         an.load(histories); an.search()
@@ -75,11 +79,13 @@ class Analyzer:
     HostPolicyEvaluator); None = set `.evaluator` (any callable(obs, priors_out, values_out)) before the first search."""
 
     def __init__(self, policy_fn, game_name, n_slots, n_playouts=100, c_puct=2.5, use_dirichlet=False, device=None,
-                 eval_backend="fused", eval_precision="f32x", seed=None, check_every=16, **kwargs):
+                 eval_backend="fused", eval_precision="f32x", seed=None, check_every=16, pv_depth=0, **kwargs):
         if int(n_slots) < 1:
             raise ValueError("n_slots must be positive")
         if int(check_every) < 1:
             raise ValueError("check_every must be positive")
+        if int(pv_depth) < 0:
+            raise ValueError("pv_depth must not be negative")
         self.device = torch.device(device if device is not None else default_device(policy_fn))
         self.n_playouts, self.check_every = int(n_playouts), int(check_every)
         self.seed = int(np.random.randint(0, 2 ** 31 - 1)) if seed is None else int(seed)
@@ -98,6 +104,15 @@ class Analyzer:
             raise
         self.obs, self.pri, self.val = self.engine.alloc_io()
         self.roots_buf = self.engine.alloc_roots()
+        self.pv_depth = int(pv_depth)
+        if self.pv_depth > self.engine.max_plies:
+            self.engine.close()
+            raise ValueError("pv_depth %d: a game of %s has at most %d plies" % (self.pv_depth, self.engine.game.name, self.engine.max_plies))
+        self.lines_buf = None
+        if self.pv_depth:
+            self.lines_buf = torch.empty(self.engine.lines_device_bytes(self.pv_depth), dtype=torch.uint8, device=self.engine.device)
+        self._value_lines_buf = None
+        self.lines = None
         self._header = torch.empty(4, dtype=torch.int32).pin_memory()
         self.n = 0
         self.ticks = 0
@@ -129,7 +144,7 @@ class Analyzer:
         self.engine.set_start_positions(histories)
         self.engine.reset(len(histories), self.seed if seed is None else seed)
         self.n = len(histories)
-        self.roots = None
+        self.roots = self.lines = None
 
     def load_states_device(self, bb, ply, seed=None):
         """The device twin of load: start a search from each of the n <= n_slots states (bb int64 [n, 2], ply int32 [n] device
@@ -140,14 +155,14 @@ class Analyzer:
         self.engine.set_start_states_device(bb, ply)
         self.engine.reset(n, self.seed if seed is None else seed)
         self.n = n
-        self.roots = None
+        self.roots = self.lines = None
 
     def update_root(self, actions, keep_subtree=True):
         """MCTS.update_root for every loaded position (actions [n]; -1 leaves a slot alone) and arm the next search."""
         acts = np.full(self.engine.G, -1, dtype=np.int64)
         acts[:self.n] = np.asarray(actions, dtype=np.int64).reshape(-1)[:self.n]
         self.engine.update_root(acts.tolist(), keep_subtree=keep_subtree)
-        self.roots = None
+        self.roots = self.lines = None
 
     def search_again(self):
         """Another n_playouts on the same roots (MCTS.search called twice, mcts.py:164-180)."""
@@ -157,6 +172,8 @@ class Analyzer:
     def _finished(self):
         """Root export + its 16-byte header: (slots finished or idle, error flags).  One kernel, one small copy."""
         self.engine.export_roots_device(self.roots_buf)
+        if self.pv_depth:
+            self.engine.export_lines_device(self.pv_depth, self.lines_buf)
         self._header.copy_(self.roots_buf[:16].view(torch.int32), non_blocking=True)
         torch.cuda.current_stream(self.engine.device).synchronize()
         return int(self._header[0]), int(self._header[3]) & 0xFFFFFFFF
@@ -166,6 +183,7 @@ class Analyzer:
         with torch.cuda.device(self.engine.device):
             self.search_device(max_ticks)
             self.roots = self.engine.read_roots(self.roots_buf)
+            self.lines = read_lines(self.lines_buf) if self.pv_depth else None
         return self.roots
 
     def search_device(self, max_ticks=None):
@@ -192,15 +210,38 @@ class Analyzer:
                     raise EngineError("analysis did not finish within %d ticks: %r" % (limit, e.progress()))
                 drv.run(self.check_every)
             self.ticks += drv.ticks
-        self.roots = None
+        self.roots = self.lines = None
         return self.roots_buf
+
+    def lines_device(self, max_depth=1):
+        """The packed line export (engine.export_lines_device) of the finished searches -> a device buffer this Analyzer owns
+        and rewrites per call.  The value target and the line's length do not depend on max_depth; Reanalyser takes 1."""
+        D = int(max_depth)
+        if self.pv_depth and D == self.pv_depth:
+            return self.engine.export_lines_device(D, self.lines_buf)
+        need = self.engine.lines_device_bytes(D)
+        if self._value_lines_buf is None or self._value_lines_buf.numel() != need:
+            self._value_lines_buf = torch.empty(need, dtype=torch.uint8, device=self.engine.device)
+        return self.engine.export_lines_device(D, self._value_lines_buf)
 
     def results(self):
         """The loaded positions' roots as dense arrays: visits [n, A] int64, q / priors [n, A] float64 (zero where there is
         no child), root_q, root_n, best_action [n] (first maximum of the visits: the engine's rule), phase [n]."""
         if self.roots is None:
             self.roots = self.engine.read_roots(self.roots_buf)
-        return dense_roots(self.roots, self.n, self.engine.A)
+        res = dense_roots(self.roots, self.n, self.engine.A)
+        if self.pv_depth:
+            if self.lines is None:
+                self.lines = read_lines(self.engine.export_lines_device(self.pv_depth, self.lines_buf))
+            res.update(dense_lines(self.lines, self.n))
+        return res
+
+
+def dense_lines(lines, n):
+    """read_lines() dict -> the principal-variation arrays of the first n slots (see Analyzer)."""
+    return {"pv_actions": lines["line_action"][:n].astype(np.int64), "pv_n": lines["line_n"][:n].copy(),
+            "pv_q": lines["line_q"][:n].copy(), "pv_len": lines["depth"][:n].astype(np.int64),
+            "greedy_value": lines["value"][:n].copy()}
 
 
 def dense_roots(roots, n, num_actions):
@@ -222,13 +263,15 @@ def dense_roots(roots, n, num_actions):
 
 
 def analyze_positions(policy_fn, game_name, histories, n_playouts=100, c_puct=2.5, use_dirichlet=False, n_slots=None,
-                      device=None, eval_backend="fused", eval_precision="f32x", seed=None, check_every=16, **kwargs):
+                      device=None, eval_backend="fused", eval_precision="f32x", seed=None, check_every=16, pv_depth=0, **kwargs):
     """Search every given position with n_playouts of PUCT search, all of them side by side on the device.
 
     policy_fn   the network (nn.Module or its bound .predict) or an evaluator object, as elsewhere in the package
     histories   a list of action lists (from the initial position) or of `games.State`
     n_slots     positions searched at once (default min(n, 4096)); more positions run in chunks on ONE engine and ONE
                 evaluator.  With the fused network at f32x the results do not depend on it.
+    pv_depth    D > 0: also return every position's principal variation - pv_actions [n, D] (-1 padded), pv_n, pv_q [n, D],
+                pv_len [n] (the whole greedy line's length) and greedy_value [n] (the off-policy target A0GB at its end)
     kwargs      further SelfPlayEngine keywords (dirichlet_ratio, use_puct, nodes_per_slot, max_sims_per_tick, ...)
 
     Returns a dict, rows in the order given: visits [n, A] int64, q [n, A], priors [n, A] float64 (zero where there is no
@@ -242,7 +285,7 @@ def analyze_positions(policy_fn, game_name, histories, n_playouts=100, c_puct=2.
     if n_slots < 1:
         raise ValueError("n_slots must be positive")
     an = Analyzer(policy_fn, game, n_slots, n_playouts=n_playouts, c_puct=c_puct, use_dirichlet=use_dirichlet, device=device,
-                  eval_backend=eval_backend, eval_precision=eval_precision, seed=seed, check_every=check_every, **kwargs)
+                  eval_backend=eval_backend, eval_precision=eval_precision, seed=seed, check_every=check_every, pv_depth=pv_depth, **kwargs)
     try:
         parts = []
         prog = {k: 0 for k in _PROGRESS_SUMS}

@@ -216,6 +216,69 @@ __device__ __forceinline__ void pool_init_root(const Pool &t, int lane) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The greedy line of a tree (A0GB, game_utils.py:181-194), one wave per tree; the ONE copy of the walk: move_step takes its
+// value, az_export_lines_kernel records it.  At a node with children value = node.Q and the next node is the child with the
+// largest N + P (-99.0 for a child without a visit); the first maximum wins = the lowest action, children being in
+// ascending-action order like the dict of mcts.py.  The sign flips per step; a final leaf with a visit gives value = leaf.Q and
+// one more flip.  visit(d, node, meta, n) is called by all lanes with wave-uniform arguments for the node reached after d + 1
+// moves.  A line has at most max_steps moves (a game has max_plies plies): a walk that would go on, or that meets a child block
+// outside the pool, is cut there (cut = true; value is that of the line so far) - it never spins on a corrupt tree.
+struct LineEnd {
+    double value;    // value * mult of game_utils.py:194
+    int steps;       // moves walked
+    bool cut;
+    uint32_t leaf_n; // N of the node the walk ended at
+};
+struct LineValueOnly {
+    __device__ __forceinline__ void operator()(int, uint32_t, uint32_t, uint32_t) const {}
+};
+template <class Visit>
+__device__ __forceinline__ LineEnd greedy_line(const AzNode *__restrict__ nd, const uint32_t cap, const uint32_t root, const int lane,
+                                               const int max_steps, Visit visit) {
+    uint32_t node = root, nn = rflu(nd[root].N);
+    uint32_t kc0 = rflu(nd[root].C0);
+    int knc = kc0 == NONE32 ? 0 : (int)(rflu(nd[root].META) >> 16);
+    double value = 0.0, mult = 1.0;
+    LineEnd end = {0.0, 0, false, 0u};
+    while (knc > 0) {
+        if (end.steps >= max_steps || knc > 64 || kc0 >= cap || kc0 + (uint32_t)knc > cap) {
+            end.cut = true;
+            break;
+        }
+        value = nd[node].Q;
+        double sc = -INFINITY;
+        uint32_t n2 = 0, c2 = NONE32, m2 = 0;
+        if (lane < knc) {
+            n2 = nd[kc0 + lane].N;
+            c2 = nd[kc0 + lane].C0;
+            m2 = nd[kc0 + lane].META;
+            sc = n2 > 0 ? (double)n2 + nd[kc0 + lane].P : -99.0;
+        }
+        double mx = wave_max(sc);
+        int best = __ffsll((unsigned long long)__ballot(sc == mx)) - 1;
+        if (best < 0) { // (a NaN prior: no lane equals the maximum)
+            end.cut = true;
+            break;
+        }
+        node = kc0 + (uint32_t)best;
+        nn = rflu(__shfl(n2, best));
+        const uint32_t meta = rflu(__shfl(m2, best));
+        kc0 = rflu(__shfl(c2, best));
+        knc = kc0 == NONE32 ? 0 : (int)(meta >> 16);
+        mult *= -1.0;
+        visit(end.steps, node, meta, nn);
+        end.steps++;
+    }
+    if (!end.cut && nn > 0) {
+        value = nd[node].Q;
+        mult *= -1.0;
+    }
+    end.value = value * mult;
+    end.leaf_n = nn;
+    return end;
+}
+
 template <int NP> struct Path { // depth d lives in lane d&63, register d>>6
     uint32_t r[NP];  // node index
     uint32_t pn[NP]; // the node's N and Q as last read or written by this wave: the backup needs no second read
@@ -755,34 +818,8 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
             target = -t.nd[sr.root].Q;
         } else if (p.backup == AZ_BACKUP_A0C) {
             target = wave_max(lane < nc ? (cn > 0 ? cq : -99.0) : -INFINITY);
-        } else if (p.backup == AZ_BACKUP_OFF_POLICY) { // A0GB: walk the most-visited line
-            uint32_t node = sr.root, nn = rflu(t.nd[sr.root].N);
-            double value = 0.0, mult = 1.0;
-            uint32_t kc0 = c0;
-            int knc = nc;
-            while (knc > 0) {
-                value = t.nd[node].Q;
-                double sc = -INFINITY;
-                uint32_t n2 = 0, c2 = NONE32, m2 = 0;
-                if (lane < knc) {
-                    n2 = t.nd[kc0 + lane].N;
-                    c2 = t.nd[kc0 + lane].C0;
-                    m2 = t.nd[kc0 + lane].META;
-                    sc = n2 > 0 ? (double)n2 + t.nd[kc0 + lane].P : -99.0;
-                }
-                double mx = wave_max(sc);
-                int best = __ffsll((unsigned long long)__ballot(sc == mx)) - 1;
-                node = kc0 + (uint32_t)best;
-                nn = rflu(__shfl(n2, best));
-                kc0 = rflu(__shfl(c2, best));
-                knc = kc0 == NONE32 ? 0 : (int)(rflu(__shfl(m2, best)) >> 16);
-                mult *= -1.0;
-            }
-            if (nn > 0) {
-                value = t.nd[node].Q;
-                mult *= -1.0;
-            }
-            target = value * mult;
+        } else if (p.backup == AZ_BACKUP_OFF_POLICY) { // A0GB: the value at the end of the most-visited line
+            target = greedy_line(t.nd, p.cap, sr.root, lane, p.max_plies - sr.rs.ply + 1, LineValueOnly()).value;
         }
         // action sampling: visit fractions -> remove_illegal_actions -> temperature -> np.random.choice
         double nv = (lane < nc && tot > 0) ? (double)cn / (double)tot : 0.0; // mcts.py:162
@@ -2567,6 +2604,117 @@ extern "C" int az_engine_export_roots_device(az_engine *e, void *dev_buf, int64_
     hipLaunchKernelGGL(az_export_roots_kernel, dim3((e->p.G + 3) / 4), dim3(256), 0, st, e->p, o);
     HIPCHK(e, hipGetLastError());
     hipLaunchKernelGGL(az_roots_header_kernel, dim3(1), dim3(1024), 0, st, e->p, o);
+    HIPCHK(e, hipGetLastError());
+    return AZ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The greedy line of every slot's finished search in one buffer (layout: include/az_engine.h, az_engine_export_lines_device).
+// A wave per slot walks its tree with greedy_line, lane 0 records the first D steps as they are met, then the wave clears the
+// rows the line did not reach, so the buffer's contents depend on the trees alone.  The header is written by workgroup 0 from
+// the phase words themselves (nothing on the stream changes them while this kernel runs): one kernel, no counter, no atomics.
+struct LineRecord {
+    LinesOut o;
+    const AzNode *nd;
+    size_t row;
+    int D, lane;
+    __device__ __forceinline__ void operator()(int d, uint32_t node, uint32_t meta, uint32_t n) const {
+        if (d < D && lane == 0) {
+            o.line_action[row + d] = (int)(meta & 0xFFFFu);
+            o.line_n[row + d] = n;
+            o.line_q[row + d] = nd[node].Q;
+        }
+    }
+};
+
+__global__ __launch_bounds__(256) void az_export_lines_kernel(Params p, LinesOut o, int D) {
+    __shared__ int s_cnt[4];
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g < p.G) {
+        const int ph = rfl(p.phase[g]);
+        const int ply = rfl(p.ply[g]);
+        const int pool = rfl(p.which[g]) & POOL_MASK;
+        const uint32_t root = rflu(p.root[g]);
+        const size_t row = (size_t)g * D;
+        int depth = -1, written = 0;
+        uint32_t leaf_n = 0;
+        double value = 0.0;
+        if (ph == PH_SEARCH_DONE) {
+            if (pool < p.G + p.n_spare && root < p.cap && ply >= 0 && ply <= p.max_plies) { // (a slot's own words: never out of the pools)
+                const AzNode *nd = p.nodes + (size_t)pool * p.cap;
+                const LineRecord rec = {o, nd, row, D, lane};
+                const LineEnd end = greedy_line(nd, p.cap, root, lane, p.max_plies - ply + 1, rec);
+                depth = end.cut ? -2 : end.steps;
+                written = end.steps < D ? end.steps : D;
+                leaf_n = end.leaf_n;
+                value = end.value;
+            } else {
+                depth = -2;
+            }
+        }
+        if (lane == 0) {
+            o.game_id[g] = p.gid[g];
+            o.phase[g] = ph;
+            o.ply[g] = ply;
+            o.depth[g] = depth;
+            o.leaf_n[g] = leaf_n;
+            o.value[g] = value;
+        }
+        for (int d = written + lane; d < D; d += 64) {
+            o.line_action[row + d] = -1;
+            o.line_n[row + d] = 0u;
+            o.line_q[row + d] = 0.0;
+        }
+    }
+    if (blockIdx.x == 0) {
+        int n = 0;
+        for (int s = threadIdx.x; s < p.G; s += 256) {
+            const int ph = p.phase[s];
+            n += ph == PH_SEARCH_DONE || ph == PH_IDLE;
+        }
+        for (int d = 32; d > 0; d >>= 1) n += __shfl_down(n, d);
+        if (lane == 0) s_cnt[threadIdx.x >> 6] = n;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            o.header[0] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+            o.header[1] = p.G;
+            o.header[2] = D;
+            o.header[3] = (int)*p.faults;
+        }
+    }
+}
+
+extern "C" int64_t az_engine_lines_device_bytes(const az_engine *e, int32_t max_depth) {
+    if (!e || max_depth < 1 || max_depth > e->p.max_plies) return AZ_E_INVALID;
+    size_t off[AZ_LINES_ARRAYS + 1];
+    lines_offsets((size_t)e->p.G, (size_t)max_depth, off);
+    return (int64_t)off[AZ_LINES_ARRAYS];
+}
+
+extern "C" int az_engine_export_lines_device(az_engine *e, int32_t max_depth, void *dev_buf, int64_t bytes, void *stream) {
+    if (!e || !dev_buf) return AZ_E_INVALID;
+    if (max_depth < 1 || max_depth > e->p.max_plies) {
+        e->err = "az_engine_export_lines_device: max_depth must lie in [1, max_plies = " + std::to_string(e->p.max_plies) + "]";
+        return AZ_E_INVALID;
+    }
+    size_t off[AZ_LINES_ARRAYS + 1];
+    lines_offsets((size_t)e->p.G, (size_t)max_depth, off);
+    if (bytes < (int64_t)off[AZ_LINES_ARRAYS]) {
+        e->err = "az_engine_export_lines_device: buffer smaller than az_engine_lines_device_bytes()";
+        return AZ_E_INVALID;
+    }
+    if (((uintptr_t)dev_buf & 15) != 0) {
+        e->err = "az_engine_export_lines_device: the buffer must be 16-byte aligned";
+        return AZ_E_INVALID;
+    }
+    if (!e->reset_done) {
+        e->err = "az_engine_export_lines_device before az_engine_reset";
+        return AZ_E_STATE;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    LinesOut o = lines_arrays(dev_buf, (size_t)e->p.G, (size_t)max_depth);
+    hipLaunchKernelGGL(az_export_lines_kernel, dim3((e->p.G + 3) / 4), dim3(256), 0, (hipStream_t)stream, e->p, o, (int)max_depth);
     HIPCHK(e, hipGetLastError());
     return AZ_OK;
 }

@@ -172,3 +172,37 @@ static inline RootsOut roots_arrays(void *dev_buf, size_t G, size_t mc) {
     o.child_p = (double *)(b + off[11]);
     return o;
 }
+
+// The packed line export (layout: include/az_engine.h, az_engine_export_lines_device): written by az_engine.hip, read by the
+// replay store's az_replay_refresh_from_search.
+#define AZ_LINES_ARRAYS 10
+static inline void lines_offsets(size_t G, size_t D, size_t off[AZ_LINES_ARRAYS + 1]) {
+    const size_t sizes[AZ_LINES_ARRAYS] = {16, G * 4, G * 4, G * 4, G * 4, G * 4, G * 8, G * D * 4, G * D * 4, G * D * 8};
+    off[0] = 0;
+    for (int i = 0; i < AZ_LINES_ARRAYS; i++) off[i + 1] = off[i] + ((sizes[i] + 15) & ~(size_t)15);
+}
+struct LinesOut {
+    int *header, *game_id, *phase, *ply, *depth;
+    uint32_t *leaf_n;
+    double *value;
+    int *line_action;
+    uint32_t *line_n;
+    double *line_q;
+};
+static inline LinesOut lines_arrays(void *dev_buf, size_t G, size_t D) {
+    size_t off[AZ_LINES_ARRAYS + 1];
+    lines_offsets(G, D, off);
+    char *b = (char *)dev_buf;
+    LinesOut o;
+    o.header = (int *)(b + off[0]);
+    o.game_id = (int *)(b + off[1]);
+    o.phase = (int *)(b + off[2]);
+    o.ply = (int *)(b + off[3]);
+    o.depth = (int *)(b + off[4]);
+    o.leaf_n = (uint32_t *)(b + off[5]);
+    o.value = (double *)(b + off[6]);
+    o.line_action = (int *)(b + off[7]);
+    o.line_n = (uint32_t *)(b + off[8]);
+    o.line_q = (double *)(b + off[9]);
+    return o;
+}

@@ -746,6 +746,7 @@ extern "C" int az_replay_gather_states(az_replay *r, const int64_t *indices, int
 #define REFRESH_FREE 0xFFFFFFFFu
 struct RefreshArgs {
     RootsOut roots; // (read only here)
+    LinesOut lines; // (read only; AZ_REFRESH_OFF_POLICY alone looks at it)
     int G, mc, A, value_mode;
     long long n, n_unique, head, cap;
     const int64_t *indices, *unique;
@@ -773,6 +774,8 @@ __global__ void replay_refresh_claim_kernel(RefreshArgs a) {
     long long phys = (a.head + a.unique[u]) % a.cap;
     int nc = a.roots.n_children[g];
     bool ok = a.roots.ply[g] == a.ply[phys] && nc >= 0 && nc <= a.mc;
+    if (a.value_mode == AZ_REFRESH_OFF_POLICY) // the line must be of the search the root is of, and a whole one
+        ok = ok && a.lines.game_id[g] == gid && a.lines.ply[g] == a.roots.ply[g] && a.lines.phase[g] == PH_SEARCH_DONE && a.lines.depth[g] >= 0;
     for (int k = 0; ok && k < nc; k++) {
         int act = a.roots.child_action[(size_t)g * a.mc + k];
         ok = act >= 0 && act < a.A;
@@ -801,6 +804,8 @@ __global__ void replay_refresh_write_kernel(RefreshArgs a) {
             if (k == 0 || v > best) best = v;
         }
         if (nc > 0) a.z[phys] = best;
+    } else if (a.value_mode == AZ_REFRESH_OFF_POLICY) { // game_utils.py:182-194, walked by az_engine_export_lines_device
+        a.z[phys] = a.lines.value[g];
     }
     atomicAdd(a.refreshed, 1ull);
 }
@@ -809,40 +814,51 @@ __global__ void replay_refresh_release_kernel(RefreshArgs a) {
     if (g < a.G && a.sel[g] >= 0) a.claim[a.sel[g]] = REFRESH_FREE;
 }
 
-extern "C" int64_t az_replay_refresh_from_roots(az_replay *r, const int64_t *indices, int64_t n, const void *roots, int64_t roots_bytes,
-                                                int32_t value_mode, void *stream) {
-    if (!r) return AZ_E_INVALID;
-    if (!indices || !roots || n < 1 || ((uintptr_t)roots & 15) != 0 ||
-        (value_mode != AZ_REFRESH_KEEP_Z && value_mode != AZ_REFRESH_SOFT_Z && value_mode != AZ_REFRESH_A0C)) {
-        r->err = "az_replay_refresh_from_roots: null / unaligned argument, n < 1 or an unknown value_mode";
+// Both refresh entries: `what` names the entry in the error texts; lines is read in AZ_REFRESH_OFF_POLICY only.
+static int64_t refresh_from_search(az_replay *r, const std::string &what, const int64_t *indices, int64_t n, const void *roots,
+                                   int64_t roots_bytes, const void *lines, int64_t lines_bytes, int32_t value_mode, hipStream_t st) {
+    const bool off_policy = value_mode == AZ_REFRESH_OFF_POLICY;
+    if (roots_bytes < 16) {
+        r->err = what + ": roots_bytes does not hold the header";
         return AZ_E_INVALID;
     }
-    if (roots_bytes < 16) {
-        r->err = "az_replay_refresh_from_roots: roots_bytes does not hold the header";
+    if (off_policy && lines_bytes < 16) {
+        r->err = what + ": lines_bytes does not hold the header";
         return AZ_E_INVALID;
     }
     if (r->n_unique < 1 || r->gather_epoch != r->epoch) {
-        r->err = "az_replay_refresh_from_roots: the store has changed (append, dedupe or capacity) since az_replay_gather_states - the "
+        r->err = what + ": the store has changed (append, dedupe or capacity) since az_replay_gather_states - the "
                  "indices may name other records";
         return AZ_E_STATE;
     }
-    hipStream_t st = (hipStream_t)stream;
     RCHK(r, hipSetDevice(r->cfg.device));
-    int32_t hdr[4] = {0, 0, 0, 0};
+    int32_t hdr[4] = {0, 0, 0, 0}, lhdr[4] = {0, 0, 0, 0};
     RCHK(r, hipMemcpyAsync(hdr, roots, 16, hipMemcpyDeviceToHost, st));
+    if (off_policy) RCHK(r, hipMemcpyAsync(lhdr, lines, 16, hipMemcpyDeviceToHost, st));
     RCHK(r, hipStreamSynchronize(st));
     size_t off[AZ_ROOTS_ARRAYS + 1];
     if (hdr[1] >= 1 && hdr[2] == r->maxc) roots_offsets((size_t)hdr[1], (size_t)hdr[2], off);
     if (hdr[1] < 1 || hdr[2] != r->maxc || (int64_t)off[AZ_ROOTS_ARRAYS] > roots_bytes) {
-        r->err = "az_replay_refresh_from_roots: the header says " + std::to_string(hdr[1]) + " slots x " + std::to_string(hdr[2]) +
+        r->err = what + ": the header says " + std::to_string(hdr[1]) + " slots x " + std::to_string(hdr[2]) +
                  " children: not a root export of this game that fits roots_bytes = " + std::to_string(roots_bytes);
         return AZ_E_INVALID;
     }
-    if (hdr[3] != 0) {
-        r->err = "az_replay_refresh_from_roots: the root export carries engine fault flags " + std::to_string((uint32_t)hdr[3]);
+    const int G = hdr[1];
+    if (off_policy) {
+        size_t loff[AZ_LINES_ARRAYS + 1];
+        const bool shape = lhdr[1] == G && lhdr[2] >= 1 && lhdr[2] <= r->max_plies;
+        if (shape) lines_offsets((size_t)lhdr[1], (size_t)lhdr[2], loff);
+        if (!shape || (int64_t)loff[AZ_LINES_ARRAYS] > lines_bytes) {
+            r->err = what + ": the lines header says " + std::to_string(lhdr[1]) + " slots x depth " + std::to_string(lhdr[2]) +
+                     ": not a line export of the " + std::to_string(G) + " slots of the roots that fits lines_bytes = " +
+                     std::to_string(lines_bytes);
+            return AZ_E_INVALID;
+        }
+    }
+    if (hdr[3] != 0 || lhdr[3] != 0) {
+        r->err = what + ": the export carries engine fault flags " + std::to_string((uint32_t)(hdr[3] | lhdr[3]));
         return AZ_E_DEVICE;
     }
-    const int G = hdr[1];
     if (G > r->sel_cap) {
         (void)hipFree(r->sel);
         r->sel = nullptr;
@@ -852,6 +868,8 @@ extern "C" int64_t az_replay_refresh_from_roots(az_replay *r, const int64_t *ind
     }
     RefreshArgs a;
     a.roots = roots_arrays(const_cast<void *>(roots), (size_t)G, (size_t)r->maxc);
+    a.lines = LinesOut();
+    if (off_policy) a.lines = lines_arrays(const_cast<void *>(lines), (size_t)G, (size_t)lhdr[2]);
     a.G = G;
     a.mc = r->maxc;
     a.A = r->A;
@@ -880,6 +898,33 @@ extern "C" int64_t az_replay_refresh_from_roots(az_replay *r, const int64_t *ind
     RCHK(r, hipMemcpyAsync(&count, r->refreshed, 8, hipMemcpyDeviceToHost, st));
     RCHK(r, hipStreamSynchronize(st));
     return (int64_t)count;
+}
+
+extern "C" int64_t az_replay_refresh_from_roots(az_replay *r, const int64_t *indices, int64_t n, const void *roots, int64_t roots_bytes,
+                                                int32_t value_mode, void *stream) {
+    if (!r) return AZ_E_INVALID;
+    if (!indices || !roots || n < 1 || ((uintptr_t)roots & 15) != 0 ||
+        (value_mode != AZ_REFRESH_KEEP_Z && value_mode != AZ_REFRESH_SOFT_Z && value_mode != AZ_REFRESH_A0C)) {
+        r->err = "az_replay_refresh_from_roots: null / unaligned argument, n < 1 or a value_mode that is no function of a root";
+        return AZ_E_INVALID;
+    }
+    return refresh_from_search(r, "az_replay_refresh_from_roots", indices, n, roots, roots_bytes, nullptr, 0, value_mode, (hipStream_t)stream);
+}
+
+extern "C" int64_t az_replay_refresh_from_search(az_replay *r, const int64_t *indices, int64_t n, const void *roots, int64_t roots_bytes,
+                                                 const void *lines, int64_t lines_bytes, int32_t value_mode, void *stream) {
+    if (!r) return AZ_E_INVALID;
+    if (!indices || !roots || n < 1 || ((uintptr_t)roots & 15) != 0 || ((uintptr_t)lines & 15) != 0 || value_mode < AZ_REFRESH_KEEP_Z ||
+        value_mode > AZ_REFRESH_OFF_POLICY) {
+        r->err = "az_replay_refresh_from_search: null / unaligned argument, n < 1 or an unknown value_mode";
+        return AZ_E_INVALID;
+    }
+    if (value_mode == AZ_REFRESH_OFF_POLICY && !lines) {
+        r->err = "az_replay_refresh_from_search: AZ_REFRESH_OFF_POLICY needs the line export (lines is NULL)";
+        return AZ_E_INVALID;
+    }
+    return refresh_from_search(r, "az_replay_refresh_from_search", indices, n, roots, roots_bytes, lines, lines_bytes, value_mode,
+                               (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------ read-back

@@ -343,6 +343,24 @@ class SelfPlayEngine:
         buf = self.export_roots_device(self.alloc_roots() if buf is None else buf)
         return unpack_roots_export(buf.cpu().numpy(), self.G, self.max_children)
 
+    def lines_device_bytes(self, max_depth):
+        if not 1 <= int(max_depth) <= self.max_plies:
+            raise EngineError("max_depth %d is outside [1, max_plies = %d]" % (int(max_depth), self.max_plies))
+        return int(self._check(self.lib.az_engine_lines_device_bytes(self._h, int(max_depth))))
+
+    def export_lines_device(self, max_depth, buf=None):
+        """Pack the greedy line of every slot's finished search (the principal variation, and the off-policy value target A0GB
+        at its end) into `buf` (default: a fresh uint8 device tensor; layout: lines_export_layout) on the current stream: one
+        kernel, no host synchronisation, may be captured in a graph.  max_depth = the steps kept per line, 1..max_plies; depth
+        and value are those of the whole line whatever it is."""
+        if buf is None:
+            buf = torch.empty(self.lines_device_bytes(max_depth), dtype=torch.uint8, device=self.device)
+        elif buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.device != self.device:
+            raise EngineError("expected a contiguous uint8 tensor on %s" % (self.device,))
+        self._check(self.lib.az_engine_export_lines_device(self._h, int(max_depth), C.c_void_p(buf.data_ptr()), int(buf.numel()),
+                                                           self._stream()))
+        return buf
+
 
 def pack_histories(histories):
     """Action lists -> (actions int32 [n, stride], lengths int32 [n], stride): the arguments of az_engine_set_start_positions."""
@@ -386,6 +404,47 @@ def unpack_roots_export(host_bytes, n_slots, max_children):
     out["n_finished"], out["error_flags"] = int(hdr[0]), int(hdr[3]) & 0xFFFFFFFF
     out["root_n"] = out["root_n"].astype(np.int64)
     out["child_n"] = out["child_n"].astype(np.int64)
+    return out
+
+
+def lines_export_layout(n_slots, max_depth):
+    """(name, dtype, shape, byte offset) of every array in the packed line export (include/az_engine.h,
+    az_engine_export_lines_device) + total bytes."""
+    G, D = int(n_slots), int(max_depth)
+    spec = (("header", np.int32, (4,)), ("game_id", np.int32, (G,)), ("phase", np.int32, (G,)), ("ply", np.int32, (G,)),
+            ("depth", np.int32, (G,)), ("leaf_n", np.uint32, (G,)), ("value", np.float64, (G,)),
+            ("line_action", np.int32, (G, D)), ("line_n", np.uint32, (G, D)), ("line_q", np.float64, (G, D)))
+    out, off = [], 0
+    for name, dt, shape in spec:
+        out.append((name, dt, shape, off))
+        off += (int(np.prod(shape)) * np.dtype(dt).itemsize + 15) & ~15
+    return out, off
+
+
+def read_lines(buf):
+    """A packed line export (SelfPlayEngine.export_lines_device; a uint8 device tensor, or a host copy of one) -> dict of numpy
+    arrays game_id / phase / ply / depth [G], leaf_n [G] int64, value [G] float64, line_action [G, D] int32 (-1 beyond the
+    line), line_n [G, D] int64, line_q [G, D] float64, plus n_finished, max_depth and error_flags from the header (which also
+    gives G and D)."""
+    host = buf.cpu().numpy() if torch.is_tensor(buf) else buf
+    host = np.ascontiguousarray(host, dtype=np.uint8).reshape(-1)
+    if host.size < 16:
+        raise ValueError("line export buffer holds %d bytes, not even the header" % host.size)
+    hdr = host[:16].view(np.int32)
+    G, D = int(hdr[1]), int(hdr[2])
+    if G < 1 or D < 1:
+        raise ValueError("line export header says %d slots x depth %d" % (G, D))
+    layout, total = lines_export_layout(G, D)
+    if host.size < total:
+        raise ValueError("line export buffer holds %d bytes, its header's layout needs %d" % (host.size, total))
+    out = {}
+    for name, dt, shape, off in layout:
+        cnt = int(np.prod(shape)) * np.dtype(dt).itemsize
+        out[name] = host[off:off + cnt].view(dt).reshape(shape)
+    out.pop("header")
+    out["n_finished"], out["max_depth"], out["error_flags"] = int(hdr[0]), D, int(hdr[3]) & 0xFFFFFFFF
+    out["leaf_n"] = out["leaf_n"].astype(np.int64)
+    out["line_n"] = out["line_n"].astype(np.int64)
     return out
 
 

@@ -144,14 +144,32 @@ class DeviceReplay:
         visit counts, z by value_target ("soft-Z", "A0C", None = keep).  -> the number of examples refreshed.  RuntimeError
         (AZ_E_STATE) if the store has changed since gather_states."""
         if value_target not in _lib.REFRESH_MODES:
-            raise ValueError("value_target must be one of %s: on-policy needs the game's outcome, off-policy a tree descent"
-                             % sorted(map(str, _lib.REFRESH_MODES)))
+            raise ValueError("value_target must be one of %s: on-policy needs the game's outcome, off-policy the searches' "
+                             "greedy lines as well (refresh_from_search)" % sorted(map(str, _lib.REFRESH_MODES)))
         if roots_buf.dtype != torch.uint8 or not roots_buf.is_contiguous() or roots_buf.device != self.device:
             raise RuntimeError("refresh_from_roots expects a contiguous uint8 tensor on %s" % (self.device,))
         idx = self._indices(indices)
         return int(self._check(self.lib.az_replay_refresh_from_roots(
             self._h, C.c_void_p(idx.data_ptr()), int(idx.numel()), C.c_void_p(roots_buf.data_ptr()), int(roots_buf.numel()),
             _lib.REFRESH_MODES[value_target], self._stream())))
+
+    def refresh_from_search(self, indices, roots_buf, lines_buf, value_target="off-policy"):
+        """refresh_from_roots with the searches' greedy lines at hand (lines_buf: SelfPlayEngine.export_lines_device of the same
+        engine at the same moment as roots_buf, any max_depth; None for the targets that do not need it): value_target may also
+        be "off-policy" - z = the value at the end of the most-visited line (A0GB).  pi comes from the roots as always."""
+        if value_target not in _lib.SEARCH_REFRESH_MODES:
+            raise ValueError("value_target must be one of %s: on-policy needs the game's outcome"
+                             % sorted(map(str, _lib.SEARCH_REFRESH_MODES)))
+        if value_target == "off-policy" and lines_buf is None:
+            raise ValueError("value_target off-policy needs lines_buf (SelfPlayEngine.export_lines_device)")
+        for buf in (roots_buf, lines_buf):
+            if buf is not None and (buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.device != self.device):
+                raise RuntimeError("refresh_from_search expects contiguous uint8 tensors on %s" % (self.device,))
+        idx = self._indices(indices)
+        return int(self._check(self.lib.az_replay_refresh_from_search(
+            self._h, C.c_void_p(idx.data_ptr()), int(idx.numel()), C.c_void_p(roots_buf.data_ptr()), int(roots_buf.numel()),
+            C.c_void_p(lines_buf.data_ptr()) if lines_buf is not None else None, int(lines_buf.numel()) if lines_buf is not None else 0,
+            _lib.SEARCH_REFRESH_MODES[value_target], self._stream())))
 
     def read_unique(self):
         n = self.stats()["n_unique"]
@@ -184,16 +202,18 @@ class Reanalyser:
 
     One Analyzer (a manual_moves engine and an evaluator) lives across the calls.  A chunk goes gather_states ->
     load_states_device -> search_device -> refresh_from_roots: positions and roots stay in HBM, the host sees the 16-byte
-    headers of the root export and the refreshed count.  value_target: "soft-Z", "A0C" or None (pi only) - the targets that
-    are functions of a search root; further keywords go to the Analyzer (c_puct, use_dirichlet, eval_precision, ...).
+    headers of the exports and the refreshed count.  value_target: "soft-Z", "A0C" or None (pi only) - the targets that
+    are functions of a search root - or "off-policy" (A0GB, the value at the end of the most-visited line): the chunk's
+    greedy lines are then exported too (Analyzer.lines_device, one kernel, depth 1: the value does not depend on it) and the
+    refresh goes through refresh_from_search.  Further keywords go to the Analyzer (c_puct, use_dirichlet, eval_precision, ...).
     The store must not change between the calls made here (it is the caller's between reanalyse() calls); the next dedupe()
     averages a refreshed first occurrence with its stale duplicates, as the reference's aliasing does."""
 
     def __init__(self, store, policy_fn, n_slots, n_playouts, value_target="soft-Z", **kwargs):
         from .analysis import Analyzer
-        if value_target not in _lib.REFRESH_MODES:
-            raise ValueError("value_target must be one of %s: on-policy needs the game's outcome, off-policy a tree descent"
-                             % sorted(map(str, _lib.REFRESH_MODES)))
+        if value_target not in _lib.SEARCH_REFRESH_MODES:
+            raise ValueError("value_target must be one of %s: on-policy needs the game's outcome"
+                             % sorted(map(str, _lib.SEARCH_REFRESH_MODES)))
         self.store, self.value_target = store, value_target
         kwargs.setdefault("device", store.device)
         kwargs.setdefault("seed", 0)  # (keys the root noise only, and that is off unless use_dirichlet is asked for)
@@ -231,7 +251,11 @@ class Reanalyser:
             chunk = idx[first:first + self.n_slots]
             bb, ply = self.store.gather_states(chunk)
             an.load_states_device(bb, ply, seed=an.seed + first)
-            done += self.store.refresh_from_roots(chunk, an.search_device(), self.value_target)
+            roots = an.search_device()
+            if self.value_target == "off-policy":
+                done += self.store.refresh_from_search(chunk, roots, an.lines_device(1), self.value_target)
+            else:
+                done += self.store.refresh_from_roots(chunk, roots, self.value_target)
         return done
 
 

@@ -43,7 +43,7 @@ def main():
                          "for a generation's longest game, and games in flight go on under each updated net")
     ap.add_argument("--reanalyse", type=int, default=0,
                     help="before training, search N sampled positions of the de-duplicated buffer again with the current net and "
-                         "overwrite their pi (and z, when --backup is soft-Z or A0C: the targets a search root alone gives)")
+                         "overwrite their pi (and z, when --backup is soft-Z, A0C or off-policy: the targets a search gives)")
     a = ap.parse_args()
 
     dev = torch.device("cuda:0")
@@ -82,7 +82,7 @@ def main():
         if a.reanalyse:                                                    # stale targets of older generations -> the current net's
             if reanalyser is None:
                 reanalyser = replay.Reanalyser(store, net, min(a.reanalyse, 4096), a.playouts,
-                                               value_target=a.backup if a.backup in ("soft-Z", "A0C") else None,
+                                               value_target=a.backup if a.backup in ("soft-Z", "A0C", "off-policy") else None,
                                                eval_precision=a.precision)
             else:
                 reanalyser.set_evaluator(net)

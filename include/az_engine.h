@@ -348,6 +348,27 @@ int az_engine_stream_take_device(az_engine *e, int64_t n_games, void *dev_buf, i
 int64_t az_engine_roots_device_bytes(const az_engine *e);
 int az_engine_export_roots_device(az_engine *e, void *dev_buf, int64_t bytes, void *stream);
 
+/* Every slot's GREEDY LINE - the principal variation of its finished search, and the reference's off-policy value target
+ * A0GB at its end (game_utils.py:181-194) - packed into ONE caller-owned device buffer by one kernel, a wave per slot:
+ * asynchronous on `stream`, no host synchronisation, usable inside a captured graph, for every engine the root export accepts.
+ * The walk: at a node with children value = node.Q and the next node is the child with the largest N + P (-99.0 for a child
+ * with N = 0; the first maximum = the lowest action wins), the sign flips at every step; a final leaf with N > 0 gives
+ * value = leaf.Q and one more flip; the target is value * sign.  It is the function self-play's off-policy backup runs.
+ * Layout, G = n_slots, D = max_depth (1 <= D <= max_plies), every array 16-byte aligned (and so must dev_buf be), in order:
+ *   header i32[4] | game_id i32[G] | phase i32[G] | ply i32[G] | depth i32[G] | leaf_n u32[G] | value f64[G] |
+ *   line_action i32[G][D] | line_n u32[G][D] | line_q f64[G][D]
+ * header = { number of slots whose phase is 5 or 0, G, D, az_progress.error_flags }, as in the root export.  depth = the full
+ * length of the line in moves (it may exceed D: the arrays then hold the first D steps), leaf_n = N of the node it ends at,
+ * value = the target over the FULL line whatever D is.  line_*[d] = action, N and Q of the node reached after d + 1 moves: the
+ * node records' own values, no arithmetic.  Rows beyond min(depth, D) hold action -1 and zeros.  A slot whose phase is not 5
+ * (a search still running, an idle slot) gets depth = -1, value = 0 and empty rows.  A line cannot be longer than
+ * max_plies - ply + 1 moves: a walk that reaches that bound, or leaves the slot's pool, ends there with depth = -2 (a corrupt
+ * tree; the rows hold the steps taken).
+ * AZ_E_INVALID, and nothing is written: max_depth outside [1, max_plies], bytes < az_engine_lines_device_bytes, dev_buf not
+ * 16-byte aligned. */
+int64_t az_engine_lines_device_bytes(const az_engine *e, int32_t max_depth);
+int az_engine_export_lines_device(az_engine *e, int32_t max_depth, void *dev_buf, int64_t bytes, void *stream);
+
 /* debug / parity read-back of one slot's root (mcts.root.{N,Q,children[a].{N,Q,P}}, read by
  * game_utils.py:30-31,174,178,183-193).  Arrays sized max_children.  Returns n_children or <0.
  * Synchronises the device. */

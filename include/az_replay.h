@@ -50,14 +50,16 @@ typedef struct az_replay_stats {
 } az_replay_stats;
 
 #define AZ_REPLAY_FAULT_KEY_COLLISION 1u /* remove_duplicates met two different histories with one 64-bit key */
-#define AZ_REPLAY_FAULT_BAD_INDEX 2u     /* az_replay_sample / az_replay_gather_states / az_replay_refresh_from_roots were given an
-                                            index outside [0, n_unique) */
-#define AZ_REPLAY_FAULT_ROOT_MISMATCH 4u /* az_replay_refresh_from_roots skipped a root that does not belong to its example */
+#define AZ_REPLAY_FAULT_BAD_INDEX 2u     /* az_replay_sample / az_replay_gather_states / az_replay_refresh_from_roots /
+                                            az_replay_refresh_from_search were given an index outside [0, n_unique) */
+#define AZ_REPLAY_FAULT_ROOT_MISMATCH 4u /* a refresh skipped a root (or a root and line pair) that does not belong to its example */
 
-/* value_mode of az_replay_refresh_from_roots: the value targets that are functions of a search root alone */
+/* value_mode of the refresh entries.  0-2 are functions of a search root alone (az_replay_refresh_from_roots takes these);
+ * 3 needs the greedy line as well (az_replay_refresh_from_search with a line export). */
 #define AZ_REFRESH_KEEP_Z 0 /* pi only */
 #define AZ_REFRESH_SOFT_Z 1 /* z = -root.Q                                         game_utils.py:172-174 */
 #define AZ_REFRESH_A0C 2    /* z = max(child.Q if child.N > 0 else -99.0)          game_utils.py:177-179 */
+#define AZ_REFRESH_OFF_POLICY 3 /* z = the value at the end of the most-visited line (A0GB)  game_utils.py:181-194 */
 
 int az_replay_create(const az_replay_config *cfg, az_replay **out);
 int az_replay_destroy(az_replay *r);
@@ -103,8 +105,8 @@ int az_replay_sample(az_replay *r, const int64_t *indices, int32_t batch, uint64
 
 /*
  * Reanalyse: search stored positions again with the current network and overwrite their targets, device to device:
- *   az_replay_gather_states -> az_engine_set_start_states_device -> reset, tick -> az_engine_export_roots_device ->
- *   az_replay_refresh_from_roots
+ *   az_replay_gather_states -> az_engine_set_start_states_device -> reset, tick -> az_engine_export_roots_device
+ *   (+ az_engine_export_lines_device) -> az_replay_refresh_from_roots (az_replay_refresh_from_search)
  * The store counts its appends, dedupes and capacity changes (an epoch); az_replay_gather_states records the epoch and a
  * refresh under another one returns AZ_E_STATE: after a FIFO eviction or a new dedupe the indices may name other records.
  *
@@ -123,12 +125,24 @@ int az_replay_sample(az_replay *r, const int64_t *indices, int32_t batch, uint64
  *
  * Duplicate indices in one call: the result of the lowest slot is stored (without root noise all of them are the same bits).
  * The next az_replay_dedupe averages a refreshed first occurrence with its stale duplicates, exactly as the reference's
- * aliasing treats any first occurrence (train.py:191-197).  On-policy targets (the game's outcome) and off-policy targets
- * (a descent of the tree) are not functions of a root and cannot be refreshed this way.
+ * aliasing treats any first occurrence (train.py:191-197).  The off-policy target (A0GB) is no function of a root: given
+ * AZ_REFRESH_OFF_POLICY this entry returns AZ_E_INVALID and leaves the store untouched - use az_replay_refresh_from_search.
+ * On-policy targets (the game's outcome) cannot be refreshed by a search at all.
+ *
+ * az_replay_refresh_from_search: the same refresh (the same claim, write and release kernels) with the greedy lines of the
+ * searches at hand: lines = a device buffer (16-byte aligned) in the layout of az_engine_export_lines_device, exported from the
+ * same engine at the same moment as roots; any max_depth will do, the value does not depend on it.  With lines == NULL and
+ * value_mode 0, 1 or 2 it is az_replay_refresh_from_roots (lines is read in AZ_REFRESH_OFF_POLICY only).
+ * AZ_REFRESH_OFF_POLICY requires lines: its header is validated against lines_bytes and against the roots' slot count before
+ * anything is written (AZ_E_INVALID; AZ_E_DEVICE when either header carries engine fault flags); pi comes from the roots as in
+ * the other modes and z = value[slot].  A slot whose game_id, ply or phase in lines differs from the roots', or whose
+ * depth < 0, is skipped and raises AZ_REPLAY_FAULT_ROOT_MISMATCH.  The epoch refusal (AZ_E_STATE) is that of the other entry.
  */
 int az_replay_gather_states(az_replay *r, const int64_t *indices, int64_t n, uint64_t *bb_out, int32_t *ply_out, void *stream);
 int64_t az_replay_refresh_from_roots(az_replay *r, const int64_t *indices, int64_t n, const void *roots, int64_t roots_bytes,
                                      int32_t value_mode, void *stream);
+int64_t az_replay_refresh_from_search(az_replay *r, const int64_t *indices, int64_t n, const void *roots, int64_t roots_bytes,
+                                      const void *lines, int64_t lines_bytes, int32_t value_mode, void *stream);
 
 /* Counters and device fault flags; synchronises the device.  Returns AZ_E_DEVICE when a fault flag is set; the flags are
  * reported ONCE (cleared by this call).  az_replay_dedupe clears AZ_REPLAY_FAULT_KEY_COLLISION when it starts, leaves a group

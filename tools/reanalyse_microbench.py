@@ -29,7 +29,7 @@ ap.add_argument("--slots", type=int, default=0, help="engine slots (default: min
 ap.add_argument("--precision", default="f32x", choices=["f16", "f32x"])
 ap.add_argument("--min-ply", type=int, default=6)
 ap.add_argument("--max-ply", type=int, default=30)
-ap.add_argument("--value-target", default="soft-Z", choices=["soft-Z", "A0C", "none"])
+ap.add_argument("--value-target", default="soft-Z", choices=["soft-Z", "A0C", "off-policy", "none"])
 ap.add_argument("--check-every", type=int, default=16)
 ap.add_argument("--repeat", type=int, default=3)
 ap.add_argument("--seed", type=int, default=0)
