@@ -151,6 +151,7 @@ PROTOTYPES = [
     ("az_replay_append_device", C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp]),
     ("az_replay_dedupe", C.c_int, [_vp, _vp]),
     ("az_replay_sample", C.c_int, [_vp, _vp, C.c_int32, C.c_uint64, _vp, _vp, _vp, _vp]),
+    ("az_replay_sample_sym", C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_uint64, _vp, _vp, _vp, _vp]),
     ("az_replay_gather_states", C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp]),
     ("az_replay_refresh_from_roots", C.c_int64, [_vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp]),
     ("az_replay_refresh_from_search", C.c_int64, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, _vp]),

@@ -246,6 +246,50 @@ template <int GAME> AZ_HD int az_check_state(const AzState &s, const AzGeom &g, 
     return az_count_legal<GAME>(s, g) > 0 ? AZ_STATE_OK : AZ_STATE_NO_MOVE;
 }
 
+// Left-right mirror of the board: column c <-> cols-1-c.  Both games are symmetric under it (az_apply, the legality helpers
+// and az_check_state commute with the two functions below), so the mirror image of a training example is the mirrored
+// position with the mirrored policy and the same value.  Both are involutions; bits that are no cell stay where they are,
+// so az_check_state gives a mirrored state the rule it gives the original.
+//   connect_four : the 7-bit column groups swap (a column's sentinel bit travels with it: clear stays clear)
+//   breakthrough : every row of C bits is reversed
+template <int GAME> AZ_HD uint64_t az_mirror_bits(uint64_t b, const AzGeom &g) {
+    if (GAME == AZG_CONNECT_FOUR) {
+        const uint64_t c = 0x7Full;
+        return (b & ~((1ull << 49) - 1)) | ((b & c) << 42) | ((b & (c << 7)) << 28) | ((b & (c << 14)) << 14) | (b & (c << 21)) |
+               ((b >> 14) & (c << 14)) | ((b >> 28) & (c << 7)) | ((b >> 42) & c);
+    } else {
+        const uint64_t col0 = g.board_mask & ~g.not_col0; // column 0 of every row
+        uint64_t out = b & ~g.board_mask;
+        for (int c = 0; c < g.cols; c++) { // column c moves by cols-1-2c bits
+            uint64_t v = b & (col0 << c);
+            int sh = g.cols - 1 - 2 * c;
+            out |= sh >= 0 ? v << sh : v >> -sh;
+        }
+        return out;
+    }
+}
+template <int GAME> AZ_HD AzState az_mirror_state(const AzState &s, const AzGeom &g) {
+    AzState m;
+    m.bb0 = az_mirror_bits<GAME>(s.bb0, g);
+    m.bb1 = az_mirror_bits<GAME>(s.bb1, g);
+    m.ply = s.ply;
+    return m;
+}
+// The action that does to az_mirror_state(s) what `action` does to s; action in [0, A).
+//   connect_four : a -> 6 - a
+//   breakthrough : the cell is mirrored, dc is negated inside the side's own three directions (az_apply: dc = dir % 3 - 1),
+//                  the capture bit is kept
+// (no run-time division: the replay store's mirrored gather calls this per element.  / 6 and % 6 are multiplies; the row of a
+// cell is counted from the row starts at or below it.)
+template <int GAME> AZ_HD int az_mirror_action(int action, const AzGeom &g) {
+    if (GAME == AZG_CONNECT_FOUR) return 6 - action;
+    const int h = action >> 1, cell = h / 6, d = h % 6;
+    const uint64_t col0 = g.board_mask & ~g.not_col0;
+    const int row = az_popc64(col0 & ((2ull << cell) - 1)) - 1, col = cell - row * g.cols;
+    const int mcell = cell + g.cols - 1 - 2 * col, md = d >= 3 ? 8 - d : 2 - d;
+    return ((mcell * 6 + md) << 1) | (action & 1);
+}
+
 // Observation element idx of state_to_board's (C+1,H,W) tensor (network.py:9-18), C = 3.
 //   connect_four planes: 0 empty, 1 player-1 stones, 2 player-0 stones, 3 current player
 //   breakthrough planes: 0 black,  1 white,          2 empty,           3 current player

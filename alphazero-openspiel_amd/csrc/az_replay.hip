@@ -673,13 +673,8 @@ __global__ void replay_sample_kernel(SampleArgs a) {
     if (threadIdx.x == 0) a.zo[b] = (float)a.z[phys];
 }
 
-extern "C" int az_replay_sample(az_replay *r, const int64_t *indices, int32_t batch, uint64_t seed, float *x, float *pi,
-                                float *z, void *stream) {
-    if (!r || !x || !pi || !z || batch < 1) return AZ_E_INVALID;
-    if (r->n_unique < 1) {
-        r->err = "az_replay_sample before az_replay_dedupe (or the buffer is empty)";
-        return AZ_E_STATE;
-    }
+// What both sampling entries hand their kernel; takes the call's number from the store's one counter.
+static SampleArgs sample_args(az_replay *r, const int64_t *indices, int32_t batch, uint64_t seed, float *x, float *pi, float *z) {
     SampleArgs a;
     a.geom = r->geom;
     a.game = r->cfg.game;
@@ -702,8 +697,67 @@ extern "C" int az_replay_sample(az_replay *r, const int64_t *indices, int32_t ba
     a.pio = pi;
     a.zo = z;
     a.faults = r->faults;
+    return a;
+}
+
+extern "C" int az_replay_sample(az_replay *r, const int64_t *indices, int32_t batch, uint64_t seed, float *x, float *pi,
+                                float *z, void *stream) {
+    if (!r || !x || !pi || !z || batch < 1) return AZ_E_INVALID;
+    if (r->n_unique < 1) {
+        r->err = "az_replay_sample before az_replay_dedupe (or the buffer is empty)";
+        return AZ_E_STATE;
+    }
+    SampleArgs a = sample_args(r, indices, batch, seed, x, pi, z);
     RCHK(r, hipSetDevice(r->cfg.device));
     hipLaunchKernelGGL(replay_sample_kernel, dim3(batch), dim3(128), 0, (hipStream_t)stream, a);
+    RCHK(r, hipGetLastError());
+    return AZ_OK;
+}
+
+// The same gather with a left-right mirror bit per row (az_mirror_state / az_mirror_action): one workgroup per row, the row's
+// example chosen exactly as replay_sample_kernel chooses it.  GAME is a template argument here: the mirror of the position is
+// formed once per thread and the action mirror runs per element.
+template <int GAME> __global__ void replay_sample_sym_kernel(SampleArgs a, const uint8_t *flips) {
+    int b = blockIdx.x;
+    const uint64_t h = mix64(mix64(a.seed, a.call), (uint64_t)b); // the row's index word, as in replay_sample_kernel
+    long long u = a.indices ? a.indices[b] : (long long)__umul64hi(h, (uint64_t)a.n_unique);
+    if (u < 0 || u >= a.n_unique) { // as replay_sample_kernel, whatever the row's flip
+        if (threadIdx.x == 0) {
+            atomicOr(a.faults, AZ_REPLAY_FAULT_BAD_INDEX);
+            a.zo[b] = __builtin_nanf("");
+        }
+        for (int i = threadIdx.x; i < a.planes_elems; i += blockDim.x) a.x[(size_t)b * a.planes_elems + i] = __builtin_nanf("");
+        for (int i = threadIdx.x; i < a.A; i += blockDim.x) a.pio[(size_t)b * a.A + i] = __builtin_nanf("");
+        return;
+    }
+    // the coin is the top bit of a further splitmix step over the index word: no bit of the word that picks the example decides it
+    const bool flip = flips ? flips[b] != 0 : (mix64(h, 0x6A09E667F3BCC908ull) >> 63) != 0; // (block-uniform)
+    long long phys = (a.head + a.unique[u]) % a.cap;
+    AzState s;
+    s.bb0 = a.bb0[phys];
+    s.bb1 = a.bb1[phys];
+    s.ply = a.ply[phys];
+    if (flip) s = az_mirror_state<GAME>(s, a.geom);
+    for (int i = threadIdx.x; i < a.planes_elems; i += blockDim.x) a.x[(size_t)b * a.planes_elems + i] = az_obs_elem<GAME>(s, a.geom, i);
+    // pi_out[mirror(i)] = pi[i], written as pi_out[i] = pi[mirror(i)] (an involution): the stores stay in order
+    for (int i = threadIdx.x; i < a.A; i += blockDim.x)
+        a.pio[(size_t)b * a.A + i] = (float)a.pi[(size_t)phys * a.A + (flip ? az_mirror_action<GAME>(i, a.geom) : i)];
+    if (threadIdx.x == 0) a.zo[b] = (float)a.z[phys];
+}
+
+extern "C" int az_replay_sample_sym(az_replay *r, const int64_t *indices, const uint8_t *flips, int32_t batch, uint64_t seed, float *x,
+                                    float *pi, float *z, void *stream) {
+    if (!r || !x || !pi || !z || batch < 1) return AZ_E_INVALID;
+    if (r->n_unique < 1) {
+        r->err = "az_replay_sample_sym before az_replay_dedupe (or the buffer is empty)";
+        return AZ_E_STATE;
+    }
+    SampleArgs a = sample_args(r, indices, batch, seed, x, pi, z);
+    RCHK(r, hipSetDevice(r->cfg.device));
+    if (a.game == AZG_CONNECT_FOUR)
+        hipLaunchKernelGGL(replay_sample_sym_kernel<AZG_CONNECT_FOUR>, dim3(batch), dim3(128), 0, (hipStream_t)stream, a, flips);
+    else
+        hipLaunchKernelGGL(replay_sample_sym_kernel<AZG_BREAKTHROUGH>, dim3(batch), dim3(128), 0, (hipStream_t)stream, a, flips);
     RCHK(r, hipGetLastError());
     return AZ_OK;
 }

@@ -102,22 +102,48 @@ class DeviceReplay:
         self._check(self.lib.az_replay_stats_get(self._h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in _lib.AzReplayStats._fields_}
 
-    def sample(self, batch, indices=None, seed=0):
+    def sample(self, batch, indices=None, seed=0, mirror=None, out=None):
         """-> (x [B,4,H,W], pi [B,A], z [B]) float32 device tensors.  indices: int64 tensor/array of positions in the
-        de-duplicated list (the reference's np.random.randint draw); None = drawn on the device."""
-        x = torch.empty((batch,) + self.obs_shape, dtype=torch.float32, device=self.device)
-        pi = torch.empty((batch, self.A), dtype=torch.float32, device=self.device)
-        z = torch.empty((batch,), dtype=torch.float32, device=self.device)
-        idx_ptr = None
+        de-duplicated list (the reference's np.random.randint draw); None = drawn on the device.
+        mirror: None / False = every row as it was played; True = each row left-right mirrored or not by a coin drawn on the
+        device from (seed, call counter, row); a bool / uint8 tensor or array of length batch = row b mirrored where mirror[b]
+        (az_replay_sample_sym: the mirrored position, the mirrored policy, the same value).
+        out: (x, pi, z) contiguous float32 tensors of those shapes on the store's device, filled and returned instead of
+        newly allocated ones; anything else is refused."""
+        batch = int(batch)
+        shapes = ((batch,) + self.obs_shape, (batch, self.A), (batch,))
+        if out is None:
+            out = tuple(torch.empty(sh, dtype=torch.float32, device=self.device) for sh in shapes)
+        else:
+            out = tuple(out)
+            if len(out) != 3:
+                raise ValueError("out must be the three tensors (x, pi, z)")
+            for name, t, sh in zip(("x", "pi", "z"), out, shapes):
+                if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != sh or t.device != self.device \
+                        or not t.is_contiguous():
+                    raise ValueError("out: %s must be a contiguous float32 tensor of shape %s on %s" % (name, sh, self.device))
+        x, pi, z = out
+        keep = []  # tensors made here that the kernel reads
+        idx_ptr = flip_ptr = None
         if indices is not None:
             idx = torch.as_tensor(np.asarray(indices, dtype=np.int64)).to(self.device)
             assert idx.numel() == batch
             idx_ptr = C.c_void_p(idx.data_ptr())
-        self._check(self.lib.az_replay_sample(self._h, idx_ptr, int(batch), int(seed) & (2 ** 64 - 1),
-                                              C.c_void_p(x.data_ptr()), C.c_void_p(pi.data_ptr()),
-                                              C.c_void_p(z.data_ptr()), self._stream()))
-        if indices is not None:
-            torch.cuda.current_stream(self.device).synchronize()  # idx must outlive the kernel
+            keep.append(idx)
+        ptrs = (C.c_void_p(x.data_ptr()), C.c_void_p(pi.data_ptr()), C.c_void_p(z.data_ptr()), self._stream())
+        if mirror is None or (isinstance(mirror, (bool, np.bool_)) and not mirror):
+            self._check(self.lib.az_replay_sample(self._h, idx_ptr, batch, int(seed) & (2 ** 64 - 1), *ptrs))
+        else:
+            if not isinstance(mirror, (bool, np.bool_)):
+                flips = mirror if torch.is_tensor(mirror) else torch.as_tensor(np.asarray(mirror))
+                if flips.dtype not in (torch.bool, torch.uint8) or flips.numel() != batch:
+                    raise ValueError("mirror must be None, a bool, or a bool / uint8 tensor or array of length batch")
+                flips = flips.reshape(-1).to(device=self.device, dtype=torch.uint8).contiguous()
+                flip_ptr = C.c_void_p(flips.data_ptr())
+                keep.append(flips)
+            self._check(self.lib.az_replay_sample_sym(self._h, idx_ptr, flip_ptr, batch, int(seed) & (2 ** 64 - 1), *ptrs))
+        if keep:
+            torch.cuda.current_stream(self.device).synchronize()  # they must outlive the kernel
         return x, pi, z
 
     # ------------------------------------------------------------------ reanalyse (include/az_replay.h)
@@ -279,10 +305,12 @@ def make_optimizer(net, lr=0.001):
 class GraphedNetStep:
     """net_step captured once as a HIP graph (forward, loss, backward, Adam with capturable state) and replayed per batch:
     the update is the same sequence of kernels as `net_step`, minus ~100 kernel launches' worth of host latency per step.
-    Usage: step = GraphedNetStep(net, batch, replay); loss_p, loss_v = step(seed)  (samples on the device, then replays)."""
+    Usage: step = GraphedNetStep(net, batch, replay); loss_p, loss_v = step(seed)  (samples on the device, straight into the
+    graph's input tensors, then replays).  mirror=True: every batch is sampled with device-drawn left-right flips
+    (DeviceReplay.sample(mirror=True)), which doubles the distinct positions the net sees at no cost in search or memory."""
 
-    def __init__(self, net, batch, store, lr=0.001):
-        self.net, self.store, self.batch = net, store, batch
+    def __init__(self, net, batch, store, lr=0.001, mirror=False):
+        self.net, self.store, self.batch, self.mirror = net, store, batch, bool(mirror)
         dev = store.device
         self.opt = torch.optim.Adam(net.parameters(), lr=lr, weight_decay=0.0001, capturable=True)
         self.x = torch.zeros((batch,) + store.obs_shape, dtype=torch.float32, device=dev)
@@ -324,9 +352,6 @@ class GraphedNetStep:
         self.loss_v.copy_(lv.detach())
 
     def __call__(self, seed=0, indices=None):
-        x, pi, z = self.store.sample(self.batch, indices=indices, seed=seed)
-        self.x.copy_(x)
-        self.pi.copy_(pi)
-        self.z.copy_(z)
+        self.store.sample(self.batch, indices=indices, seed=seed, mirror=self.mirror, out=(self.x, self.pi, self.z))
         self.graph.replay()
         return self.loss_p, self.loss_v

@@ -44,6 +44,9 @@ def main():
     ap.add_argument("--reanalyse", type=int, default=0,
                     help="before training, search N sampled positions of the de-duplicated buffer again with the current net and "
                          "overwrite their pi (and z, when --backup is soft-Z, A0C or off-policy: the targets a search gives)")
+    ap.add_argument("--mirror", action="store_true",
+                    help="train on left-right mirrored batches: every sampled position is flipped or not by a coin drawn on the "
+                         "device (both games are symmetric under it; the policy is mirrored with the board)")
     a = ap.parse_args()
 
     dev = torch.device("cuda:0")
@@ -91,7 +94,7 @@ def main():
                   flush=True)
         net.train()
         if trainer is None:
-            trainer = replay.GraphedNetStep(net, a.batch_size, store)
+            trainer = replay.GraphedNetStep(net, a.batch_size, store, mirror=a.mirror)
         t1 = time.perf_counter()
         lp = lv = 0.0
         for i in range(a.batches):

@@ -103,6 +103,20 @@ int az_replay_dedupe(az_replay *r, void *stream);
 int az_replay_sample(az_replay *r, const int64_t *indices, int32_t batch, uint64_t seed, float *x, float *pi,
                      float *z, void *stream);
 
+/* az_replay_sample with a left-right mirror bit per row (no counterpart in the reference).  Both games are symmetric under
+ * column c -> cols-1-c: the mirror image of a position has the mirrored policy and the same value (az_mirror_state /
+ * az_mirror_action in csrc/az_games.h), so a row may be handed to the net in either orientation.  `flips` (device uint8
+ * [batch], 0 = as stored, non-zero = mirrored) chooses per row; pass NULL to draw the bits on the device, one fair coin per
+ * row over (seed, call counter, row) that goes through a splitmix64 step of its own after the word that picks the example, so
+ * the orientation says nothing about the index.  A mirrored row holds the observation of the mirrored position, pi with
+ * pi_out[mirror(a)] = pi[a], and z as stored; a row that is not mirrored holds exactly what az_replay_sample writes.  indices,
+ * the device draw for indices == NULL (with equal seed and call counter both entries pick the same examples), the NaN row and
+ * AZ_REPLAY_FAULT_BAD_INDEX for an index outside [0, n_unique), and AZ_E_STATE before a dedupe are az_replay_sample's; the two
+ * entries count their calls in one counter.  Asynchronous on `stream`; nothing is read back, so with device `indices` and
+ * `flips` a call can be captured into a graph (a replay then repeats the call number it was captured with). */
+int az_replay_sample_sym(az_replay *r, const int64_t *indices, const uint8_t *flips, int32_t batch, uint64_t seed, float *x,
+                         float *pi, float *z, void *stream);
+
 /*
  * Reanalyse: search stored positions again with the current network and overwrite their targets, device to device:
  *   az_replay_gather_states -> az_engine_set_start_states_device -> reset, tick -> az_engine_export_roots_device
