@@ -676,7 +676,8 @@ __device__ __forceinline__ bool finish_game_take_next(const Params &p, int g, in
     if (lane == 0) {
         const size_t row = rec_row(p, sr.gid);
         p.rec_ret0[row] = ret0;
-        p.rec_len[row] = sr.rs.ply - p.start.ply; // (stream mode: a non-zero length marks the row finished - read after the launch)
+        // plies played from the game's OWN start (a table of starts is read by game id, here at the game's end - not per tick)
+        p.rec_len[row] = sr.rs.ply - (p.starts ? p.starts[sr.gid].ply : p.start.ply); // (stream mode: a non-zero length marks the row finished - read after the launch)
         __threadfence(); // records before the done-count
         atomicAdd(p.games_done, 1ull);
     }
@@ -690,12 +691,14 @@ __device__ __forceinline__ bool finish_game_take_next(const Params &p, int g, in
     }
     return true;
 }
-// Rule of the tree a game's first search runs on, when the agent is the first to move from p.start.  A bot that keeps its
-// tree calls update_root on its (leaf) constructor root before its first search when the history is long enough - self-play
-// bots with >= 1 move played (alphazerobot.py:57-59), the others with >= 2 (:62-64) - which installs MCTS.use_puct.
-__device__ __forceinline__ int start_rule(const Params &p) {
+// Rule of the tree a game's first search runs on, when the agent is the first to move from the game's start position (start_ply:
+// p.start.ply, or the game's own entry of the start table - the callers have it in sr.rs.ply, which take_next_game has just
+// loaded).  A bot that keeps its tree calls update_root on its (leaf) constructor root before its first search when the history
+// is long enough - self-play bots with >= 1 move played (alphazerobot.py:57-59), the others with >= 2 (:62-64) - which installs
+// MCTS.use_puct.  Decided per game: with a table, a game from ply 0 starts under PUCT beside one from ply 3 under select_rule.
+__device__ __forceinline__ int start_rule(const Params &p, int start_ply) {
     if (!p.keep_tree || p.manual_moves) return AZ_SELECT_PUCT;
-    return p.start.ply >= (p.arena_agent == AZ_ARENA_SELF_PLAY ? 1 : 2) ? p.select_rule : AZ_SELECT_PUCT;
+    return start_ply >= (p.arena_agent == AZ_ARENA_SELF_PLAY ? 1 : 2) ? p.select_rule : AZ_SELECT_PUCT;
 }
 // arena: the agent plays side gid & 1; is it the OPPONENT's turn in state s of game gid?
 __device__ __forceinline__ bool opponent_to_move(const Params &p, int gid, const AzState &s) {
@@ -744,7 +747,7 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
 
     if (ph == PH_IDLE) { // stream mode: the slot finished a game while no id could be handed out; the limit may have risen since
         if (!take_next_game(p, lane, sr)) return; // (nothing was changed: still idle, game id -1)
-        reroot(p, g, sr, t, -1, true, start_rule(p), lane, fault, st_compact);
+        reroot(p, g, sr, t, -1, true, start_rule(p, sr.rs.ply), lane, fault, st_compact);
         ph = p.use_dirichlet ? PH_NEED_ROOT : PH_RUN;
     }
 
@@ -774,7 +777,7 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
                 release_rsv();
                 return;
             }
-            reroot(p, g, sr, t, -1, true, start_rule(p), lane, fault, st_compact);
+            reroot(p, g, sr, t, -1, true, start_rule(p, sr.rs.ply), lane, fault, st_compact);
             ph = opponent_to_move(p, sr.gid, sr.rs) ? PH_OPPONENT : (p.use_dirichlet ? PH_NEED_ROOT : PH_RUN);
         } else { // a leaf root here = the agent's first step of the game: update_root runs only with >= 2 moves played
             reroot(p, g, sr, t, sel, !p.keep_tree, (p.keep_tree && sr.rs.ply >= 2) ? p.select_rule : AZ_SELECT_PUCT, lane, fault,
@@ -882,7 +885,7 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
                 release_rsv();
                 return;
             }
-            reroot(p, g, sr, t, -1, true, start_rule(p), lane, fault, st_compact);
+            reroot(p, g, sr, t, -1, true, start_rule(p, sr.rs.ply), lane, fault, st_compact);
         } else {
             reroot(p, g, sr, t, sel, !p.keep_tree, p.keep_tree ? p.select_rule : AZ_SELECT_PUCT, lane, fault, st_compact, rsv_k, rsv_np);
             if (sr.pool == rsv_np) {
@@ -1459,13 +1462,12 @@ __global__ void az_reset_kernel(Params p) {
                  : ((p.arena_agent != AZ_ARENA_SELF_PLAY && ((p.start.ply ^ g ^ p.arena_flip) & 1)) ? PH_OPPONENT
                                                                                        : (p.use_dirichlet ? PH_NEED_ROOT : PH_RUN));
     p.gid[g] = active ? g : -1;
-    const AzState s0 = (p.starts && active) ? p.starts[g] : p.start; // game id g (manual_moves engines only: see the phase above)
+    const AzState s0 = (p.starts && active) ? p.starts[g] : p.start; // game id g (a table is never set on an arena engine: the phase above)
     p.bb0[g] = s0.bb0;
     p.bb1[g] = s0.bb1;
     p.ply[g] = s0.ply;
     p.sims[g] = 0;
-    p.which[g] = g | (!p.keep_tree || p.manual_moves ? AZ_SELECT_PUCT
-                      : (p.start.ply >= (p.arena_agent == AZ_ARENA_SELF_PLAY ? 1 : 2) ? p.select_rule : AZ_SELECT_PUCT)) << 30; // pool g, start_rule
+    p.which[g] = g | start_rule(p, s0.ply) << 30; // pool g, the start rule of game g (its own start ply when a table is set)
     for (int k = g; k < p.n_spare; k += p.G) p.spare[k] = p.G + k; // the spare pools follow the slots' own
     if (g == 0) p.cjob_count[0] = 1, p.cjob_count[1] = p.cjob_count[2] = 0; // epoch 1: no row has been seen in it
     p.cj_job[g] = 0;
@@ -1538,6 +1540,8 @@ extern "C" int az_engine_destroy(az_engine *e) {
     if (e->d_us) (void)hipFree(e->d_us);
     if (e->d_actions) (void)hipFree(e->d_actions);
     if (e->d_starts) (void)hipFree(e->d_starts);
+    if (e->d_start_ply) (void)hipFree(e->d_start_ply);
+    if (e->d_start_keys) (void)hipFree(e->d_start_keys);
     if (e->d_start_check) (void)hipFree(e->d_start_check);
     delete e;
     return AZ_OK;
@@ -1778,7 +1782,7 @@ extern "C" int az_engine_reset(az_engine *e, uint64_t seed, int64_t n_games, voi
         return AZ_E_INVALID;
     }
     if (e->p.starts && n_games > e->starts_n) {
-        e->err = "n_games exceeds the games given to az_engine_set_start_positions";
+        e->err = "n_games exceeds the games given to az_engine_set_start_positions / az_engine_set_game_starts (the start table)";
         return AZ_E_INVALID;
     }
     return reset_common(e, seed, n_games, false, stream);
@@ -1794,7 +1798,7 @@ extern "C" int az_engine_stream_begin(az_engine *e, uint64_t seed, void *stream)
     else if (e->cfg.manual_moves) why = "a manual_moves engine (its slots are re-armed by the caller)";
     else if (e->cfg.rng_mode == AZ_RNG_INJECTED) why = "rng_mode = AZ_RNG_INJECTED (injected draws are tables indexed by game id)";
     else if (e->has_prefix) why = "a start prefix is set (az_engine_set_start_prefix)";
-    else if (e->p.starts) why = "a start-position table is set (az_engine_set_start_positions)";
+    else if (e->p.starts) why = "a start-position table is set (az_engine_set_start_positions / az_engine_set_game_starts)";
     else if (e->cfg.max_games < e->cfg.n_slots) why = "max_games < n_slots (slots 0..G-1 start ids 0..G-1, each needs a row of the ring)";
     if (why) {
         e->err = std::string("az_engine_stream_begin is for plain self-play engines: refused for ") + why;
@@ -1993,6 +1997,7 @@ extern "C" int az_engine_set_start_prefix(az_engine *e, const int32_t *actions, 
     e->has_prefix = n > 0;
     e->p.starts = nullptr; // one prefix for every game again
     e->starts_n = 0;
+    e->game_starts = e->starts_keyed = false;
     e->reset_done = false; // caller must reset again so that slots pick the new start up
     return AZ_OK;
 }
@@ -2001,11 +2006,18 @@ extern "C" int az_engine_set_start_prefix(az_engine *e, const int32_t *actions, 
 static int starts_reserve(az_engine *e, int64_t n_games) {
     if (n_games <= e->starts_cap) return AZ_OK;
     if (e->d_starts) (void)hipFree(e->d_starts);
+    if (e->d_start_ply) (void)hipFree(e->d_start_ply);
+    if (e->d_start_keys) (void)hipFree(e->d_start_keys);
     e->d_starts = nullptr;
+    e->d_start_ply = nullptr;
+    e->d_start_keys = nullptr;
     e->starts_cap = 0;
     e->p.starts = nullptr;
     e->starts_n = 0;
+    e->game_starts = e->starts_keyed = false;
     HIPCHK(e, hipMalloc((void **)&e->d_starts, (size_t)n_games * sizeof(AzState)));
+    HIPCHK(e, hipMalloc((void **)&e->d_start_ply, (size_t)n_games * sizeof(int32_t)));
+    HIPCHK(e, hipMalloc((void **)&e->d_start_keys, (size_t)n_games * 2 * sizeof(uint64_t)));
     e->starts_cap = n_games;
     return AZ_OK;
 }
@@ -2015,6 +2027,7 @@ static void starts_in_force(az_engine *e, int64_t n_games) {
     else az_init_state<AZG_BREAKTHROUGH>(e->p.start, e->p.geom);
     e->p.starts = e->d_starts;
     e->starts_n = n_games;
+    e->game_starts = e->starts_keyed = false; // (the game-start setters raise them after this)
     e->reset_done = false; // caller must reset again so that slots pick the new starts up
 }
 
@@ -2080,6 +2093,37 @@ __global__ void az_fill_start_states_kernel(const uint64_t *bb, const int32_t *p
     tab[i] = s;
 }
 
+// The validity pass of both device-form start entries: every state through az_check_state on the device, the lowest offending
+// index named in az_last_error as "<what>: game <i>: <rule>".  plies_out (may be null) receives a host copy of ply_dev.
+// Synchronises the device first (the states are written, and nothing reads the table any more) and `st` at the end.
+static int check_start_states_device(az_engine *e, const char *what, const uint64_t *bb_dev, const int32_t *ply_dev, int64_t n_games,
+                                     hipStream_t st, std::vector<int32_t> *plies_out) {
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, hipDeviceSynchronize());
+    if (!e->d_start_check) HIPCHK(e, hipMalloc((void **)&e->d_start_check, sizeof(unsigned long long)));
+    unsigned long long res = START_CHECK_CLEAN;
+    HIPCHK(e, hipMemcpyAsync(e->d_start_check, &res, sizeof res, hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)((n_games + 255) / 256)), block(256);
+    if (e->cfg.game == AZ_GAME_CONNECT_FOUR)
+        hipLaunchKernelGGL(az_check_start_states_kernel<AZG_CONNECT_FOUR>, grid, block, 0, st, e->p.geom, e->p.max_plies, bb_dev, ply_dev,
+                           (long long)n_games, e->d_start_check);
+    else
+        hipLaunchKernelGGL(az_check_start_states_kernel<AZG_BREAKTHROUGH>, grid, block, 0, st, e->p.geom, e->p.max_plies, bb_dev, ply_dev,
+                           (long long)n_games, e->d_start_check);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipMemcpyAsync(&res, e->d_start_check, sizeof res, hipMemcpyDeviceToHost, st));
+    if (plies_out) {
+        plies_out->resize((size_t)n_games);
+        HIPCHK(e, hipMemcpyAsync(plies_out->data(), ply_dev, (size_t)n_games * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(e, hipStreamSynchronize(st));
+    if (res != START_CHECK_CLEAN) {
+        e->err = std::string(what) + ": game " + std::to_string(res >> 8) + ": " + az_state_rule_name((int)(res & 0xFF));
+        return AZ_E_INVALID;
+    }
+    return AZ_OK;
+}
+
 extern "C" int az_engine_set_start_states_device(az_engine *e, const uint64_t *bb_dev, const int32_t *ply_dev, int64_t n_games,
                                                  void *stream) {
     if (!e) return AZ_E_INVALID;
@@ -2093,32 +2137,150 @@ extern "C" int az_engine_set_start_states_device(az_engine *e, const uint64_t *b
         return AZ_E_INVALID;
     }
     hipStream_t st = (hipStream_t)stream;
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    HIPCHK(e, hipDeviceSynchronize()); // the states are written, and a reset of the previous chunk has read the table
-    if (!e->d_start_check) HIPCHK(e, hipMalloc((void **)&e->d_start_check, sizeof(unsigned long long)));
-    unsigned long long res = START_CHECK_CLEAN;
-    HIPCHK(e, hipMemcpyAsync(e->d_start_check, &res, sizeof res, hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)((n_games + 255) / 256)), block(256);
-    if (e->cfg.game == AZ_GAME_CONNECT_FOUR)
-        hipLaunchKernelGGL(az_check_start_states_kernel<AZG_CONNECT_FOUR>, grid, block, 0, st, e->p.geom, e->p.max_plies, bb_dev, ply_dev,
-                           (long long)n_games, e->d_start_check);
-    else
-        hipLaunchKernelGGL(az_check_start_states_kernel<AZG_BREAKTHROUGH>, grid, block, 0, st, e->p.geom, e->p.max_plies, bb_dev, ply_dev,
-                           (long long)n_games, e->d_start_check);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(&res, e->d_start_check, sizeof res, hipMemcpyDeviceToHost, st));
-    HIPCHK(e, hipStreamSynchronize(st));
-    if (res != START_CHECK_CLEAN) {
-        e->err = "az_engine_set_start_states_device: game " + std::to_string(res >> 8) + ": " + az_state_rule_name((int)(res & 0xFF));
-        return AZ_E_INVALID;
-    }
-    int rc = starts_reserve(e, n_games);
+    int rc = check_start_states_device(e, "az_engine_set_start_states_device", bb_dev, ply_dev, n_games, st, nullptr);
     if (rc != AZ_OK) return rc;
+    rc = starts_reserve(e, n_games);
+    if (rc != AZ_OK) return rc;
+    const dim3 grid((unsigned)((n_games + 255) / 256)), block(256);
     hipLaunchKernelGGL(az_fill_start_states_kernel, grid, block, 0, st, bb_dev, ply_dev, (long long)n_games, e->d_starts);
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipStreamSynchronize(st));
     starts_in_force(e, n_games);
     return AZ_OK;
+}
+
+// ---- a start position per game for SELF-PLAY (include/az_engine.h: az_engine_set_game_starts) --------------------------------
+// The same table as above, on a plain self-play engine, with each game's start ply and history key pair beside it.
+static int game_starts_refusal(az_engine *e, const char *what) {
+    const char *why = nullptr;
+    if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) why = "an arena engine (game id i fixes the agent's side from ONE start ply)";
+    else if (e->cfg.manual_moves) why = "a manual_moves engine (az_engine_set_start_positions / az_engine_set_start_states_device are its entries)";
+    else if (e->streaming) why = "an engine in stream mode (az_engine_stream_begin: game ids are open-ended, a table is not)";
+    if (!why) return AZ_OK;
+    e->err = std::string(what) + " is for plain self-play engines in a closed generation: refused for " + why;
+    return AZ_E_INVALID;
+}
+
+extern "C" int az_engine_set_game_starts(az_engine *e, const int32_t *actions, const int32_t *lengths, int64_t stride, int64_t n_games) {
+    if (!e) return AZ_E_INVALID;
+    if (game_starts_refusal(e, "az_engine_set_game_starts")) return AZ_E_INVALID;
+    if (!lengths || n_games < 1 || n_games > e->cfg.max_games || stride < 0) {
+        e->err = "az_engine_set_game_starts: n_games must be in [1, max_games], lengths non-null, stride >= 0";
+        return AZ_E_INVALID;
+    }
+    std::vector<AzState> tab((size_t)n_games);
+    std::vector<int32_t> plies((size_t)n_games);
+    std::vector<uint64_t> keys((size_t)n_games * 2);
+    AzState init;
+    if (e->cfg.game == AZ_GAME_CONNECT_FOUR) az_init_state<AZG_CONNECT_FOUR>(init, e->p.geom);
+    else az_init_state<AZG_BREAKTHROUGH>(init, e->p.geom);
+    for (int64_t i = 0; i < n_games; i++) {
+        const int32_t n = lengths[i];
+        if (n < 0 || n > stride || (n > 0 && !actions)) {
+            e->err = "az_engine_set_game_starts: game " + std::to_string(i) + ": prefix length " + std::to_string(n) + " outside [0, stride]";
+            return AZ_E_INVALID;
+        }
+        const int32_t *pre = n > 0 ? actions + i * stride : nullptr;
+        int bad = replay_prefix(e, pre, n, tab[(size_t)i]);
+        if (bad) {
+            e->err = "az_engine_set_game_starts: game " + std::to_string(i) + (bad == 1 ? ": illegal prefix action" : ": prefix ends the game");
+            return AZ_E_INVALID;
+        }
+        // the pair of an ordinary game from the initial position after these moves (az_keychain.h): the j-th move steps with index j
+        AzKeyPair k = az_key_seed(init.ply, init.bb0, init.bb1);
+        for (int32_t j = 0; j < n; j++) k = az_key_step(k, (uint32_t)pre[j], j + 1);
+        plies[(size_t)i] = tab[(size_t)i].ply;
+        keys[(size_t)i * 2] = k.key;
+        keys[(size_t)i * 2 + 1] = k.key2;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, hipDeviceSynchronize()); // a generation that still plays, or an append, may be reading the table
+    int rc = starts_reserve(e, n_games);
+    if (rc != AZ_OK) return rc;
+    HIPCHK(e, hipMemcpy(e->d_starts, tab.data(), (size_t)n_games * sizeof(AzState), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(e->d_start_ply, plies.data(), (size_t)n_games * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(e, hipMemcpy(e->d_start_keys, keys.data(), (size_t)n_games * 2 * sizeof(uint64_t), hipMemcpyHostToDevice));
+    starts_in_force(e, n_games);
+    e->has_prefix = false;
+    e->h_start_ply = plies;
+    e->game_starts = e->starts_keyed = true;
+    return AZ_OK;
+}
+
+// keys == null: every game's pair is its start state's own seed (what an ordinary game starting there carries at its first ply)
+__global__ void az_fill_game_starts_kernel(const uint64_t *bb, const int32_t *ply, const uint64_t *keys, long long n, AzState *tab,
+                                           int32_t *ply_tab, uint64_t *key_tab) {
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    AzState s;
+    s.bb0 = bb[2 * i];
+    s.bb1 = bb[2 * i + 1];
+    s.ply = ply[i];
+    tab[i] = s;
+    ply_tab[i] = s.ply;
+    AzKeyPair k;
+    if (keys) k.key = keys[2 * i], k.key2 = keys[2 * i + 1];
+    else k = az_key_seed(s.ply, s.bb0, s.bb1);
+    key_tab[2 * i] = k.key;
+    key_tab[2 * i + 1] = k.key2;
+}
+
+extern "C" int az_engine_set_game_starts_device(az_engine *e, const uint64_t *bb_dev, const int32_t *ply_dev, const uint64_t *keys_dev,
+                                                int64_t n_games, void *stream) {
+    if (!e) return AZ_E_INVALID;
+    if (game_starts_refusal(e, "az_engine_set_game_starts_device")) return AZ_E_INVALID;
+    if (!bb_dev || !ply_dev || n_games < 1 || n_games > e->cfg.max_games) {
+        e->err = "az_engine_set_game_starts_device: n_games must be in [1, max_games], bb_dev and ply_dev non-null";
+        return AZ_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<int32_t> plies;
+    int rc = check_start_states_device(e, "az_engine_set_game_starts_device", bb_dev, ply_dev, n_games, st, &plies);
+    if (rc != AZ_OK) return rc;
+    rc = starts_reserve(e, n_games);
+    if (rc != AZ_OK) return rc;
+    const dim3 grid((unsigned)((n_games + 255) / 256)), block(256);
+    hipLaunchKernelGGL(az_fill_game_starts_kernel, grid, block, 0, st, bb_dev, ply_dev, keys_dev, (long long)n_games, e->d_starts,
+                       e->d_start_ply, e->d_start_keys);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipStreamSynchronize(st));
+    starts_in_force(e, n_games);
+    e->has_prefix = false;
+    e->h_start_ply = plies;
+    e->game_starts = true;
+    e->starts_keyed = keys_dev != nullptr;
+    return AZ_OK;
+}
+
+// table == null: the uniform start of every game, and its seed pair
+__global__ void az_game_starts_out_kernel(AzState start, const int32_t *ply_tab, const uint64_t *key_tab, long long n, int32_t *ply_out,
+                                          uint64_t *keys_out) {
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    ply_out[i] = ply_tab ? ply_tab[i] : start.ply;
+    if (!keys_out) return;
+    if (key_tab) {
+        keys_out[2 * i] = key_tab[2 * i];
+        keys_out[2 * i + 1] = key_tab[2 * i + 1];
+    } else {
+        const AzKeyPair k = az_key_seed(start.ply, start.bb0, start.bb1);
+        keys_out[2 * i] = k.key;
+        keys_out[2 * i + 1] = k.key2;
+    }
+}
+
+extern "C" int az_engine_game_starts_device(az_engine *e, int32_t *ply_out_dev, uint64_t *keys_out_dev, int64_t n_games, void *stream) {
+    if (!e) return AZ_E_INVALID;
+    if (!ply_out_dev || n_games < 1 || n_games > e->cfg.max_games || (e->game_starts && n_games > e->starts_n)) {
+        e->err = "az_engine_game_starts_device: ply_out_dev non-null, n_games in [1, max_games] and within the table";
+        return AZ_E_INVALID;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    hipLaunchKernelGGL(az_game_starts_out_kernel, dim3((unsigned)((n_games + 255) / 256)), dim3(256), 0, (hipStream_t)stream, e->p.start,
+                       e->game_starts ? e->d_start_ply : nullptr, e->game_starts ? e->d_start_keys : nullptr, (long long)n_games,
+                       ply_out_dev, keys_out_dev);
+    HIPCHK(e, hipGetLastError());
+    return e->game_starts && e->starts_keyed ? 1 : 0;
 }
 
 // `defer`: compactions of this launch are handed to its own extra workgroups (compact_jobs; whole-engine launches only: the job
@@ -2430,10 +2592,11 @@ extern "C" int az_engine_export(az_engine *e, az_example_view *out, void *stream
     HIPCHK(e, hipMemcpy(e->h_value.data(), e->p.rec_value, ng * mp * sizeof(double), hipMemcpyDeviceToHost));
     if (e->cfg.backup == AZ_BACKUP_ON_POLICY) // game_utils.py:200-204
         for (size_t g = 0; g < ng; g++) {
+            const int p0 = e->game_starts ? e->h_start_ply[g] : e->p.start.ply; // the game's own start ply when a table is set
             double reward = (double)e->h_ret0[g];
-            if (e->p.start.ply & 1) reward = -reward; // first recorded ply is player 1's
+            if (p0 & 1) reward = -reward; // first recorded ply is player 1's
             for (int i = 0; i < e->h_len[g]; i++) {
-                e->h_value[g * mp + (size_t)e->p.start.ply + i] = reward;
+                e->h_value[g * mp + (size_t)p0 + i] = reward;
                 reward *= -1;
             }
         }
@@ -2461,10 +2624,13 @@ static void export_offsets(size_t n, size_t mp, size_t mc, size_t off[9]) {
     for (int i = 0; i < 8; i++) off[i + 1] = off[i] + ((sizes[i] + 15) & ~(size_t)15);
 }
 
-__global__ void fill_on_policy_values_kernel(const int *len, const float *ret0, double *value, int n_games, int max_plies, int start_ply) {
+// start_plies: the games' own start plies (a game-start table), or null = start_ply for every game
+__global__ void fill_on_policy_values_kernel(const int *len, const float *ret0, double *value, int n_games, int max_plies, int start_ply,
+                                             const int32_t *start_plies) {
     long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; // game_utils.py:200-204: z_i = returns()[0] * (-1)^i
     int g = (int)(t / max_plies), i = (int)(t % max_plies);
     if (g >= n_games || i >= len[g]) return;
+    if (start_plies) start_ply = start_plies[g];
     double z = (double)ret0[g];
     value[(size_t)g * max_plies + start_ply + i] = ((start_ply + i) & 1) ? -z : z;
 }
@@ -2491,7 +2657,7 @@ extern "C" int az_engine_export_device(az_engine *e, void *dev_buf, int64_t byte
     if (e->cfg.backup == AZ_BACKUP_ON_POLICY) {
         long long threads = (long long)n * (long long)mp;
         hipLaunchKernelGGL(fill_on_policy_values_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, e->p.rec_len,
-                           e->p.rec_ret0, e->p.rec_value, (int)n, (int)mp, e->p.start.ply);
+                           e->p.rec_ret0, e->p.rec_value, (int)n, (int)mp, e->p.start.ply, e->game_starts ? e->d_start_ply : nullptr);
         HIPCHK(e, hipGetLastError());
     }
     char *b = (char *)dev_buf;

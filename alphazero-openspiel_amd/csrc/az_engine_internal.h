@@ -8,6 +8,7 @@
 
 #include "../../include/az_engine.h"
 #include "az_games.h"
+#include "az_keychain.h"
 
 #define NONE32 0xFFFFFFFFu
 
@@ -98,8 +99,9 @@ struct Params {
     uint8_t *rec_nchild;
     uint32_t *rec_child_visits;
     double *rec_value;
-    // start position per GAME ID (az_engine_set_start_positions / az_engine_set_start_states_device; manual_moves engines only):
-    // null = every game starts from `start`
+    // start position per GAME ID: null = every game starts from `start`.  Set for manual_moves engines by
+    // az_engine_set_start_positions / az_engine_set_start_states_device, for plain self-play engines by az_engine_set_game_starts /
+    // az_engine_set_game_starts_device.  Read by game id at reset, at take-next and at game end only - never per tick.
     const AzState *starts;
 };
 
@@ -119,6 +121,14 @@ struct az_engine {
     AzState *d_starts = nullptr; // the table behind p.starts (kept across az_engine_set_start_positions calls)
     int64_t starts_cap = 0, starts_n = 0;
     unsigned long long *d_start_check = nullptr; // result record of az_engine_set_start_states_device's validity pass
+    // az_engine_set_game_starts / az_engine_set_game_starts_device (plain self-play engines): the table is a game-start table.
+    // Next to each AzState of d_starts: the game's start ply as a plain int32 (what the replay append indexes with) and its
+    // history key pair (az_keychain.h).  keyed: the pairs were GIVEN (a prefix's chain, or the caller's keys_dev) and the games'
+    // key chains step by absolute ply; otherwise they are the start states' own seeds and the games are keyed as ordinary ones.
+    bool game_starts = false, starts_keyed = false;
+    int32_t *d_start_ply = nullptr;
+    uint64_t *d_start_keys = nullptr; // u64 [starts_cap][2]
+    std::vector<int32_t> h_start_ply; // host copy for az_engine_export's on-policy fill
     bool rows_mapped = false; // az_engine_compact_rows has been called since the last reset
     int rows_live = 0;
     bool streaming = false;   // az_engine_stream_begin since the last az_engine_reset

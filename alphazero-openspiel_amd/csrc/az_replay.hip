@@ -181,12 +181,7 @@ extern "C" int az_replay_stats_get(az_replay *r, az_replay_stats *out) {
 }
 
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t mix64(uint64_t h, uint64_t v) { // splitmix64 step over (h, v)
-    uint64_t z = h + 0x9E3779B97F4A7C15ull * (v + 1);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+__device__ __forceinline__ uint64_t mix64(uint64_t h, uint64_t v) { return az_key_mix64(h, v); } // (the device index draws use it too)
 
 struct AppendArgs {
     // source (one generation of games, layout of az_example_view / the engine's record store), device pointers
@@ -199,6 +194,11 @@ struct AppendArgs {
     const double *value;
     const long long *dst_first; // [n_src_games] logical index of the game's first example, -1 = skip
     int n_src_games, max_plies, maxc, start_ply, A, on_policy;
+    // a start per GAME (az_engine_set_game_starts, az_replay_append_device_starts): start_plies [n_src_games] replaces start_ply
+    // when non-null; start_keys u64 [n_src_games][2] non-null = the games carry GIVEN history key pairs and their chains step by
+    // absolute ply (az_keychain.h), null = every game is keyed from its start state as an ordinary game
+    const int32_t *start_plies;
+    const uint64_t *start_keys;
     long long cap, head;
     PwPlan pw;
     uint64_t *key, *key2, *bb0, *bb1;
@@ -265,14 +265,15 @@ __global__ void replay_append_kernel(AppendArgs a) {
     int len = a.game_len[g];
     if (first < 0 || i >= len) return;
     long long dst = (a.head + first + i) % a.cap;
-    size_t src = (size_t)g * a.max_plies + a.start_ply + i;
+    const int sp = a.start_plies ? a.start_plies[g] : a.start_ply;
+    size_t src = (size_t)g * a.max_plies + sp + i;
     a.bb0[dst] = a.states[src * 2];
     a.bb1[dst] = a.states[src * 2 + 1];
-    a.ply[dst] = a.start_ply + i;
+    a.ply[dst] = sp + i;
     double zz = a.value[src];
-    if (a.on_policy) { // game_utils.py:200-204: z_i = returns()[0] * (-1)^i
+    if (a.on_policy) { // game_utils.py:200-204: z_i = returns()[0] * (-1)^i, i the ABSOLUTE ply
         zz = (double)a.game_ret0[g];
-        if ((a.start_ply + i) & 1) zz = -zz;
+        if ((sp + i) & 1) zz = -zz;
     }
     a.z[dst] = zz;
     int nc = a.nchild[src] < a.maxc ? a.nchild[src] : a.maxc;
@@ -286,19 +287,25 @@ __global__ void replay_keys_kernel(AppendArgs a) {
     long long first = a.dst_first[g];
     if (first < 0) return;
     int len = a.game_len[g];
-    size_t s0 = (size_t)g * a.max_plies + a.start_ply;
-    uint64_t h = mix64(0x243F6A8885A308D3ull, (uint64_t)a.start_ply);
-    h = mix64(h, a.states[s0 * 2]);
-    h = mix64(h, a.states[s0 * 2 + 1]); // start position (identical for all games of a run)
-    // second, independent chain (other seed, other per-step tweak): the reference keys on the EXACT information-state
-    // string (train.py:177); (key, key2) together are a 128-bit fingerprint of the history, and the segment pass
-    // raises AZ_REPLAY_FAULT_KEY_COLLISION if two members of one `key` segment differ in key2, ply or position
-    uint64_t h2 = mix64(0x13198A2E03707344ull ^ (uint64_t)a.start_ply, a.states[s0 * 2] + 0x9E3779B97F4A7C15ull * a.states[s0 * 2 + 1]);
+    const int sp = a.start_plies ? a.start_plies[g] : a.start_ply;
+    size_t s0 = (size_t)g * a.max_plies + sp;
+    // The two chains (az_keychain.h): the reference keys on the EXACT information-state string (train.py:177); (key, key2)
+    // together are a 128-bit fingerprint of the history, and the segment pass raises AZ_REPLAY_FAULT_KEY_COLLISION if two members
+    // of one `key` segment differ in key2, ply or position.  An ordinary game is seeded from its start position (identical for
+    // all games of a run) and steps with index 1, 2, ...; a game with a given pair continues that pair's history, by absolute ply.
+    AzKeyPair k = {0, 0};
+    int base = 0;
+    if (a.start_keys) {
+        k.key = a.start_keys[2 * (size_t)g];
+        k.key2 = a.start_keys[2 * (size_t)g + 1];
+        base = sp;
+    } else if (len > 0) { // (a game without a recorded ply has no start state to read)
+        k = az_key_seed(sp, a.states[s0 * 2], a.states[s0 * 2 + 1]);
+    }
     for (int i = 0; i < len; i++) {
-        a.key[(a.head + first + i) % a.cap] = h;
-        a.key2[(a.head + first + i) % a.cap] = h2;
-        h = mix64(h, (uint64_t)a.move[s0 + i]);
-        h2 = mix64(h2 ^ 0xA4093822299F31D0ull, ((uint64_t)a.move[s0 + i] << 20) | (uint64_t)(i + 1));
+        a.key[(a.head + first + i) % a.cap] = k.key;
+        a.key2[(a.head + first + i) % a.cap] = k.key2;
+        k = az_key_step(k, (uint32_t)a.move[s0 + i], base + i + 1);
     }
 }
 
@@ -390,6 +397,10 @@ extern "C" int az_replay_append_engine(az_replay *r, az_engine *e, void *stream)
     a.max_plies = e->p.max_plies;
     a.maxc = e->p.maxc;
     a.start_ply = e->p.start.ply;
+    if (e->game_starts) { // a start per game: its own start ply and, when the table carries given pairs, its own key pair
+        a.start_plies = e->d_start_ply;
+        a.start_keys = e->starts_keyed ? e->d_start_keys : nullptr;
+    }
     a.on_policy = e->cfg.backup == AZ_BACKUP_ON_POLICY;
     return append_common(r, a, lens, st);
 }
@@ -462,13 +473,9 @@ extern "C" int az_replay_append_host(az_replay *r, const az_example_view *v, int
     return append_common(r, a, lens, st);
 }
 
-extern "C" int az_replay_append_device(az_replay *r, const void *dev_buf, int64_t n_games, int32_t start_ply, void *stream) {
-    if (!r || !dev_buf || n_games < 1 || start_ply < 0 || start_ply > r->max_plies) {
-        if (r) r->err = "bad device export (null buffer, n_games < 1 or start_ply outside [0, max_plies])";
-        return AZ_E_INVALID;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    RCHK(r, hipSetDevice(r->cfg.device));
+// The packed layout of az_engine_export_device (n_games games, the store's board geometry) as the source arrays of an append:
+// the ONE place the replay store spells that layout out.  on_policy = 0: az_engine_export_device has filled those targets in.
+static AppendArgs packed_export_args(const az_replay *r, const void *dev_buf, int64_t n_games) {
     size_t ng = (size_t)n_games, mp = (size_t)r->max_plies, mc = (size_t)r->maxc;
     const size_t sizes[8] = {ng * 4, ng * 4, ng * mp * 16, ng * mp * 2, ng * mp, ng * mp * mc * 2, ng * mp * mc * 4, ng * mp * 8};
     size_t off[9] = {0};
@@ -487,14 +494,91 @@ extern "C" int az_replay_append_device(az_replay *r, const void *dev_buf, int64_
     a.n_src_games = (int)ng;
     a.max_plies = (int)mp;
     a.maxc = (int)mc;
+    return a;
+}
+
+extern "C" int az_replay_append_device(az_replay *r, const void *dev_buf, int64_t n_games, int32_t start_ply, void *stream) {
+    if (!r || !dev_buf || n_games < 1 || start_ply < 0 || start_ply > r->max_plies) {
+        if (r) r->err = "bad device export (null buffer, n_games < 1 or start_ply outside [0, max_plies])";
+        return AZ_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    RCHK(r, hipSetDevice(r->cfg.device));
+    size_t ng = (size_t)n_games;
+    AppendArgs a = packed_export_args(r, dev_buf, n_games);
     a.start_ply = start_ply;
-    a.on_policy = 0; // az_engine_export_device has filled the on-policy targets in
     std::vector<int32_t> lens(ng);
     RCHK(r, hipMemcpyAsync(lens.data(), a.game_len, ng * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     RCHK(r, hipStreamSynchronize(st));
     for (size_t g = 0; g < ng; g++) // before any launch: a length outside the record rows would run the kernels off the arrays
         if (!game_len_ok(r, (int64_t)g, lens[g], r->max_plies, start_ply)) return AZ_E_INVALID;
     return append_common(r, a, lens, st);
+}
+
+extern "C" int az_replay_append_device_starts(az_replay *r, const void *dev_buf, int64_t n_games, const int32_t *start_ply_dev,
+                                              const uint64_t *keys_dev, void *stream) {
+    if (!r || !dev_buf || !start_ply_dev || n_games < 1) {
+        if (r) r->err = "bad device export (null buffer, null start_ply_dev or n_games < 1)";
+        return AZ_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    RCHK(r, hipSetDevice(r->cfg.device));
+    size_t ng = (size_t)n_games;
+    AppendArgs a = packed_export_args(r, dev_buf, n_games);
+    a.start_plies = start_ply_dev;
+    a.start_keys = keys_dev;
+    std::vector<int32_t> lens(ng), plies(ng);
+    RCHK(r, hipMemcpyAsync(lens.data(), a.game_len, ng * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    RCHK(r, hipMemcpyAsync(plies.data(), start_ply_dev, ng * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    RCHK(r, hipStreamSynchronize(st));
+    for (size_t g = 0; g < ng; g++) { // before any launch: rows [start_ply, start_ply + len) must lie inside the game's record rows
+        if (plies[g] < 0 || plies[g] > r->max_plies) {
+            r->err = "start_ply[" + std::to_string(g) + "] = " + std::to_string(plies[g]) + " is outside [0, max_plies = " +
+                     std::to_string(r->max_plies) + "]";
+            return AZ_E_INVALID;
+        }
+        if (!game_len_ok(r, (int64_t)g, lens[g], r->max_plies, plies[g])) return AZ_E_INVALID;
+    }
+    return append_common(r, a, lens, st);
+}
+
+// A fork: the positions of az_replay_gather_states with the stored history key pair of each example, the three inputs of
+// az_engine_set_game_starts_device.  Nothing is overwritten later on (a fork APPENDS), so no epoch is recorded.
+__global__ void replay_gather_forks_kernel(const int64_t *indices, long long n, long long n_unique, const int64_t *unique, long long head,
+                                           long long cap, const uint64_t *bb0, const uint64_t *bb1, const int32_t *ply, const uint64_t *key,
+                                           const uint64_t *key2, uint64_t *bb_out, int32_t *ply_out, uint64_t *keys_out,
+                                           unsigned int *faults) {
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    long long u = indices[i];
+    if (u < 0 || u >= n_unique) { // as az_replay_gather_states: a fault flag, and a state no engine accepts
+        atomicOr(faults, AZ_REPLAY_FAULT_BAD_INDEX);
+        bb_out[2 * i] = bb_out[2 * i + 1] = 0;
+        keys_out[2 * i] = keys_out[2 * i + 1] = 0;
+        ply_out[i] = -1;
+        return;
+    }
+    long long phys = (head + unique[u]) % cap;
+    bb_out[2 * i] = bb0[phys];
+    bb_out[2 * i + 1] = bb1[phys];
+    ply_out[i] = ply[phys];
+    keys_out[2 * i] = key[phys];
+    keys_out[2 * i + 1] = key2[phys];
+}
+
+extern "C" int az_replay_gather_forks(az_replay *r, const int64_t *indices, int64_t n, uint64_t *bb_out, int32_t *ply_out,
+                                      uint64_t *keys_out, void *stream) {
+    if (!r || !indices || !bb_out || !ply_out || !keys_out || n < 1) return AZ_E_INVALID;
+    if (r->n_unique < 1) {
+        r->err = "az_replay_gather_forks before az_replay_dedupe (or the buffer is empty)";
+        return AZ_E_STATE;
+    }
+    RCHK(r, hipSetDevice(r->cfg.device));
+    hipLaunchKernelGGL(replay_gather_forks_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, indices,
+                       (long long)n, (long long)r->n_unique, r->unique, (long long)r->head, (long long)r->cap, r->bb0, r->bb1, r->ply, r->key,
+                       r->key2, bb_out, ply_out, keys_out, r->faults);
+    RCHK(r, hipGetLastError());
+    return AZ_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ dedupe

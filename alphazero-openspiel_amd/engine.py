@@ -89,7 +89,8 @@ class SelfPlayEngine:
         self.obs_shape = (z.obs_planes, z.rows, z.cols)
         self.max_plies, self.max_children = z.max_plies, z.max_children
         self.start_history = []
-        self.start_histories = None  # set_start_positions: one history per game
+        self.start_histories = None  # set_start_positions / set_game_starts: one history per game
+        self.game_starts = None      # set_game_starts / set_game_starts_device: int32 array [n] of the games' start plies
         self.n_games = 0
 
     # ------------------------------------------------------------------ plumbing
@@ -131,6 +132,7 @@ class SelfPlayEngine:
         self._check(self.lib.az_engine_set_start_prefix(self._h, arr, len(actions)))
         self.start_history = [int(a) for a in actions]
         self.start_histories = None
+        self.game_starts = None
 
     def set_start_positions(self, histories):
         """A start position per game (manual_moves engines): histories[i] is the action list that leads from the initial
@@ -157,6 +159,48 @@ class SelfPlayEngine:
                                                                self._stream()))
         self.start_history = []
         self.start_histories = None  # the histories are not known: the states came as positions
+
+    def set_game_starts(self, histories):
+        """A start position per game for SELF-PLAY (az_engine_set_game_starts): game i of the next generation starts after the
+        action list histories[i], plays to its end and is recorded like any other game; reset(n <= len(histories)) afterwards.
+        Plain self-play engines only.  An illegal action or a prefix that ends the game raises EngineError naming "game <i>" and
+        an earlier table stays in force.  The games carry the history keys of their prefixes into a replay store; export()
+        then returns "start_ply" as an int32 array and start_histories keeps the prefixes for examples_from_export."""
+        actions, lengths, stride = pack_histories(histories)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.az_engine_set_game_starts(self._h, actions.ctypes.data_as(ip), lengths.ctypes.data_as(ip),
+                                                       stride, len(lengths)))
+        self.start_history = []
+        self.start_histories = [[int(a) for a in h] for h in histories]
+        self.game_starts = lengths.copy()
+
+    def set_game_starts_device(self, bb, ply, keys=None):
+        """The device form of set_game_starts: game i starts from the state (bb[i, 0], bb[i, 1], ply[i]) - tensors as
+        DeviceReplay.gather_forks returns them - and carries the history key pair keys[i] (int64 [n, 2] holding the 64-bit
+        words; None: the games are keyed from their start states, as ordinary games that start there).  Every state is
+        checked on the device; a bad one raises EngineError naming the lowest offending game, and the previous table stays."""
+        n = int(ply.numel())
+        for t, dt, shape in ((bb, torch.int64, (n, 2)), (ply, torch.int32, (n,)), (keys, torch.int64, (n, 2))):
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != self.device or tuple(t.shape) != shape):
+                raise EngineError("expected a contiguous %s %s tensor on %s, got %s %s on %s"
+                                  % (dt, shape, self.device, t.dtype, tuple(t.shape), t.device))
+        self._check(self.lib.az_engine_set_game_starts_device(
+            self._h, C.c_void_p(bb.data_ptr()), C.c_void_p(ply.data_ptr()), C.c_void_p(keys.data_ptr()) if keys is not None else None,
+            n, self._stream()))
+        self.start_history = []
+        self.start_histories = None  # the histories are not known: the states came as positions
+        self.game_starts = ply.cpu().numpy().astype(np.int32)
+
+    def game_starts_device(self, n_games=None):
+        """-> (ply int32 [n], keys int64 [n, 2] or None) device tensors: every game id's start ply and history key pair, what
+        DeviceReplay.append_device(buf, n, start_ply=ply, keys=keys) takes beside export_device().  keys is None when the
+        games carry no given pairs (no table, or set_game_starts_device(keys=None)).  n_games: default the last reset's."""
+        n = int(self.n_games if n_games is None else n_games)
+        ply = torch.empty((n,), dtype=torch.int32, device=self.device)
+        keys = torch.empty((n, 2), dtype=torch.int64, device=self.device)
+        keyed = self._check(self.lib.az_engine_game_starts_device(self._h, C.c_void_p(ply.data_ptr()), C.c_void_p(keys.data_ptr()),
+                                                                  n, self._stream()))
+        return ply, (keys if keyed else None)
 
     def set_injected_rng(self, etas, us, absolute_ply=False):
         """etas: per game, per ply, the Dirichlet draw (ragged lists ok); us: per game, per ply uniforms.  Lists are
@@ -278,7 +322,7 @@ class SelfPlayEngine:
             "child_action": arr(v.child_action, (n, mp, mc), np.uint16),
             "child_visits": arr(v.child_visits, (n, mp, mc), np.uint32),
             "value": arr(v.value, (n, mp), np.float64),
-            "start_ply": len(self.start_history),
+            "start_ply": len(self.start_history) if self.game_starts is None else self.game_starts[:n].copy(),
         }
 
 
@@ -462,12 +506,13 @@ def device_export_layout(n_games, max_plies, max_children):
 
 
 def unpack_device_export(host_bytes, n_games, max_plies, max_children, start_ply=0):
-    """A host copy of a packed device export -> the dict engine.export() returns (arrays are views)."""
+    """A host copy of a packed device export -> the dict engine.export() returns (arrays are views).
+    start_ply: one start ply for every game, or an array [n_games] (a generation with a start per game)."""
     host_bytes = np.ascontiguousarray(host_bytes, dtype=np.uint8)
     layout, total = device_export_layout(n_games, max_plies, max_children)
     if host_bytes.size < total:
         raise ValueError("export buffer holds %d bytes, layout needs %d" % (host_bytes.size, total))
-    ex = {"start_ply": int(start_ply)}
+    ex = {"start_ply": int(start_ply) if np.ndim(start_ply) == 0 else np.asarray(start_ply, dtype=np.int32).reshape(-1)}
     for name, dt, shape, off in layout:
         cnt = int(np.prod(shape)) * np.dtype(dt).itemsize
         ex[name] = host_bytes[off:off + cnt].view(dt).reshape(shape)
@@ -522,11 +567,18 @@ def examples_from_export(game, ex, start_history=()):
     All plies of all games are converted in bulk (one numpy pass for boards, one for pi); what remains per example is
     building its 4-element list."""
     A = game.num_distinct_actions()
-    p0 = int(ex["start_ply"])
     lens = np.asarray(ex["game_len"]).astype(np.int64)
     G = len(lens)
     if G == 0:
         return []
+    # a start per game (SelfPlayEngine.set_game_starts): "start_ply" is an array [G] and start_history a list of G histories
+    p0 = np.asarray(ex["start_ply"]).astype(np.int64).reshape(-1, 1) if np.ndim(ex["start_ply"]) else int(ex["start_ply"])
+    per_game = len(start_history) > 0 and isinstance(start_history[0], (list, tuple, np.ndarray))
+    if np.ndim(ex["start_ply"]) and not per_game:
+        # (after set_game_starts_device the histories are not known - start_histories is None: there are no key strings to build)
+        raise ValueError("a start ply per game needs a start history per game: the key strings are prefix + moves")
+    if per_game and len(start_history) < G:
+        raise ValueError("%d games but %d start histories" % (G, len(start_history)))
     mp = ex["move"].shape[1]
     ply = np.arange(mp)[None, :]
     valid = (ply >= p0) & (ply < p0 + lens[:, None])           # [G, mp], row-major = game by game, ply by ply
@@ -534,10 +586,10 @@ def examples_from_export(game, ex, start_history=()):
     pis = pis_from_visits(ex["child_action"][valid], ex["child_visits"][valid], ex["n_children"][valid], A).tolist()
     values = ex["value"][valid].tolist()
     moves = ex["move"][valid].tolist()
-    prefix = ", ".join(str(int(a)) for a in start_history)
+    prefixes = [", ".join(str(int(a)) for a in h) for h in (start_history if per_game else [start_history])]
     games, k = [], 0
-    for n in lens.tolist():
-        key, plies = prefix, []
+    for g, n in enumerate(lens.tolist()):
+        key, plies = prefixes[g if per_game else 0], []
         for i in range(k, k + n):
             plies.append([key, boards[i], pis[i], values[i]])
             key = (key + ", " if key else "") + str(moves[i])

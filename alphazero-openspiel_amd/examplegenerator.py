@@ -197,6 +197,47 @@ class ExampleGenerator:
         except Exception:
             pass
 
+    def _check_start_positions(self, what):
+        """A start per game is a single-process, closed-generation path: the multi-rank gather and the pools carry one start ply."""
+        if azdist.world_size() > 1:
+            bad = "torch.distributed with world size %d" % azdist.world_size()
+        elif self.n_pools > 1:
+            bad = "n_pools=%d" % self.n_pools
+        elif self.pool_devices is not None:
+            bad = "pool_devices"
+        elif self.continuous:
+            bad = "continuous=True"
+        else:
+            return
+        raise ValueError("%s is not supported with %s: games that start from their own positions are played by ONE engine in "
+                         "a closed generation" % (what, bad))
+
+    def _play_from_starts(self, n_games, histories=None, fork=None, into=None):
+        """One closed generation on one engine whose game i starts after histories[i], or from the stored position fork[1][i]
+        of the DeviceReplay fork[0].  -> the export dict of host arrays (engine.export()) or, with `into`, the number of games
+        appended to that store."""
+        n = int(n_games)
+        n_slots = int(self.n_slots or min(n, 4096))
+        engine = SelfPlayEngine(self.game, n_slots, max_games=n, device=self.device,
+                                seed=self.seed + 1000003 * self._generation, **self._engine_kwargs())
+        evaluator = None
+        try:
+            if fork is not None:
+                engine.set_game_starts_device(*fork[0].gather_forks(fork[1]))
+            else:
+                engine.set_game_starts(histories)
+            evaluator = make_evaluator(self.net, self.device, self.eval_backend, self.eval_precision, n_slots, self.eval_dtype)
+            self.last_progress = run_selfplay(engine, evaluator, n, use_graph=self.use_graph)
+            if into is not None:
+                into.append_engine(engine)
+                out = n
+            else:
+                out = engine.export()
+        finally:
+            close_all(engine, evaluator, drain=True)
+        self._generation += 1
+        return out
+
     def _play_and_gather(self, n_games):
         """This rank's shard of the generation on the HIP engine, then the generation-end exchange on DEVICE buffers.
         -> (gathered uint8 device tensor [world * nbytes], nbytes per rank, games per rank, world, (max_plies, max_children))"""
@@ -235,12 +276,19 @@ class ExampleGenerator:
         self._generation += 1
         return azdist.all_gather_device_exports(buf), buf.numel(), n_local, world, dims
 
-    def generate_examples(self, n_games):
+    def generate_examples(self, n_games, start_positions=None):
         """-> list of games; a game is a list of [info_state_str, board (C+1,H,W) f64, pi list[A], z]
         (examplegenerator.py:164-175, game_utils.py:169,200-204).  With torch.distributed initialised the net is broadcast
         from rank 0, each rank plays int(n_games / world_size) games (remainder dropped like int(n_games / n_pools),
         examplegenerator.py:149), the packed records are all-gathered on the device (RCCL) and every rank returns the
-        same gathered list.  The reference-format lists are built from ONE device-to-host copy of the gathered buffer."""
+        same gathered list.  The reference-format lists are built from ONE device-to-host copy of the gathered buffer.
+        start_positions: a list of at least n_games action lists - game i starts after start_positions[i] (an opening set, a
+        curriculum, endgames) and its keys are the full histories, prefix included.  One process, one engine, a closed
+        generation: ValueError with torch.distributed world > 1, n_pools > 1, pool_devices or continuous=True."""
+        if start_positions is not None:
+            self._check_start_positions("generate_examples(start_positions=...)")
+            histories = self._histories(n_games, start_positions)
+            return examples_from_export(self.game, self._play_from_starts(n_games, histories), histories)
         gathered, nbytes, n_local, world, (mp, mc) = self._play_and_gather(n_games)
         host = gathered.cpu().numpy()
         games = []
@@ -249,9 +297,30 @@ class ExampleGenerator:
             games.extend(examples_from_export(self.game, ex))
         return games
 
-    def generate_into(self, replay, n_games):
+    @staticmethod
+    def _histories(n_games, start_positions):
+        histories = [[int(a) for a in h] for h in start_positions][:int(n_games)]
+        if len(histories) < int(n_games) or int(n_games) < 1:
+            raise ValueError("start_positions holds %d histories, %d games were asked for" % (len(histories), int(n_games)))
+        return histories
+
+    def generate_into(self, replay, n_games, start_positions=None, fork_from=None):
         """The same generation, delivered straight into a DeviceReplay on this rank's GPU (engine -> all-gather -> replay
-        store, records never leave HBM and never become Python lists).  Returns the number of games appended."""
+        store, records never leave HBM and never become Python lists).  Returns the number of games appended.
+        start_positions: as in generate_examples.  fork_from: an int64 tensor / array of n_games indices into the store's
+        de-duplicated list (dedupe() first) - game i is forked off that stored position, store -> engine -> store on the device
+        (replay.Forker keeps an engine across such calls).  Both are single-process, closed-generation paths."""
+        if start_positions is not None and fork_from is not None:
+            raise ValueError("give start_positions or fork_from, not both")
+        if start_positions is not None:
+            self._check_start_positions("generate_into(start_positions=...)")
+            return self._play_from_starts(n_games, self._histories(n_games, start_positions), into=replay)
+        if fork_from is not None:
+            self._check_start_positions("generate_into(fork_from=...)")
+            idx = replay._indices(fork_from)
+            if int(idx.numel()) != int(n_games):
+                raise ValueError("fork_from holds %d indices, %d games were asked for" % (int(idx.numel()), int(n_games)))
+            return self._play_from_starts(n_games, fork=(replay, idx), into=replay)
         gathered, nbytes, n_local, world, _ = self._play_and_gather(n_games)
         for r in range(world):
             replay.append_device(gathered[r * nbytes:(r + 1) * nbytes], n_local)

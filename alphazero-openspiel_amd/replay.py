@@ -63,7 +63,13 @@ class DeviceReplay:
         self._check(self.lib.az_replay_append_engine(self._h, engine._h, self._stream()))
 
     def append_export(self, ex):
-        """Games in the export layout (engine.export() / distributed.unpack_export) from host memory."""
+        """Games in the export layout (engine.export() / distributed.unpack_export) from host memory.  One start ply for
+        every game: the export of a generation with a start per game (SelfPlayEngine.set_game_starts: "start_ply" is an
+        array) is refused - such games carry history keys that a host view does not; append them with append_engine, or with
+        append_device(buf, n, start_ply=ply, keys=keys)."""
+        if np.ndim(ex.get("start_ply", 0)) != 0:
+            raise ValueError("append_export takes one start ply for every game; a generation with a start per game goes "
+                             "through append_engine or append_device(buf, n, start_ply=, keys=)")
         v = _lib.AzExampleView()
         keep = {k: np.ascontiguousarray(ex[k]) for k in ("game_len", "game_ret0", "states", "move", "n_children",
                                                          "child_action", "child_visits", "value")}
@@ -80,17 +86,31 @@ class DeviceReplay:
         v.value = keep["value"].ctypes.data_as(C.POINTER(C.c_double))
         self._check(self.lib.az_replay_append_host(self._h, C.byref(v), int(ex.get("start_ply", 0)), self._stream()))
 
-    def append_device(self, buf, n_games, start_ply=0):
+    def append_device(self, buf, n_games, start_ply=0, keys=None):
         """Games from a packed DEVICE export (engine.export_device(), or one rank's section of the all-gathered buffer):
-        engine -> RCCL all-gather -> replay store with no host copy of the records."""
+        engine -> RCCL all-gather -> replay store with no host copy of the records.
+        start_ply: one start ply for every game, or - a generation with a start per game - an int32 device tensor [n_games],
+        with keys = the games' history key pairs (int64 [n_games, 2]) or None (keyed from their start states): the two tensors
+        SelfPlayEngine.game_starts_device() returns."""
         if buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.device != self.device:
             raise RuntimeError("append_device expects a contiguous uint8 tensor on %s" % (self.device,))
         from .engine import device_export_layout
         need = device_export_layout(n_games, self.game.max_game_length(), self.game.max_children())[1]
         if buf.numel() < need:
             raise RuntimeError("export buffer holds %d bytes, %d games need %d" % (buf.numel(), n_games, need))
-        self._check(self.lib.az_replay_append_device(self._h, C.c_void_p(buf.data_ptr()), int(n_games), int(start_ply),
-                                                     self._stream()))
+        if not torch.is_tensor(start_ply):
+            if keys is not None:
+                raise ValueError("keys go with a start ply per game: give start_ply as an int32 tensor [n_games]")
+            self._check(self.lib.az_replay_append_device(self._h, C.c_void_p(buf.data_ptr()), int(n_games), int(start_ply),
+                                                         self._stream()))
+            return
+        n = int(n_games)
+        for t, dt, shape in ((start_ply, torch.int32, (n,)), (keys, torch.int64, (n, 2))):
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != self.device or tuple(t.shape) != shape):
+                raise RuntimeError("append_device expects a contiguous %s %s tensor on %s" % (dt, shape, self.device))
+        self._check(self.lib.az_replay_append_device_starts(
+            self._h, C.c_void_p(buf.data_ptr()), n, C.c_void_p(start_ply.data_ptr()),
+            C.c_void_p(keys.data_ptr()) if keys is not None else None, self._stream()))
 
     def dedupe(self):
         """Trainer.remove_duplicates over the flattened buffer; returns the number of unique examples."""
@@ -163,6 +183,22 @@ class DeviceReplay:
         self._check(self.lib.az_replay_gather_states(self._h, C.c_void_p(idx.data_ptr()), n, C.c_void_p(bb.data_ptr()),
                                                      C.c_void_p(ply.data_ptr()), self._stream()))
         return bb, ply
+
+    def gather_forks(self, indices):
+        """gather_states plus the stored history key pair of each example -> (bb int64 [n, 2], ply int32 [n], keys int64 [n, 2])
+        device tensors, the arguments of SelfPlayEngine.set_game_starts_device: games forked off these positions carry on the
+        stored histories, so a fork's first example merges with the example it came from at the next dedupe().  Asynchronous;
+        a bad index raises the BAD_INDEX fault flag and gives ply -1.  Nothing is marked for a refresh: a fork appends."""
+        idx = self._indices(indices)
+        n = int(idx.numel())
+        bb = torch.empty((n, 2), dtype=torch.int64, device=self.device)
+        ply = torch.empty((n,), dtype=torch.int32, device=self.device)
+        keys = torch.empty((n, 2), dtype=torch.int64, device=self.device)
+        self._check(self.lib.az_replay_gather_forks(self._h, C.c_void_p(idx.data_ptr()), n, C.c_void_p(bb.data_ptr()),
+                                                    C.c_void_p(ply.data_ptr()), C.c_void_p(keys.data_ptr()), self._stream()))
+        if idx is not indices:
+            torch.cuda.current_stream(self.device).synchronize()  # a copy of the indices made here must outlive the kernel
+        return bb, ply, keys
 
     def refresh_from_roots(self, indices, roots_buf, value_target="soft-Z"):
         """Overwrite the targets of the examples gather_states(indices) named from the finished searches in roots_buf (the packed
@@ -283,6 +319,81 @@ class Reanalyser:
             else:
                 done += self.store.refresh_from_roots(chunk, roots, self.value_target)
         return done
+
+
+class Forker:
+    """Fork new self-play games out of stored positions and append them: the on-policy counterpart of Reanalyser.
+
+        fk = Forker(store, net, n_slots=1024, n_playouts=100)
+        store.dedupe(); fk.fork(n=256, seed=gen)         # 256 games from uniformly drawn stored positions, played to the end
+        fk.set_net(net)                                   # after training: the next call plays with the new weights
+
+    A call goes gather_forks -> set_game_starts_device -> self-play -> append_engine: positions, key pairs and records stay in
+    HBM.  A fork's first example carries the key of the example it came from (include/az_replay.h, the key rule), so the next
+    dedupe() averages the fresh search and outcome with the stored targets; the rest of the game is new data under the stored
+    history.  The stored keys must be history keys (the key rule): games from the initial position, from set_game_starts or from
+    earlier forks are; the games of an engine with ONE shared set_start_prefix of length > 0 are keyed from that prefix's
+    position instead - a fork off such a game still merges with its parent, but when it repeats the parent's next move the next
+    dedupe() meets one `key` with two `key2` and raises the KEY_COLLISION fault.  Do not fork out of such a store.  One engine lives across the calls; further keywords go to it (c_puct, temperature, backup, ...).  Positions are
+    drawn WITH replacement: two forks of one position are two different games (the random stream is keyed by game id)."""
+
+    def __init__(self, store, net, n_slots, n_playouts, eval_backend="fused", eval_precision="f32x", use_graph=False, seed=0,
+                 max_games=None, **kwargs):
+        from .engine import SelfPlayEngine, make_evaluator
+        self.store, self.seed, self.use_graph, self.calls = store, int(seed), bool(use_graph), 0
+        self.eval_backend, self.eval_precision = eval_backend, eval_precision
+        self.engine = SelfPlayEngine(store.game, int(n_slots), n_playouts=int(n_playouts), device=store.device, seed=self.seed,
+                                     max_games=int(max_games if max_games is not None else n_slots), **kwargs)
+        self.evaluator = None
+        try:
+            self.evaluator = make_evaluator(net, store.device, eval_backend, eval_precision, self.engine.G)
+        except Exception:
+            self.engine.close()
+            raise
+        self.last_progress = None
+
+    def set_net(self, net):
+        from .engine import close_all, make_evaluator
+        torch.cuda.synchronize(self.store.device)
+        old, self.evaluator = self.evaluator, make_evaluator(net, self.store.device, self.eval_backend, self.eval_precision,
+                                                             self.engine.G)
+        close_all(old)
+
+    def close(self):
+        from .engine import close_all
+        close_all(self.engine, self.evaluator, drain=True)
+        self.engine = self.evaluator = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def draw(self, n, seed=0):
+        """n indices of the de-duplicated list, uniform with replacement, drawn on the device."""
+        n_unique = self.store.stats()["n_unique"]
+        if n_unique < 1:
+            raise RuntimeError("Forker: the store has no de-duplicated list (dedupe() first)")
+        gen = torch.Generator(device=self.store.device)
+        gen.manual_seed(int(seed))
+        return torch.randint(n_unique, (int(n),), generator=gen, device=self.store.device, dtype=torch.int64)
+
+    def fork(self, n=None, indices=None, seed=None):
+        """Play one game from each position `indices` (default: draw(n, seed)) to its end and append the games -> their number.
+        At most the engine's max_games per call."""
+        from .engine import run_selfplay
+        seed = self.seed + 1000003 * self.calls if seed is None else int(seed)
+        idx = self.draw(n, seed) if indices is None else self.store._indices(indices)
+        n = int(idx.numel())
+        if n < 1 or n > self.engine.sizes.max_games:
+            raise ValueError("fork: %d games asked for, the engine holds 1..%d per call" % (n, self.engine.sizes.max_games))
+        bb, ply, keys = self.store.gather_forks(idx)
+        self.engine.set_game_starts_device(bb, ply, keys)
+        self.last_progress = run_selfplay(self.engine, self.evaluator, n, seed=seed, use_graph=self.use_graph)
+        self.store.append_engine(self.engine)
+        self.calls += 1
+        return n
 
 
 def net_step(net, optimizer, x, pi_target, z_target):

@@ -44,6 +44,9 @@ def main():
     ap.add_argument("--reanalyse", type=int, default=0,
                     help="before training, search N sampled positions of the de-duplicated buffer again with the current net and "
                          "overwrite their pi (and z, when --backup is soft-Z, A0C or off-policy: the targets a search gives)")
+    ap.add_argument("--fork", type=int, default=0,
+                    help="after each generation, fork N more games from uniformly drawn stored positions (played to the end "
+                         "with the current net) and append them: fresh outcomes under old positions, lines the policy left early")
     ap.add_argument("--mirror", action="store_true",
                     help="train on left-right mirrored batches: every sampled position is flipped or not by a coin drawn on the "
                          "device (both games are symmetric under it; the policy is mirrored with the board)")
@@ -55,7 +58,7 @@ def main():
     net = Net(game.information_state_normalized_vector_shape(), game.num_distinct_actions()).to(dev)
     n_buffer, n_buffer_max = 4 * a.games, 40 * a.games                     # train.py:38-41
     store = replay.DeviceReplay(game, max_games=n_buffer_max, device=dev)
-    trainer = reanalyser = None
+    trainer = reanalyser = forker = None
     generator, before = None, {"moves": 0, "sims": 0}
     if a.continuous:
         generator = ExampleGenerator(net, a.game, dev, continuous=True, n_slots=min(a.games, 4096), n_playouts=a.playouts,
@@ -81,6 +84,17 @@ def main():
             n_buffer += a.games
         store.set_capacity(n_buffer)
         n_unique = store.dedupe()
+        if a.fork:                                                         # store -> engine -> store, on the device
+            t_fk = time.perf_counter()
+            if forker is None:
+                forker = replay.Forker(store, net, min(a.fork, 4096), a.playouts, eval_precision=a.precision, use_graph=True,
+                                       max_games=a.fork, backup=a.backup, seed=1000)
+            else:
+                forker.set_net(net)
+            forker.fork(n=a.fork, seed=gen)
+            n_before, n_unique = n_unique, store.dedupe()
+            print("gen %d: forked %d games from %d unique positions in %.2f s -> %d unique" %
+                  (gen, a.fork, n_before, time.perf_counter() - t_fk, n_unique), flush=True)
         t_re = time.perf_counter()
         if a.reanalyse:                                                    # stale targets of older generations -> the current net's
             if reanalyser is None:
@@ -125,6 +139,8 @@ def main():
         generator.close()
     if reanalyser is not None:
         reanalyser.close()
+    if forker is not None:
+        forker.close()
 
 
 if __name__ == "__main__":

@@ -204,8 +204,8 @@ int az_engine_set_start_prefix(az_engine *e, const int32_t *actions, int32_t n);
  * actions[i * stride .. i * stride + lengths[i]) reaches from the initial one (host arrays, copied; 0 <= lengths[i] <= stride).
  * manual_moves engines only - the batched form of MCTS.search(state) for many given states: reset with at most n_games games,
  * tick until every slot has finished its search, read all roots with az_engine_export_roots_device.  Self-play and arena
- * engines keep ONE start ply (the record offset, the value targets, the replay append and the arena's side assignment use it)
- * and return AZ_E_INVALID.  Every prefix is replayed on the host with the game's legality checks: an illegal action, or a
+ * engines return AZ_E_INVALID here: a self-play engine takes its per-game starts, with the record offset, the value targets and
+ * the replay keys that go with them, through az_engine_set_game_starts; an arena engine keeps ONE start ply (side assignment).  Every prefix is replayed on the host with the game's legality checks: an illegal action, or a
  * prefix that ends the game, is refused with AZ_E_INVALID and az_last_error names the index of the offending game; nothing is
  * changed then.  As with az_engine_set_start_prefix the caller resets afterwards.  May be called again on the same engine
  * (the next chunk of positions); it supersedes a single prefix, and az_engine_set_start_prefix clears the table.
@@ -226,6 +226,47 @@ int az_engine_set_start_positions(az_engine *e, const int32_t *actions, const in
  * A bad state -> AZ_E_INVALID, az_last_error names the lowest offending index ("game <i>") and the first rule it breaks;
  * nothing is changed then.  Synchronises the device.  There is no host-state form: host callers give prefixes. */
 int az_engine_set_start_states_device(az_engine *e, const uint64_t *bb_dev, const int32_t *ply_dev, int64_t n_games, void *stream);
+
+/*
+ * A start position per game for SELF-PLAY: a closed generation in which game id i starts from its own position, plays to the
+ * end and is recorded like any other game.  It is what forking games out of the replay store, playing a generation over a list of
+ * openings and the on-policy answer to reanalyse (play a stored position out with today's network) need.
+ *
+ * Plain self-play engines only (arena_agent == AZ_ARENA_SELF_PLAY, manual_moves == 0, not in stream mode): an arena engine, a
+ * manual_moves engine and a streaming engine return AZ_E_INVALID and az_last_error names the reason; az_engine_stream_begin on an
+ * engine with such a table stays refused.  1 <= n_games <= max_games; the caller resets afterwards (az_engine_reset with more
+ * games than the table holds is refused); the table supersedes a single prefix and az_engine_set_start_prefix clears it.
+ *
+ * az_engine_set_game_starts: the arguments of az_engine_set_start_positions.  Every prefix is replayed on the host with the
+ *   legality checks; an illegal action or a prefix that ends the game is refused with AZ_E_INVALID, az_last_error names
+ *   "game <i>", and nothing changes (an earlier table stays in force).
+ * az_engine_set_game_starts_device: the arguments of az_engine_set_start_states_device plus keys_dev (device u64 [n_games][2], or
+ *   NULL).  Every state goes through az_check_state on the device first, as there.  Synchronises the device.
+ *
+ * What differs per game: the row offset of its records (rows stay indexed by ABSOLUTE ply within a game's row, game_len counts the
+ * plies played from the game's own start), the on-policy value fill, and the rule of the game's first tree - a kept tree whose
+ * game starts at ply >= 1 begins under select_rule, one at ply 0 under PUCT (see select_rule above), decided per game and for
+ * every slot that takes a later id mid-run.  Root noise, injected draws and the random streams stay keyed by (seed, game id,
+ * absolute ply): game i of a table engine is, bit for bit, game i of a plain engine with az_engine_set_start_prefix(prefix i)
+ * and the same seed.  The tick kernel reads a game's start from the table at reset, at take-next and at game end only.
+ *
+ * History keys.  Next to each start state the table keeps the game's history key pair (key, key2), the replay store's two chains
+ * (include/az_replay.h, "the key rule"; csrc/az_keychain.h).  The prefix form computes it on the host: the chains of an ordinary
+ * game from the initial position, run over the prefix.  The device form takes keys_dev[i] (what az_replay_gather_forks hands
+ * out); with keys_dev == NULL the table is UNKEYED: a game's pair is the seed the store forms for an ordinary game starting at
+ * that state and ply, and az_replay_append_engine keys the games as it keys such games.
+ *
+ * az_engine_game_starts_device: writes every game id's start ply to ply_out_dev (i32 [n_games]) and, when keys_out_dev is not
+ * NULL, its key pair (u64 [n_games][2]); with no table, the uniform values of the engine's one start.  Asynchronous on `stream`.
+ * The companion of az_engine_export_device (whose layout does not change) for az_replay_append_device_starts.  Returns 1 when
+ * the table carries GIVEN pairs (pass them on as keys_dev there), 0 when it does not (pass NULL), < 0 on error.
+ *
+ * Limits: no opening per game on arena engines, no table in stream mode, and the multi-rank gather carries one start ply.
+ */
+int az_engine_set_game_starts(az_engine *e, const int32_t *actions, const int32_t *lengths, int64_t stride, int64_t n_games);
+int az_engine_set_game_starts_device(az_engine *e, const uint64_t *bb_dev, const int32_t *ply_dev, const uint64_t *keys_dev,
+                                     int64_t n_games, void *stream);
+int az_engine_game_starts_device(az_engine *e, int32_t *ply_out_dev, uint64_t *keys_out_dev, int64_t n_games, void *stream);
 
 /*
  * One tick = MCTS.playout's select + expand + backup (mcts.py:126-153) for all slots, fused with the

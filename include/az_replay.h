@@ -88,6 +88,41 @@ int az_replay_append_host(az_replay *r, const az_example_view *v, int32_t start_
  * on the device.  Synchronises `stream`. */
 int az_replay_append_device(az_replay *r, const void *dev_buf, int64_t n_games, int32_t start_ply, void *stream);
 
+/*
+ * Games that start from their own positions (az_engine_set_game_starts / az_engine_set_game_starts_device).
+ *
+ * THE KEY RULE.  An example is keyed by the history that leads to it, as the reference keys it by the information-state string
+ * (train.py:177).  A game that was given the prefix P and then plays m_1..m_k carries, at its example after m_1..m_j, exactly the
+ * (key, key2) of an ordinary game from the initial position whose history is P + m_1..m_j: its chains start from P's pair and
+ * the second chain's step index is the ABSOLUTE ply (csrc/az_keychain.h).  Hence
+ *   - a fork's first example has the key of the stored example it was forked from, and az_replay_dedupe averages the two in
+ *     buffer order, as the reference averages any two examples with one information-state string;
+ *   - two prefixes that transpose into one position stay apart, as their strings differ;
+ *   - games appended without a table - no prefix, or the one shared az_engine_set_start_prefix - keep the keys they always had,
+ *     bit for bit: seeded from their start state, stepping with the index 1, 2, ... from there.  A shared prefix of length > 0
+ *     is therefore NOT the history P + ... of the rule, and a store that holds such games must not be forked: a fork still merges
+ *     with its parent, but `key` carries no step index, so a fork that repeats the parent's next move produces the parent
+ *     continuation's `key` with another `key2`, and the next az_replay_dedupe raises AZ_REPLAY_FAULT_KEY_COLLISION (AZ_E_DEVICE).
+ *     Games from the initial position, games of a table with given pairs and their forks are all keyed by the rule.
+ *
+ * az_replay_append_engine on an engine with a game-start table uses each game's own start ply, its key pair when the table
+ * carries given pairs, and forms the on-policy z with the sign of the absolute ply.
+ *
+ * az_replay_append_device_starts: az_replay_append_device for such a generation: dev_buf = the packed export, start_ply_dev
+ * (device i32 [n_games]) and keys_dev (device u64 [n_games][2]) = what az_engine_game_starts_device wrote.  Lengths and start
+ * plies are read back and 0 <= start_ply[g] <= max_plies and 0 <= game_len[g] <= max_plies - start_ply[g] are checked before any
+ * kernel runs (AZ_E_INVALID, store unchanged).  keys_dev == NULL: every game is keyed from its start state, as an ordinary
+ * game that starts there.  Synchronises `stream`.
+ *
+ * az_replay_gather_forks: az_replay_gather_states plus keys_out (device u64 [n][2]) = the stored (key, key2) of each example:
+ * the three inputs of az_engine_set_game_starts_device.  Same index space, same AZ_REPLAY_FAULT_BAD_INDEX behaviour (ply -1,
+ * zero keys), asynchronous.  It records no epoch: a fork appends, it overwrites nothing.
+ */
+int az_replay_gather_forks(az_replay *r, const int64_t *indices, int64_t n, uint64_t *bb_out, int32_t *ply_out, uint64_t *keys_out,
+                           void *stream);
+int az_replay_append_device_starts(az_replay *r, const void *dev_buf, int64_t n_games, const int32_t *start_ply_dev,
+                                   const uint64_t *keys_dev, void *stream);
+
 /* Trainer.remove_duplicates over the whole (flattened) buffer.  Synchronises `stream`.  Records are grouped by the
  * 64-bit history hash; every member of a group is then checked against the group's first record (a second, independent
  * 64-bit hash of the history, the ply and the position): a mismatch - two different histories under one key, which the
