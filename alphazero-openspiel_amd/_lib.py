@@ -110,6 +110,8 @@ PROTOTYPES = [
     ("az_engine_set_game_starts", C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.c_int64]),
     ("az_engine_set_game_starts_device", C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp]),
     ("az_engine_game_starts_device", C.c_int, [_vp, _vp, _vp, C.c_int64, _vp]),
+    ("az_engine_set_playout_cap", C.c_int, [_vp, C.c_int32, C.c_double]),
+    ("az_engine_full_moves_device", C.c_int, [_vp, _vp, C.c_int64, _vp]),
     ("az_engine_advance", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     ("az_engine_advance_slots", C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     ("az_engine_compact_rows", C.c_int, [_vp, C.POINTER(C.c_int32), _vp]),
@@ -154,6 +156,7 @@ PROTOTYPES = [
     ("az_replay_append_device", C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp]),
     ("az_replay_gather_forks", C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp, _vp]),
     ("az_replay_append_device_starts", C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp]),
+    ("az_replay_append_device_kept", C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp]),
     ("az_replay_dedupe", C.c_int, [_vp, _vp]),
     ("az_replay_sample", C.c_int, [_vp, _vp, C.c_int32, C.c_uint64, _vp, _vp, _vp, _vp]),
     ("az_replay_sample_sym", C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_uint64, _vp, _vp, _vp, _vp]),

@@ -633,6 +633,25 @@ __device__ void compact_jobs(const Params &p, const int wg, const int n_wg, cons
 __device__ __forceinline__ size_t rec_row(const Params &p, int gid) {
     return p.stream_mode ? (size_t)((unsigned long long)gid % (unsigned long long)p.max_games) : (size_t)gid;
 }
+// Playout cap randomisation: the kind of the search of game `gid` at absolute ply `ply` - full iff u < p_full, u the first
+// uniform of the Philox stream (seed, gid, ply, purpose 3, index 0), whatever rng_mode is: the schedule is a function of
+// (seed, game id, ply) alone.
+__device__ __forceinline__ bool cap_draw_full(uint64_t seed, int gid, int ply, double p_full) {
+    Philox r;
+    philox_init(r, seed, (uint32_t)gid, (uint32_t)ply, 3u, 0u);
+    return philox_u01(r) < p_full;
+}
+// A slot arms the search of game `gid` at absolute ply `ply` (cold paths only: the reset kernel, and move_step after a move or with
+// a new game): the playout counter starts at 0, or - a fast move under a playout cap - at S - n_fast, the value returned.  The
+// kind is read from the generation's schedule, which az_cap_schedule_kernel draws at reset (cap_draw_full for every game id and
+// ply), so the tick kernel carries one byte load instead of a Philox block.  Called by ONE thread of the slot.
+__device__ __forceinline__ int arm_search(const Params &p, int g, int gid, int ply) {
+    const CapDev *c = p.capdev;
+    const bool full = ply >= p.max_plies || c->sched[(size_t)gid * p.max_plies + ply] != 0; // (a ply past the rows ends in PLY_OVERFLOW)
+    const int base = full ? 0 : p.S - c->n_fast;
+    c->sims_base[g] = base;
+    return base;
+}
 // The next game id for a slot (lane 0's result, broadcast); false when none may be handed out.  A closed generation counts
 // next_game up to n_games (overshooting is harmless: nothing reads the counter's excess).  A stream takes an id only while it
 // is below *hand_limit, by compare-and-swap: no id is skipped when the limit rises later, none is handed out twice.
@@ -684,6 +703,7 @@ __device__ __forceinline__ bool finish_game_take_next(const Params &p, int g, in
     if (!take_next_game(p, lane, sr)) {
         sr.gid = -1;
         if (lane == 0) {
+            if (p.capdev) p.capdev->sims_base[g] = 0; // (sr.sims is 0: an idle slot reads back sims_done = 0)
             slot_store(p, g, sr, PH_IDLE);
             p.stats[(size_t)g * ST_N + ST_MOVES] += st_moves;
         }
@@ -870,6 +890,7 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
             p.rec_states[ri * 2 + 1] = sr.rs.bb1;
             p.rec_move[ri] = (uint16_t)action;
             p.rec_nchild[ri] = (uint8_t)nc;
+            if (p.capdev) p.capdev->rec_full[ri] = p.capdev->sched[ri]; // playout cap: the kind of the search that ends here (closed generation: row = game id)
             p.rec_value[ri] = target;
         }
         if (lane < nc) {
@@ -919,6 +940,9 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
     fault = wave_or(fault);
     if (lane == 0) {
         if (rsv_np >= 0) atomicExch(&p.spare[rsv_k], rsv_np); // reserved, not needed after all (game over, fresh tree, leaf root)
+        // playout cap: the kind of the search of the position sr now holds.  Every way here under a cap starts that search (after a
+        // move, with a new game) or is about to (PH_NEED_ROOT: the counter still holds this very value), so no flag is carried
+        if (p.capdev) sr.sims = arm_search(p, g, sr.gid, sr.rs.ply);
         slot_store(p, g, sr, fault ? PH_IDLE : ph);
         unsigned long long *st = p.stats + (size_t)g * ST_N;
         st[ST_MOVES] += st_moves;
@@ -1454,6 +1478,13 @@ __global__ __launch_bounds__(256) void az_update_root_kernel(Params p, const int
     }
 }
 
+// The schedule of a generation under a playout cap: one thread per (game id, absolute ply), on the stream ahead of az_reset_kernel.
+__global__ void az_cap_schedule_kernel(uint64_t seed, double p_full, long long n_games, int max_plies, uint8_t *sched) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_games * max_plies) return;
+    sched[t] = cap_draw_full(seed, (int)(t / max_plies), (int)(t % max_plies), p_full) ? 1 : 0;
+}
+
 __global__ void az_reset_kernel(Params p) {
     int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= p.G) return;
@@ -1466,7 +1497,12 @@ __global__ void az_reset_kernel(Params p) {
     p.bb0[g] = s0.bb0;
     p.bb1[g] = s0.bb1;
     p.ply[g] = s0.ply;
-    p.sims[g] = 0;
+    int sims0 = 0; // (a fast move under a playout cap does not start at 0)
+    if (p.capdev) {
+        p.capdev->sims_base[g] = 0;
+        if (active) sims0 = arm_search(p, g, g, s0.ply);
+    }
+    p.sims[g] = sims0;
     p.which[g] = g | start_rule(p, s0.ply) << 30; // pool g, the start rule of game g (its own start ply when a table is set)
     for (int k = g; k < p.n_spare; k += p.G) p.spare[k] = p.G + k; // the spare pools follow the slots' own
     if (g == 0) p.cjob_count[0] = 1, p.cjob_count[1] = p.cjob_count[2] = 0; // epoch 1: no row has been seen in it
@@ -1766,6 +1802,11 @@ static int reset_common(az_engine *e, uint64_t seed, int64_t n_games, bool strea
     e->ready_known = 0;
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(e, hipMemsetAsync(e->p.rec_len, 0, sizeof(int) * (size_t)e->cfg.max_games, st));
+    if (e->p.capdev) { // (never in stream mode: az_engine_stream_begin refuses an engine with a cap)
+        const long long threads = (long long)n_games * e->p.max_plies;
+        hipLaunchKernelGGL(az_cap_schedule_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, seed, e->cap.p_full,
+                           (long long)n_games, e->p.max_plies, e->cap.sched);
+    }
     hipLaunchKernelGGL(az_reset_kernel, dim3((e->p.G + 255) / 256), dim3(256), 0, st, e->p);
     HIPCHK(e, hipGetLastError());
     e->reset_done = true;
@@ -1799,6 +1840,7 @@ extern "C" int az_engine_stream_begin(az_engine *e, uint64_t seed, void *stream)
     else if (e->cfg.rng_mode == AZ_RNG_INJECTED) why = "rng_mode = AZ_RNG_INJECTED (injected draws are tables indexed by game id)";
     else if (e->has_prefix) why = "a start prefix is set (az_engine_set_start_prefix)";
     else if (e->p.starts) why = "a start-position table is set (az_engine_set_start_positions / az_engine_set_game_starts)";
+    else if (e->p.capdev) why = "a playout cap is set (az_engine_set_playout_cap: the mask of full-search moves does not travel with a take)";
     else if (e->cfg.max_games < e->cfg.n_slots) why = "max_games < n_slots (slots 0..G-1 start ids 0..G-1, each needs a row of the ring)";
     if (why) {
         e->err = std::string("az_engine_stream_begin is for plain self-play engines: refused for ") + why;
@@ -2283,6 +2325,84 @@ extern "C" int az_engine_game_starts_device(az_engine *e, int32_t *ply_out_dev, 
     return e->game_starts && e->starts_keyed ? 1 : 0;
 }
 
+// ---- playout cap randomisation (include/az_engine.h: az_engine_set_playout_cap) ------------------------------------------------
+extern "C" int az_engine_set_playout_cap(az_engine *e, int32_t n_fast, double p_full) {
+    if (!e) return AZ_E_INVALID;
+    const char *why = nullptr;
+    if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) why = "an arena engine (every agent move of an evaluation game is a full search)";
+    else if (e->cfg.manual_moves) why = "a manual_moves engine (its caller arms every search)";
+    else if (e->streaming) why = "an engine in stream mode (az_engine_stream_begin: the mask does not travel with a take)";
+    if (why) {
+        e->err = std::string("az_engine_set_playout_cap is for plain self-play engines in a closed generation: refused for ") + why;
+        return AZ_E_INVALID;
+    }
+    if (n_fast != 0) {
+        if (n_fast < 1 || n_fast > e->cfg.n_playouts || (!e->cfg.use_dirichlet && n_fast < 2)) {
+            e->err = "az_engine_set_playout_cap: n_fast must be in [1, n_playouts = " + std::to_string(e->cfg.n_playouts) +
+                     "], and >= 2 without root Dirichlet expansion (mcts.py:162 divides by zero); 0 clears the cap";
+            return AZ_E_INVALID;
+        }
+        if (!(p_full >= 0.0 && p_full <= 1.0)) {
+            e->err = "az_engine_set_playout_cap: p_full must be in [0, 1]";
+            return AZ_E_INVALID;
+        }
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, hipDeviceSynchronize()); // a generation that still plays may be reading the record
+    if (n_fast && !e->d_cap) { // the first cap: the device record, the slots' word, the schedule and the mask beside the records
+        const size_t G = (size_t)e->p.G, plies = (size_t)e->cfg.max_games * e->p.max_plies;
+        const size_t off_sched = (G * sizeof(int) + 15) & ~(size_t)15, off_full = (off_sched + plies + 15) & ~(size_t)15,
+                     off_rec = (off_full + plies + 15) & ~(size_t)15; // ONE block: nothing is held if it cannot be had or cleared
+        void *blk = nullptr;
+        hipError_t hs = hipMalloc(&blk, off_rec + sizeof(CapDev));
+        if (hs == hipSuccess) hs = hipMemset(blk, 0, off_rec + sizeof(CapDev));
+        if (hs != hipSuccess) {
+            if (blk) (void)hipFree(blk);
+            e->err = std::string("az_engine_set_playout_cap: ") + hipGetErrorString(hs);
+            return hs == hipErrorOutOfMemory ? AZ_E_NOMEM : AZ_E_HIP;
+        }
+        e->dev_allocs.push_back(blk);
+        e->sizes.device_bytes += (int64_t)(off_rec + sizeof(CapDev));
+        e->cap.sims_base = (int *)blk;
+        e->cap.sched = (uint8_t *)blk + off_sched;
+        e->cap.rec_full = (uint8_t *)blk + off_full;
+        e->d_cap = (CapDev *)((char *)blk + off_rec);
+    }
+    e->cap.n_fast = n_fast;
+    e->cap.p_full = n_fast ? p_full : 0.0;
+    if (e->d_cap) HIPCHK(e, hipMemcpy(e->d_cap, &e->cap, sizeof(CapDev), hipMemcpyHostToDevice));
+    e->p.capdev = n_fast ? e->d_cap : nullptr;
+    e->reset_done = false; // the slots' counters were armed under the old setting: the caller resets (az_engine_reset)
+    return AZ_OK;
+}
+
+// one thread per (game, absolute ply): 1 for a recorded ply whose search was a full one, 0 elsewhere
+__global__ void az_full_moves_kernel(const int *len, const uint8_t *rec_full, int start_ply, const int32_t *start_plies, long long n_games,
+                                     int max_plies, uint8_t *out) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_games * max_plies) return;
+    const long long g = t / max_plies;
+    const int i = (int)(t % max_plies);
+    const int sp = start_plies ? start_plies[g] : start_ply;
+    out[t] = (i >= sp && i < sp + len[g] && (!rec_full || rec_full[t])) ? 1 : 0; // (no cap: every recorded ply was a full search)
+}
+
+extern "C" int az_engine_full_moves_device(az_engine *e, uint8_t *full_out_dev, int64_t n_games, void *stream) {
+    if (!e) return AZ_E_INVALID;
+    if (refuse_in_stream(e, "az_engine_full_moves_device")) return AZ_E_STATE;
+    if (!full_out_dev || n_games < 1 || n_games > e->cfg.max_games || (e->game_starts && n_games > e->starts_n)) {
+        e->err = "az_engine_full_moves_device: full_out_dev non-null, n_games in [1, max_games] and within the game-start table";
+        return AZ_E_INVALID;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    const long long threads = (long long)n_games * e->p.max_plies;
+    hipLaunchKernelGGL(az_full_moves_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, e->p.rec_len,
+                       e->p.capdev ? e->cap.rec_full : nullptr, e->p.start.ply, e->game_starts ? e->d_start_ply : nullptr, (long long)n_games, e->p.max_plies,
+                       full_out_dev);
+    HIPCHK(e, hipGetLastError());
+    return e->p.capdev ? 1 : 0;
+}
+
 // `defer`: compactions of this launch are handed to its own extra workgroups (compact_jobs; whole-engine launches only: the job
 // list and its counters are one set per engine, and slot groups ticking on their own streams would share them).
 template <bool MAPPED>
@@ -2696,7 +2816,7 @@ __global__ __launch_bounds__(256) void az_export_roots_kernel(Params p, RootsOut
         o.game_id[g] = p.gid[g];
         o.phase[g] = ph;
         o.ply[g] = p.ply[g];
-        o.sims_done[g] = p.sims[g];
+        o.sims_done[g] = p.sims[g] - (p.capdev ? p.capdev->sims_base[g] : 0); // (the base: a fast move's counter under a playout cap)
         o.n_children[g] = nc;
         o.root_n[g] = rn;
         o.root_q[g] = rq;
@@ -2895,6 +3015,11 @@ extern "C" int az_engine_read_slot(az_engine *e, int32_t slot, az_slot_info *o) 
     RD(o->leaf_bb[0], e->p.leaf_bb0); RD(o->leaf_bb[1], e->p.leaf_bb1); RD(o->leaf_ply, e->p.leaf_ply);
     RD(o->depth, e->p.depth);
     o->depth &= 0xFFFF; // (the high half carries the action that leads to the requested leaf)
+    if (e->p.capdev) { // a fast move's counter starts above 0 under a playout cap: sims_done counts the current search from 0
+        int32_t base = 0;
+        RD(base, e->cap.sims_base);
+        o->sims_done -= base;
+    }
 #undef RD
     return AZ_OK;
 }

@@ -33,6 +33,18 @@ struct PwPlan { // numpy pairwise-sum recursion for a length-A vector, flattened
     int ops[32]; // >=0: push block i, -1: add top two
 };
 
+// Playout cap randomisation, device side (one record per engine, written by az_engine_set_playout_cap).  az_engine_reset draws the
+// generation's schedule into `sched` (one byte per game id and absolute ply, 1 = full search: az_cap_schedule_kernel); a slot that
+// arms a search reads its byte and starts a fast search's counter at S - n_fast, so the tick kernel's `sims >= S` ends both kinds.
+// sims_base [G]: that start value, subtracted by the read-back paths only; rec_full: one byte per (game row, ply) beside
+// rec_nchild, written by move_step with the record: 1 = the recorded move was searched in full.
+struct CapDev {
+    int n_fast, pad;
+    double p_full;
+    int *sims_base;
+    uint8_t *sched, *rec_full;
+};
+
 struct Params {
     // geometry / config
     AzGeom geom;
@@ -103,6 +115,9 @@ struct Params {
     // az_engine_set_start_positions / az_engine_set_start_states_device, for plain self-play engines by az_engine_set_game_starts /
     // az_engine_set_game_starts_device.  Read by game id at reset, at take-next and at game end only - never per tick.
     const AzState *starts;
+    // playout cap randomisation (az_engine_set_playout_cap): null = none.  One pointer (Params grows by 8 bytes); only the cold
+    // paths (reset, move_step, the read-backs) follow it.  Register figures of the tick kernel: DESIGN.md section 4.
+    const CapDev *capdev;
 };
 
 
@@ -129,6 +144,8 @@ struct az_engine {
     int32_t *d_start_ply = nullptr;
     uint64_t *d_start_keys = nullptr; // u64 [starts_cap][2]
     std::vector<int32_t> h_start_ply; // host copy for az_engine_export's on-policy fill
+    CapDev cap = {0, 0, 0.0, nullptr, nullptr, nullptr}; // host copy of the playout cap's record; d_cap: the device record (p.capdev when a cap is in force)
+    CapDev *d_cap = nullptr;
     bool rows_mapped = false; // az_engine_compact_rows has been called since the last reset
     int rows_live = 0;
     bool streaming = false;   // az_engine_stream_begin since the last az_engine_reset

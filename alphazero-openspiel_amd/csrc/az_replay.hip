@@ -199,6 +199,9 @@ struct AppendArgs {
     // absolute ply (az_keychain.h), null = every game is keyed from its start state as an ordinary game
     const int32_t *start_plies;
     const uint64_t *start_keys;
+    // keep u8 [n_src_games][max_plies] by absolute ply, non-null = only the plies with a non-zero byte become examples
+    // (az_replay_append_device_kept, an engine under a playout cap); a game's examples are then its kept plies, in ply order
+    const uint8_t *keep;
     long long cap, head;
     PwPlan pw;
     uint64_t *key, *key2, *bb0, *bb1;
@@ -264,9 +267,15 @@ __global__ void replay_append_kernel(AppendArgs a) {
     long long first = a.dst_first[g];
     int len = a.game_len[g];
     if (first < 0 || i >= len) return;
-    long long dst = (a.head + first + i) % a.cap;
     const int sp = a.start_plies ? a.start_plies[g] : a.start_ply;
     size_t src = (size_t)g * a.max_plies + sp + i;
+    int rank = i; // the example's place within its game: the number of kept plies before it
+    if (a.keep) {
+        if (!a.keep[src]) return;
+        rank = 0;
+        for (int j = 0; j < i; j++) rank += a.keep[src - i + j] != 0;
+    }
+    long long dst = (a.head + first + rank) % a.cap;
     a.bb0[dst] = a.states[src * 2];
     a.bb1[dst] = a.states[src * 2 + 1];
     a.ply[dst] = sp + i;
@@ -302,9 +311,12 @@ __global__ void replay_keys_kernel(AppendArgs a) {
     } else if (len > 0) { // (a game without a recorded ply has no start state to read)
         k = az_key_seed(sp, a.states[s0 * 2], a.states[s0 * 2 + 1]);
     }
-    for (int i = 0; i < len; i++) {
-        a.key[(a.head + first + i) % a.cap] = k.key;
-        a.key2[(a.head + first + i) % a.cap] = k.key2;
+    for (int i = 0, rank = 0; i < len; i++) { // (the chains step over EVERY move: a kept example carries the key of its full history)
+        if (!a.keep || a.keep[s0 + i]) {
+            a.key[(a.head + first + rank) % a.cap] = k.key;
+            a.key2[(a.head + first + rank) % a.cap] = k.key2;
+            rank++;
+        }
         k = az_key_step(k, (uint32_t)a.move[s0 + i], base + i + 1);
     }
 }
@@ -367,6 +379,29 @@ static int append_common(az_replay *r, AppendArgs &a, const std::vector<int32_t>
     return AZ_OK;
 }
 
+// A keep mask (device u8 [n][max_plies] by absolute ply) against the games' rows [plies[g], plies[g] + lens[g]) (validated by the
+// caller): copied to the host, a non-zero byte outside a game's rows is refused, kept[g] = the game's number of kept plies - its
+// FIFO length.  Before any kernel runs: the store stays as it was.
+static int kept_counts(az_replay *r, const uint8_t *keep_dev, const std::vector<int32_t> &lens, const std::vector<int32_t> &plies,
+                       int32_t max_plies, hipStream_t st, std::vector<int32_t> &kept) {
+    const size_t ng = lens.size(), mp = (size_t)max_plies;
+    std::vector<uint8_t> h(ng * mp);
+    RCHK(r, hipMemcpyAsync(h.data(), keep_dev, ng * mp, hipMemcpyDeviceToHost, st));
+    RCHK(r, hipStreamSynchronize(st));
+    kept.assign(ng, 0);
+    for (size_t g = 0; g < ng; g++)
+        for (int32_t i = 0; i < max_plies; i++) {
+            if (!h[g * mp + (size_t)i]) continue;
+            if (i < plies[g] || i >= plies[g] + lens[g]) {
+                r->err = "keep byte at game " + std::to_string(g) + ", ply " + std::to_string(i) + " lies outside the game's recorded plies [" +
+                         std::to_string(plies[g]) + ", " + std::to_string(plies[g] + lens[g]) + ")";
+                return AZ_E_INVALID;
+            }
+            kept[g]++;
+        }
+    return AZ_OK;
+}
+
 extern "C" int az_replay_append_engine(az_replay *r, az_engine *e, void *stream) {
     if (!r || !e) return AZ_E_INVALID;
     if (e->cfg.game != r->cfg.game || e->cfg.rows != r->cfg.rows || e->cfg.cols != r->cfg.cols || e->cfg.device != r->cfg.device) {
@@ -402,7 +437,22 @@ extern "C" int az_replay_append_engine(az_replay *r, az_engine *e, void *stream)
         a.start_keys = e->starts_keyed ? e->d_start_keys : nullptr;
     }
     a.on_policy = e->cfg.backup == AZ_BACKUP_ON_POLICY;
-    return append_common(r, a, lens, st);
+    if (!e->p.capdev) return append_common(r, a, lens, st);
+    // a playout cap is in force: the engine's own mask of full-search moves decides which plies become examples
+    const size_t ng = lens.size(), mp = (size_t)e->p.max_plies;
+    uint8_t *d_keep = nullptr;
+    RCHK(r, hipMalloc((void **)&d_keep, ng * mp));
+    int rc = az_engine_full_moves_device(e, d_keep, (int64_t)ng, st);
+    if (rc < 0) r->err = std::string("az_engine_full_moves_device: ") + az_last_error(e);
+    std::vector<int32_t> plies(ng, e->p.start.ply), kept;
+    if (rc >= 0 && e->game_starts) plies.assign(e->h_start_ply.begin(), e->h_start_ply.begin() + (long)ng);
+    if (rc >= 0) rc = kept_counts(r, d_keep, lens, plies, (int32_t)mp, st, kept);
+    if (rc >= 0) {
+        a.keep = d_keep;
+        rc = append_common(r, a, kept, st); // (synchronises: the mask may be freed afterwards)
+    }
+    (void)hipFree(d_keep);
+    return rc;
 }
 
 // A game length the kernels may run with: rows [start_ply, start_ply + len) of a record array with max_plies rows per game.
@@ -540,6 +590,39 @@ extern "C" int az_replay_append_device_starts(az_replay *r, const void *dev_buf,
         if (!game_len_ok(r, (int64_t)g, lens[g], r->max_plies, plies[g])) return AZ_E_INVALID;
     }
     return append_common(r, a, lens, st);
+}
+
+extern "C" int az_replay_append_device_kept(az_replay *r, const void *dev_buf, int64_t n_games, int32_t start_ply,
+                                            const int32_t *start_ply_dev, const uint64_t *keys_dev, const uint8_t *keep_dev, void *stream) {
+    if (!r || !dev_buf || n_games < 1 || (!start_ply_dev && (start_ply < 0 || start_ply > r->max_plies))) {
+        if (r) r->err = "bad device export (null buffer, n_games < 1, or - without start_ply_dev - start_ply outside [0, max_plies])";
+        return AZ_E_INVALID;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    RCHK(r, hipSetDevice(r->cfg.device));
+    size_t ng = (size_t)n_games;
+    AppendArgs a = packed_export_args(r, dev_buf, n_games);
+    a.start_ply = start_ply;
+    a.start_plies = start_ply_dev;
+    a.start_keys = keys_dev;
+    std::vector<int32_t> lens(ng), plies(ng, start_ply);
+    RCHK(r, hipMemcpyAsync(lens.data(), a.game_len, ng * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (start_ply_dev) RCHK(r, hipMemcpyAsync(plies.data(), start_ply_dev, ng * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    RCHK(r, hipStreamSynchronize(st));
+    for (size_t g = 0; g < ng; g++) { // before any launch: rows [start_ply, start_ply + len) must lie inside the game's record rows
+        if (plies[g] < 0 || plies[g] > r->max_plies) {
+            r->err = "start_ply[" + std::to_string(g) + "] = " + std::to_string(plies[g]) + " is outside [0, max_plies = " +
+                     std::to_string(r->max_plies) + "]";
+            return AZ_E_INVALID;
+        }
+        if (!game_len_ok(r, (int64_t)g, lens[g], r->max_plies, plies[g])) return AZ_E_INVALID;
+    }
+    if (!keep_dev) return append_common(r, a, lens, st);
+    std::vector<int32_t> kept;
+    int rc = kept_counts(r, keep_dev, lens, plies, r->max_plies, st, kept);
+    if (rc != AZ_OK) return rc;
+    a.keep = keep_dev;
+    return append_common(r, a, kept, st);
 }
 
 // A fork: the positions of az_replay_gather_states with the stored history key pair of each example, the three inputs of

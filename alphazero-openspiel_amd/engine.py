@@ -91,6 +91,7 @@ class SelfPlayEngine:
         self.start_history = []
         self.start_histories = None  # set_start_positions / set_game_starts: one history per game
         self.game_starts = None      # set_game_starts / set_game_starts_device: int32 array [n] of the games' start plies
+        self.playout_cap = None      # set_playout_cap: (n_fast, p_full) while a cap is in force
         self.n_games = 0
 
     # ------------------------------------------------------------------ plumbing
@@ -201,6 +202,24 @@ class SelfPlayEngine:
         keyed = self._check(self.lib.az_engine_game_starts_device(self._h, C.c_void_p(ply.data_ptr()), C.c_void_p(keys.data_ptr()),
                                                                   n, self._stream()))
         return ply, (keys if keyed else None)
+
+    def set_playout_cap(self, n_fast, p_full=1.0):
+        """Playout cap randomisation (az_engine_set_playout_cap): from the next reset() on, every move is searched in full
+        (n_playouts) with probability p_full and otherwise fast (n_fast playouts, 1 <= n_fast <= n_playouts); every move is
+        still recorded, and full_moves_device() tells the two kinds apart.  Plain self-play engines only, not in stream mode
+        (EngineError names the reason otherwise).  n_fast = 0 clears the cap.  reset() afterwards."""
+        self._check(self.lib.az_engine_set_playout_cap(self._h, int(n_fast), float(p_full)))
+        self.playout_cap = (int(n_fast), float(p_full)) if int(n_fast) else None
+
+    def full_moves_device(self, n_games=None):
+        """-> uint8 device tensor [n, max_plies] by absolute ply: 1 where a recorded ply was searched in full, 0 elsewhere (a
+        fast move under a playout cap, a ply that was not played); all recorded plies give 1 without a cap.  What
+        DeviceReplay.append_device(buf, n, keep=) and examples_from_export(keep=) take beside export_device() / export().
+        n_games: default the last reset's."""
+        n = int(self.n_games if n_games is None else n_games)
+        full = torch.empty((n, self.max_plies), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.az_engine_full_moves_device(self._h, C.c_void_p(full.data_ptr()), n, self._stream()))
+        return full
 
     def set_injected_rng(self, etas, us, absolute_ply=False):
         """etas: per game, per ply, the Dirichlet draw (ragged lists ok); us: per game, per ply uniforms.  Lists are
@@ -561,11 +580,14 @@ def pis_from_visits(actions, visits, n_children, num_actions):
     return out
 
 
-def examples_from_export(game, ex, start_history=()):
+def examples_from_export(game, ex, start_history=(), keep=None):
     """Engine records -> the reference's list of games, each a list of `[info_state_str, board (C+1,H,W)
     float64, pi list[A], value]` (game_utils.py:169,200-204; consumed by train.py:109-126,172-198).
     All plies of all games are converted in bulk (one numpy pass for boards, one for pi); what remains per example is
-    building its 4-element list."""
+    building its 4-element list.
+    keep: an array [G, max_plies] by absolute ply (SelfPlayEngine.full_moves_device, a playout cap's mask) - only plies with a
+    non-zero entry become examples; the others are dropped from the lists, while the key strings still run over every move
+    and the values stay those of the plies' own (absolute) numbers."""
     A = game.num_distinct_actions()
     lens = np.asarray(ex["game_len"]).astype(np.int64)
     G = len(lens)
@@ -582,16 +604,20 @@ def examples_from_export(game, ex, start_history=()):
     mp = ex["move"].shape[1]
     ply = np.arange(mp)[None, :]
     valid = (ply >= p0) & (ply < p0 + lens[:, None])           # [G, mp], row-major = game by game, ply by ply
-    boards = boards_from_bitboards(game, ex["states"][valid], np.broadcast_to(ply, valid.shape)[valid])
-    pis = pis_from_visits(ex["child_action"][valid], ex["child_visits"][valid], ex["n_children"][valid], A).tolist()
-    values = ex["value"][valid].tolist()
+    kept = valid if keep is None else valid & (np.asarray(keep).reshape(valid.shape) != 0)
+    boards = boards_from_bitboards(game, ex["states"][kept], np.broadcast_to(ply, kept.shape)[kept])
+    pis = pis_from_visits(ex["child_action"][kept], ex["child_visits"][kept], ex["n_children"][kept], A).tolist()
+    values = ex["value"][kept].tolist()
     moves = ex["move"][valid].tolist()
+    is_kept = kept[valid].tolist()
     prefixes = [", ".join(str(int(a)) for a in h) for h in (start_history if per_game else [start_history])]
-    games, k = [], 0
+    games, k, j = [], 0, 0  # k: the ply among the valid ones, j: among the kept ones
     for g, n in enumerate(lens.tolist()):
         key, plies = prefixes[g if per_game else 0], []
         for i in range(k, k + n):
-            plies.append([key, boards[i], pis[i], values[i]])
+            if is_kept[i]:
+                plies.append([key, boards[j], pis[j], values[j]])
+                j += 1
             key = (key + ", " if key else "") + str(moves[i])
         games.append(plies)
         k += n

@@ -84,6 +84,24 @@ class ExampleGenerator:
                 raise ValueError("continuous=True ticks the engine on one stream: overlap > 1 is not supported with it")
             if self.eval_backend != "fused":
                 raise ValueError("continuous=True needs eval_backend=\"fused\" (got %r)" % (self.eval_backend,))
+        # playout_cap=(n_fast, p_full): playout cap randomisation (SelfPlayEngine.set_playout_cap) - every move is searched in full
+        # (n_playouts) with probability p_full, else with n_fast playouts, and ONLY the full-search moves become examples.  The
+        # mask of full-search moves is a side table of one engine: it does not travel with a gather (as game starts do not).
+        self.playout_cap = kwargs.get("playout_cap")
+        if self.playout_cap is not None:
+            try:
+                n_fast, p_full = self.playout_cap
+                n_fast, p_full = int(n_fast), float(p_full)
+            except (TypeError, ValueError):
+                raise ValueError("playout_cap must be a pair (n_fast, p_full), got %r" % (self.playout_cap,))
+            n_playouts = int(kwargs.get("n_playouts", 100))  # (SelfPlayEngine's default)
+            if not 1 <= n_fast <= n_playouts or not 0.0 <= p_full <= 1.0:
+                raise ValueError("playout_cap=(n_fast, p_full) needs 1 <= n_fast <= n_playouts = %d and 0 <= p_full <= 1, got %r"
+                                 % (n_playouts, self.playout_cap))
+            self.playout_cap = (n_fast, p_full)
+            self._check_start_positions("playout_cap")
+            if self.overlap > 1:
+                raise ValueError("playout_cap is not supported with overlap > 1: the capped generation is ticked on one stream")
 
     def _engine_kwargs(self):
         return {k: self.kwargs[k] for k in _ENGINE_KW if k in self.kwargs}
@@ -209,13 +227,14 @@ class ExampleGenerator:
             bad = "continuous=True"
         else:
             return
-        raise ValueError("%s is not supported with %s: games that start from their own positions are played by ONE engine in "
-                         "a closed generation" % (what, bad))
+        raise ValueError("%s is not supported with %s: games with a side table of their own (start positions, a playout cap's mask of "
+                         "full-search moves) are played by ONE engine in a closed generation" % (what, bad))
 
     def _play_from_starts(self, n_games, histories=None, fork=None, into=None):
         """One closed generation on one engine whose game i starts after histories[i], or from the stored position fork[1][i]
-        of the DeviceReplay fork[0].  -> the export dict of host arrays (engine.export()) or, with `into`, the number of games
-        appended to that store."""
+        of the DeviceReplay fork[0] (neither: from the initial position - the path of playout_cap).  -> the export dict of host
+        arrays (engine.export()) or, with `into`, the number of games appended to that store.  Under playout_cap the dict
+        carries "keep", the host copy of the mask of full-search moves, and the store takes only those moves (append_engine)."""
         n = int(n_games)
         n_slots = int(self.n_slots or min(n, 4096))
         engine = SelfPlayEngine(self.game, n_slots, max_games=n, device=self.device,
@@ -224,8 +243,10 @@ class ExampleGenerator:
         try:
             if fork is not None:
                 engine.set_game_starts_device(*fork[0].gather_forks(fork[1]))
-            else:
+            elif histories is not None:
                 engine.set_game_starts(histories)
+            if self.playout_cap is not None:
+                engine.set_playout_cap(*self.playout_cap)
             evaluator = make_evaluator(self.net, self.device, self.eval_backend, self.eval_precision, n_slots, self.eval_dtype)
             self.last_progress = run_selfplay(engine, evaluator, n, use_graph=self.use_graph)
             if into is not None:
@@ -233,6 +254,8 @@ class ExampleGenerator:
                 out = n
             else:
                 out = engine.export()
+                if self.playout_cap is not None:
+                    out["keep"] = engine.full_moves_device().cpu().numpy()
         finally:
             close_all(engine, evaluator, drain=True)
         self._generation += 1
@@ -284,11 +307,17 @@ class ExampleGenerator:
         same gathered list.  The reference-format lists are built from ONE device-to-host copy of the gathered buffer.
         start_positions: a list of at least n_games action lists - game i starts after start_positions[i] (an opening set, a
         curriculum, endgames) and its keys are the full histories, prefix included.  One process, one engine, a closed
-        generation: ValueError with torch.distributed world > 1, n_pools > 1, pool_devices or continuous=True."""
+        generation: ValueError with torch.distributed world > 1, n_pools > 1, pool_devices or continuous=True.
+        With playout_cap=(n_fast, p_full) the games hold only their full-search examples (same limits)."""
         if start_positions is not None:
             self._check_start_positions("generate_examples(start_positions=...)")
             histories = self._histories(n_games, start_positions)
-            return examples_from_export(self.game, self._play_from_starts(n_games, histories), histories)
+            ex = self._play_from_starts(n_games, histories)
+            return examples_from_export(self.game, ex, histories, keep=ex.get("keep"))
+        if self.playout_cap is not None:  # only the full-search moves become examples; one engine, whose mask says which
+            self._check_start_positions("playout_cap")
+            ex = self._play_from_starts(n_games)
+            return examples_from_export(self.game, ex, keep=ex["keep"])
         gathered, nbytes, n_local, world, (mp, mc) = self._play_and_gather(n_games)
         host = gathered.cpu().numpy()
         games = []
@@ -321,6 +350,9 @@ class ExampleGenerator:
             if int(idx.numel()) != int(n_games):
                 raise ValueError("fork_from holds %d indices, %d games were asked for" % (int(idx.numel()), int(n_games)))
             return self._play_from_starts(n_games, fork=(replay, idx), into=replay)
+        if self.playout_cap is not None:  # the kept path: the store takes the engine's full-search moves only
+            self._check_start_positions("playout_cap")
+            return self._play_from_starts(n_games, into=replay)
         gathered, nbytes, n_local, world, _ = self._play_and_gather(n_games)
         for r in range(world):
             replay.append_device(gathered[r * nbytes:(r + 1) * nbytes], n_local)

@@ -86,18 +86,34 @@ class DeviceReplay:
         v.value = keep["value"].ctypes.data_as(C.POINTER(C.c_double))
         self._check(self.lib.az_replay_append_host(self._h, C.byref(v), int(ex.get("start_ply", 0)), self._stream()))
 
-    def append_device(self, buf, n_games, start_ply=0, keys=None):
+    def append_device(self, buf, n_games, start_ply=0, keys=None, keep=None):
         """Games from a packed DEVICE export (engine.export_device(), or one rank's section of the all-gathered buffer):
         engine -> RCCL all-gather -> replay store with no host copy of the records.
         start_ply: one start ply for every game, or - a generation with a start per game - an int32 device tensor [n_games],
         with keys = the games' history key pairs (int64 [n_games, 2]) or None (keyed from their start states): the two tensors
-        SelfPlayEngine.game_starts_device() returns."""
+        SelfPlayEngine.game_starts_device() returns.
+        keep: a uint8 device tensor [n_games, max_plies] by absolute ply (SelfPlayEngine.full_moves_device(): the full-search
+        moves of a generation under a playout cap) - only plies with a non-zero byte become examples; a game's FIFO length is
+        its number of kept plies, and the keys are still those of the full histories."""
         if buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.device != self.device:
             raise RuntimeError("append_device expects a contiguous uint8 tensor on %s" % (self.device,))
         from .engine import device_export_layout
         need = device_export_layout(n_games, self.game.max_game_length(), self.game.max_children())[1]
         if buf.numel() < need:
             raise RuntimeError("export buffer holds %d bytes, %d games need %d" % (buf.numel(), n_games, need))
+        if keep is not None:
+            n, per_game = int(n_games), torch.is_tensor(start_ply)
+            if keys is not None and not per_game:
+                raise ValueError("keys go with a start ply per game: give start_ply as an int32 tensor [n_games]")
+            for t, dt, shape in ((start_ply if per_game else None, torch.int32, (n,)), (keys, torch.int64, (n, 2)),
+                                 (keep, torch.uint8, (n, self.game.max_game_length()))):
+                if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != self.device or tuple(t.shape) != shape):
+                    raise RuntimeError("append_device expects a contiguous %s %s tensor on %s" % (dt, shape, self.device))
+            self._check(self.lib.az_replay_append_device_kept(
+                self._h, C.c_void_p(buf.data_ptr()), n, 0 if per_game else int(start_ply),
+                C.c_void_p(start_ply.data_ptr()) if per_game else None, C.c_void_p(keys.data_ptr()) if keys is not None else None,
+                C.c_void_p(keep.data_ptr()), self._stream()))
+            return
         if not torch.is_tensor(start_ply):
             if keys is not None:
                 raise ValueError("keys go with a start ply per game: give start_ply as an int32 tensor [n_games]")

@@ -50,7 +50,18 @@ def main():
     ap.add_argument("--mirror", action="store_true",
                     help="train on left-right mirrored batches: every sampled position is flipped or not by a coin drawn on the "
                          "device (both games are symmetric under it; the policy is mirrored with the board)")
+    ap.add_argument("--playout-cap", default=None, metavar="N_FAST:P_FULL",
+                    help="playout cap randomisation: every move is searched with --playouts playouts with probability P_FULL and "
+                         "with N_FAST otherwise, and only the full-search moves are trained on (e.g. 25:0.25; not with --continuous)")
     a = ap.parse_args()
+    cap = None
+    if a.playout_cap:
+        if a.continuous:
+            ap.error("--playout-cap is not available with --continuous (the mask of full-search moves does not travel with a take)")
+        try:
+            cap = (int(a.playout_cap.split(":")[0]), float(a.playout_cap.split(":")[1]))
+        except (IndexError, ValueError):
+            ap.error("--playout-cap takes N_FAST:P_FULL, e.g. 25:0.25")
 
     dev = torch.device("cuda:0")
     game = games.load_game(a.game)
@@ -75,6 +86,8 @@ def main():
         else:
             eng = E.SelfPlayEngine(game, min(a.games, 4096), n_playouts=a.playouts, backup=a.backup, max_games=a.games,
                                    device=dev, seed=gen)
+            if cap is not None:
+                eng.set_playout_cap(*cap)                                  # append_engine below keeps the full-search moves only
             prog = E.run_selfplay(eng, FusedNet(net, dev, max_boards=eng.G, precision=a.precision), a.games, use_graph=True)
         t_play = time.perf_counter() - t0
         if generator is None:

@@ -269,6 +269,36 @@ int az_engine_set_game_starts_device(az_engine *e, const uint64_t *bb_dev, const
 int az_engine_game_starts_device(az_engine *e, int32_t *ply_out_dev, uint64_t *keys_out_dev, int64_t n_games, void *stream);
 
 /*
+ * Playout cap randomisation (KataGo: Wu 2019, section 3.1) for SELF-PLAY: every move is searched in full (n_playouts) with
+ * probability p_full and otherwise fast (n_fast playouts); only full-search moves are meant to become training examples, the fast
+ * ones carry the game to its outcome.  The reference has no counterpart (play_game_self searches every move alike,
+ * game_utils.py:156-197); with no cap set nothing changes, bit for bit.
+ *
+ * az_engine_set_playout_cap: plain self-play engines only (arena_agent == AZ_ARENA_SELF_PLAY, manual_moves == 0, not in stream
+ *   mode): the others return AZ_E_INVALID and az_last_error names the reason; az_engine_stream_begin refuses an engine with a cap.
+ *   1 <= n_fast <= n_playouts (n_fast >= 2 without root Dirichlet expansion, the rule az_engine_create applies to n_playouts),
+ *   0 <= p_full <= 1; n_fast == 0 clears the cap.  Call it before az_engine_reset (the next call the engine accepts): it holds for
+ *   every later generation, and composes with a start prefix and with a game-start table.
+ * The draw: the search a slot arms - at reset, when it takes the next game, after every move - has the kind of one uniform u, the
+ *   first philox_u01 of the stream (seed, game id, ply, purpose 3, index 0), ply = the absolute ply of the position to be
+ *   searched; the move is full iff u < p_full.  (az_engine_reset draws the generation's whole schedule, one byte per game id and
+ *   ply, with one small kernel on `stream`; the tick kernel reads a byte where a slot arms a search.)  It comes from Philox whatever rng_mode is, so the schedule is a function of (seed, game id, ply)
+ *   alone and AZ_RNG_INJECTED engines take a cap too.  (Purposes 0, 1, 2: root noise, move choice, arena opponent.)
+ * The search: a full move adds n_playouts playouts to its tree, a fast one n_fast (a kept tree works as without a cap).  Root
+ *   noise, temperature and move sampling are the same for both kinds.  az_slot_info.sims_done and the root export's sims_done count
+ *   the current search from 0; az_progress.sims counts the playouts actually run.  Node pools stay sized by n_playouts.
+ * Records: every move is recorded exactly as without a cap (packed export, az_example_view and the on-policy value fill do not
+ *   change); beside them the engine keeps one byte per (game, ply): 1 = full search, 0 = fast.
+ *
+ * az_engine_full_moves_device: writes that mask to full_out_dev, a device u8 [n_games][max_plies] indexed by absolute ply like the
+ *   other per-ply arrays: 1 for a recorded full-search ply, 0 elsewhere; with no cap every recorded ply gives 1.  One small kernel,
+ *   asynchronous on `stream`.  The companion of az_engine_export_device for az_replay_append_device_kept.  Returns 1 when a cap is
+ *   in force, 0 when none is, < 0 on error (AZ_E_STATE in stream mode).
+ */
+int az_engine_set_playout_cap(az_engine *e, int32_t n_fast, double p_full);
+int az_engine_full_moves_device(az_engine *e, uint8_t *full_out_dev, int64_t n_games, void *stream);
+
+/*
  * One tick = MCTS.playout's select + expand + backup (mcts.py:126-153) for all slots, fused with the
  * agent's move step when a slot has finished its S playouts (alphazerobot.py:71-93,
  * game_utils.py:156-197, mcts.py:155-162,192-203) and the root Dirichlet expansion (mcts.py:182-190):

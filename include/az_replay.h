@@ -123,6 +123,25 @@ int az_replay_gather_forks(az_replay *r, const int64_t *indices, int64_t n, uint
 int az_replay_append_device_starts(az_replay *r, const void *dev_buf, int64_t n_games, const int32_t *start_ply_dev,
                                    const uint64_t *keys_dev, void *stream);
 
+/*
+ * Appending only SOME plies of a generation: the examples of an engine under a playout cap (az_engine_set_playout_cap), whose
+ * fast-search moves carry a game to its outcome but are not trained on.
+ *
+ * az_replay_append_device_kept: az_replay_append_device_starts with start_ply_dev == NULL allowed (every game then starts at
+ * start_ply, which is ignored otherwise) plus keep_dev, a device u8 [n_games][max_plies] indexed by ABSOLUTE ply (what
+ * az_engine_full_moves_device writes).  Only plies with a non-zero byte become stored examples, in ply order; a game's FIFO length
+ * is its number of kept plies, and a game with none is skipped, as a game of length 0 is.  The key chains still step over every
+ * move of the game, so a kept example carries the key of its full history (the key rule); on-policy z keeps the sign of the
+ * absolute ply; pi is formed by the one routine every append uses.  Lengths, start plies and the mask are read back and checked
+ * before any kernel runs (AZ_E_INVALID, store unchanged): the checks of az_replay_append_device_starts, and a non-zero keep byte
+ * outside a game's plies [start, start + len) is refused.  keep_dev == NULL keeps every ply.  Synchronises `stream`.
+ *
+ * az_replay_append_engine on an engine with a cap in force applies the engine's own mask in this way; on an engine without one it
+ * does what it always did.
+ */
+int az_replay_append_device_kept(az_replay *r, const void *dev_buf, int64_t n_games, int32_t start_ply, const int32_t *start_ply_dev,
+                                 const uint64_t *keys_dev, const uint8_t *keep_dev, void *stream);
+
 /* Trainer.remove_duplicates over the whole (flattened) buffer.  Synchronises `stream`.  Records are grouped by the
  * 64-bit history hash; every member of a group is then checked against the group's first record (a second, independent
  * 64-bit hash of the history, the ply and the position): a mismatch - two different histories under one key, which the
