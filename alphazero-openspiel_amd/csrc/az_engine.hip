@@ -725,13 +725,37 @@ __device__ __forceinline__ bool opponent_to_move(const Params &p, int gid, const
     return p.arena_agent != AZ_ARENA_SELF_PLAY && ((s.ply ^ gid ^ p.arena_flip) & 1);
 }
 
+// Policy target pruning (KataGo: Wu 2019, section 3.2; include/az_engine.h: az_engine_set_forced_playouts) - the root's child visits
+// as the record takes them after a full search with forced playouts.  One lane per child (n, Q, P its own), N the root's count.
+// The most-visited child b (the first of them) keeps its count and sets the bar V = its own selection value; every other visited
+// child gives back playouts one at a time, at most the F = floor(sqrt(k P N)) it may have been forced to take, while the selection
+// value it would have had with one playout less still stays below V; a child left with a single playout loses that one too.
+// The loop runs at most F times (k = 2, N = 400: 28).  A NaN anywhere makes a comparison false and ends the lane's loop.
+__device__ __forceinline__ uint32_t prune_forced_visits(const Params &p, uint32_t root_n, double cp, double cq, uint32_t cn, int lane, int nc) {
+    const double nmax = wave_max(lane < nc ? (double)cn : -1.0); // (a u32 count is exact in a double)
+    const int b = __ffsll((unsigned long long)__ballot(lane < nc && (double)cn == nmax)) - 1;
+    const double u = (p.c_puct * cp) * sqrt((double)root_n); // the select's own expression (mcts.py:78), so the same bits
+    const double v = __shfl(cq + u / (double)(cn + 1), b);
+    const double kpn = (p.forced_k * cp) * (double)root_n;
+    uint32_t m = cn;
+    if (lane < nc && lane != b && cn > 0) {
+        for (uint32_t f = 1; m > 0; f++, m--) {
+            if (!((double)f * (double)f <= kpn)) break;   // all F forced playouts are given back
+            if (!(cq + u / (double)m < v)) break;         // with m - 1 visits the child would have been selected on its own merit
+        }
+        if (m < cn && m == 1) m = 0;
+    }
+    return m;
+}
+
 // ------------------------------------------------------------------------------------------------
 // The cold path of a tick: AlphaZeroBot.step's tail + play_game_self's loop body for a slot whose S playouts are
 // done (phase PH_MOVE, set by the previous tick), game turnover, and the root-evaluation request of the next search.
 // Runs at the START of the slot's wave in az_advance_kernel and ends the wave's tick, so its registers never
 // overlap the playout loop's (it used to be a kernel of its own: one more launch gap and ~11 us of serial latency
 // per tick; now moving slots run beside the other slots' playouts).
-template <int GAME>
+// FORCED (az_engine_set_forced_playouts with prune = 1 reaches here): the recorded child visits of a full search are the pruned ones.
+template <int GAME, bool FORCED>
 __device__ __forceinline__ void move_step(const Params &p, const int g, const int lane, int ph, SlotRegs sr,
                                           float *__restrict__ obs_row, const int row) { // obs_row: row `row` of the request buffer, this slot's
     const AzGeom &geom = p.geom;
@@ -897,6 +921,12 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
             p.rec_child_action[ri * p.maxc + lane] = (uint16_t)cact;
             p.rec_child_visits[ri * p.maxc + lane] = cn;
         }
+        if constexpr (FORCED) { // a full search under forced playouts with pruning: the record takes the pruned counts instead
+            if (p.forced_prune && (!p.capdev || p.capdev->sched[ri] != 0)) {
+                const uint32_t m = prune_forced_visits(p, t.nd[sr.root].N, lane < nc ? t.nd[c0 + lane].P : 0.0, cq, cn, lane, nc);
+                if (lane < nc && m != cn) p.rec_child_visits[ri * p.maxc + lane] = m; // (same lane, same address: program order)
+            }
+        }
         st_moves++;
         float ret0 = 0.f;
         int term = az_apply<GAME>(sr.rs, geom, action, &ret0); // game_utils.py:197
@@ -963,7 +993,10 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
 // MAPPED = false: the launch covers slots [g_first, g_end), row g of priors / values / obs_out belongs to slot g.
 // MAPPED = true (az_engine_advance_rows, the thinned-out tail of a generation): it covers the first g_end entries of the
 // dense list row_slot[]; entry i writes its request to row i, and reads the answer to its previous request from row req_row[g].
-template <int GAME, int NP, bool MAPPED>
+// FORCED = true (picked at launch when az_engine_set_forced_playouts is in force; plain PUCT self-play engines only): a root child
+// with n > 0 visits and n * n < k * P * N is selected before any other in a full search (forced playouts), and move_step may
+// prune the recorded counts.  FORCED = false compiles to the kernel without the feature.
+template <int GAME, int NP, bool MAPPED, bool FORCED>
 __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_first, const int g_end, const float *__restrict__ priors,
                                                   const float *__restrict__ values, float *__restrict__ obs_out) {
     const int lane = threadIdx.x & 63;
@@ -990,7 +1023,7 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
         // the agent's move / the opponent's move / the next search's root request / a stream's stalled slot asking for a game id
         // again: ends this slot's tick
         if (MAPPED && lane == 0) p.req_row[g] = row;
-        move_step<GAME>(p, g, lane, ph, sr, obs_row, row);
+        move_step<GAME, FORCED>(p, g, lane, ph, sr, obs_row, row);
         return;
     }
     if (ph != PH_RUN && ph != PH_WAIT_LEAF && ph != PH_WAIT_ROOT) return;
@@ -1113,6 +1146,12 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
     int budget = p.max_sims_per_tick;
     int next_phase = PH_RUN;
     const unsigned long long t_start = wall_clock64(); // 100 MHz
+    // forced playouts act in full searches only: under a playout cap the schedule says which this one is (arm_search's rule);
+    // a fast search runs with k = 0, under which no child is ever forced
+    [[maybe_unused]] double forced_k = 0.0;
+    if constexpr (FORCED) {
+        if (!p.capdev || sr.rs.ply >= p.max_plies || p.capdev->sched[(size_t)sr.gid * p.max_plies + sr.rs.ply] != 0) forced_k = p.forced_k;
+    }
     // The root's children, kept in registers across the playouts CHAINED in this launch (a chained playout follows a terminal
     // hit, which expands nothing and changes only N and Q of the nodes on its path): the launch is as long as its slowest wave,
     // and that wave is a chain - one HBM round trip less per chained playout.
@@ -1180,6 +1219,9 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
                     val = c.Q + ((p.c_puct * c.P) * sqrt((double)np_)) / (double)(cn + 1); // mcts.py:78
                 else // mcts.py:80; log(N_parent) from the host's table (N_parent >= 1 whenever a child has a visit)
                     val = cn == 0 ? INFINITY : c.Q + (p.c_puct * c.P) * sqrt(p.log_table[np_ < p.log_n ? np_ : 0u] / (double)cn);
+                if constexpr (FORCED) { // a forced playout: the first-maximum ballot below takes the lowest forced child
+                    if (depth == 0 && cn > 0 && (double)cn * (double)cn < (forced_k * c.P) * (double)np_) val = INFINITY;
+                }
             }
             double mx = wave_max(val);
             unsigned long long eq = __ballot(val == mx);
@@ -1250,7 +1292,7 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
     }
 }
 
-template <int GAME, int NP, bool MAPPED>
+template <int GAME, int NP, bool MAPPED, bool FORCED>
 __global__ __launch_bounds__(256) void az_advance_kernel(Params p, const int g_first, const int g_end, const float *__restrict__ priors,
                                                          const float *__restrict__ values, float *__restrict__ obs_out) {
     const int n_slot_wgs = (g_end - g_first + 3) >> 2;
@@ -1259,7 +1301,7 @@ __global__ __launch_bounds__(256) void az_advance_kernel(Params p, const int g_f
         return;
     }
     const int epoch = p.defer_compact ? p.cjob_count[0] : 0; // (the same in every wave of the launch: compact_jobs)
-    advance_slot_wave<GAME, NP, MAPPED>(p, g_first, g_end, priors, values, obs_out);
+    advance_slot_wave<GAME, NP, MAPPED, FORCED>(p, g_first, g_end, priors, values, obs_out);
     // every slot wave reports itself seen, whichever way it left: its extra workgroup stays until none of its rows can hand over a job
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (p.defer_compact && (threadIdx.x & 63) == 0 && g_first + row < g_end)
@@ -2403,6 +2445,29 @@ extern "C" int az_engine_full_moves_device(az_engine *e, uint8_t *full_out_dev, 
     return e->p.capdev ? 1 : 0;
 }
 
+// ---- forced playouts and policy target pruning (include/az_engine.h: az_engine_set_forced_playouts) ----------------------------
+extern "C" int az_engine_set_forced_playouts(az_engine *e, double k, int32_t prune) {
+    if (!e) return AZ_E_INVALID;
+    const char *why = nullptr;
+    if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) why = "an arena engine (an evaluation game records no policy target)";
+    else if (e->cfg.manual_moves) why = "a manual_moves engine (analysis and reanalyse searches are read raw)";
+    else if (e->cfg.select_rule != AZ_SELECT_PUCT) why = "select_rule = AZ_SELECT_UCT (the forcing and pruning rules are stated for the PUCT value)";
+    if (why) {
+        e->err = std::string("az_engine_set_forced_playouts is for plain PUCT self-play engines: refused for ") + why;
+        return AZ_E_INVALID;
+    }
+    if (!(k >= 0.0 && k <= 1.7976931348623157e308) || (prune != 0 && prune != 1)) { // (the negated form takes NaN too)
+        e->err = "az_engine_set_forced_playouts: k must be finite and >= 0 (0 clears the setting), prune 0 or 1";
+        return AZ_E_INVALID;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, hipDeviceSynchronize()); // a generation that still plays was launched under the old setting
+    e->p.forced_k = k;
+    e->p.forced_prune = k > 0.0 ? prune : 0;
+    e->reset_done = false; // the caller starts a generation next (az_engine_reset / az_engine_stream_begin)
+    return AZ_OK;
+}
+
 // `defer`: compactions of this launch are handed to its own extra workgroups (compact_jobs; whole-engine launches only: the job
 // list and its counters are one set per engine, and slot groups ticking on their own streams would share them).
 template <bool MAPPED>
@@ -2413,10 +2478,13 @@ static int advance_range(az_engine *e, int g_first, int g_end, const float *prio
     defer = defer && e->may_compact;
     dim3 grid((g_end - g_first + 3) / 4 + (defer ? AZ_COMPACT_WGS : 0)), block(256);
     e->p.defer_compact = defer ? 1 : 0;
+    const bool forced = e->p.forced_k > 0.0; // (az_engine_set_forced_playouts: its own instantiations, the others stay as they are)
     if (e->cfg.game == AZ_GAME_CONNECT_FOUR) {
-        hipLaunchKernelGGL((az_advance_kernel<AZG_CONNECT_FOUR, 1, MAPPED>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out);
+        if (forced) hipLaunchKernelGGL((az_advance_kernel<AZG_CONNECT_FOUR, 1, MAPPED, true>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out);
+        else hipLaunchKernelGGL((az_advance_kernel<AZG_CONNECT_FOUR, 1, MAPPED, false>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out);
     } else {
-        hipLaunchKernelGGL((az_advance_kernel<AZG_BREAKTHROUGH, 3, MAPPED>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out);
+        if (forced) hipLaunchKernelGGL((az_advance_kernel<AZG_BREAKTHROUGH, 3, MAPPED, true>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out);
+        else hipLaunchKernelGGL((az_advance_kernel<AZG_BREAKTHROUGH, 3, MAPPED, false>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out);
     }
     e->p.defer_compact = 0;
     HIPCHK(e, hipGetLastError());

@@ -51,6 +51,7 @@ struct Params {
     int game, A, maxc, max_plies, obs_elems, pstride;
     int G, S, use_dirichlet, keep_tree, backup, rng_mode, max_sims_per_tick, manual_moves, chain_clocks;
     uint32_t cap, need_per_move;
+    int forced_prune; // az_engine_set_forced_playouts (with forced_k at the end of the record; here it fills a hole of the layout)
     double c_puct, one_minus_ratio, alpha, inv_temp;
     uint64_t seed;
     long long n_games, max_games;
@@ -118,6 +119,9 @@ struct Params {
     // playout cap randomisation (az_engine_set_playout_cap): null = none.  One pointer (Params grows by 8 bytes); only the cold
     // paths (reset, move_step, the read-backs) follow it.  Register figures of the tick kernel: DESIGN.md section 4.
     const CapDev *capdev;
+    // forced playouts and policy target pruning (az_engine_set_forced_playouts): k = 0 = none.  Read by the FORCED instantiations
+    // of az_advance_kernel only, which the host launches while forced_k > 0; the others never touch the two fields.
+    double forced_k;
 };
 
 

@@ -92,6 +92,7 @@ class SelfPlayEngine:
         self.start_histories = None  # set_start_positions / set_game_starts: one history per game
         self.game_starts = None      # set_game_starts / set_game_starts_device: int32 array [n] of the games' start plies
         self.playout_cap = None      # set_playout_cap: (n_fast, p_full) while a cap is in force
+        self.forced_playouts = None  # set_forced_playouts: (k, prune) while the setting is in force
         self.n_games = 0
 
     # ------------------------------------------------------------------ plumbing
@@ -210,6 +211,16 @@ class SelfPlayEngine:
         (EngineError names the reason otherwise).  n_fast = 0 clears the cap.  reset() afterwards."""
         self._check(self.lib.az_engine_set_playout_cap(self._h, int(n_fast), float(p_full)))
         self.playout_cap = (int(n_fast), float(p_full)) if int(n_fast) else None
+
+    def set_forced_playouts(self, k, prune=True):
+        """Forced playouts and policy target pruning (az_engine_set_forced_playouts; KataGo, Wu 2019, section 3.2): from the
+        next reset() / stream_begin() on, every full search gives a root child with n > 0 visits and n^2 < k P N a playout
+        before any other child, and with prune the recorded child visits are the pruned ones - the raw counts are not kept, so
+        export(), export_device(), stream_take() and DeviceReplay.append_* all deliver the pruned target.  Fast moves under a
+        playout cap are searched and recorded as without the setting.  Plain PUCT self-play engines only (EngineError names
+        the reason otherwise).  k = 0 clears the setting.  reset() or stream_begin() afterwards."""
+        self._check(self.lib.az_engine_set_forced_playouts(self._h, float(k), int(prune)))
+        self.forced_playouts = (float(k), bool(prune)) if float(k) > 0.0 else None
 
     def full_moves_device(self, n_games=None):
         """-> uint8 device tensor [n, max_plies] by absolute ply: 1 where a recorded ply was searched in full, 0 elsewhere (a
@@ -796,12 +807,17 @@ class SelfPlayStream:
     set_evaluator(ev) swaps the network between takes.  Games in flight go on under the new network from the next tick and
     keep their search trees - a game that straddles the swap was searched partly with the old and partly with the new net
     (the usual semantics of asynchronous self-play, and the one place where a streamed game is not what a closed generation
-    would have played)."""
+    would have played).
 
-    def __init__(self, engine, evaluator, seed=None, use_graph=True, ticks_per_graph=16, check_every=32):
+    forced_playouts=k or (k, prune): SelfPlayEngine.set_forced_playouts before the stream begins (an engine that already carries
+    the setting streams with it as well: the pruned counts travel in the records themselves)."""
+
+    def __init__(self, engine, evaluator, seed=None, use_graph=True, ticks_per_graph=16, check_every=32, forced_playouts=None):
         self.engine, self.evaluator = engine, evaluator
         self.use_graph, self.check_every = bool(use_graph), max(1, int(check_every))
         self.ticks_per_graph = min(max(1, int(ticks_per_graph)), self.check_every)
+        if forced_playouts is not None:
+            engine.set_forced_playouts(*(forced_playouts if isinstance(forced_playouts, (tuple, list)) else (forced_playouts,)))
         engine.stream_begin(seed)
         self.obs, self.pri, self.val = engine.alloc_io()
         self.taken = 0          # games handed over so far = the id of the next one

@@ -103,8 +103,39 @@ class ExampleGenerator:
             if self.overlap > 1:
                 raise ValueError("playout_cap is not supported with overlap > 1: the capped generation is ticked on one stream")
 
+        # forced_playouts=k or (k, prune): forced playouts at the root and policy target pruning (SelfPlayEngine.set_forced_playouts)
+        # in every full search.  The pruned counts sit where the raw ones sat, so every path carries them: the setting goes to
+        # EVERY engine this generator builds (pools, ranks, overlap, the stream of continuous=True).
+        self.forced_playouts = kwargs.get("forced_playouts")
+        if self.forced_playouts is not None:
+            fp = self.forced_playouts
+            try:
+                k, prune = (fp if isinstance(fp, (tuple, list)) else (fp, True))
+                k = float(k)
+            except (TypeError, ValueError):
+                raise ValueError("forced_playouts must be k or a pair (k, prune), got %r" % (fp,))
+            if not (0.0 <= k < float("inf")) or prune not in (0, 1, False, True):
+                raise ValueError("forced_playouts needs a finite k >= 0 and prune False / True, got %r" % (fp,))
+            if self.is_test:
+                raise ValueError("forced_playouts is a self-play setting: it is not supported with is_test=True (evaluation games "
+                                 "record no policy target)")
+            if not kwargs.get("use_puct", True):
+                raise ValueError("forced_playouts is not supported with use_puct=False: the rules are stated for the PUCT value")
+            self.forced_playouts = (k, bool(prune)) if k > 0.0 else None
+
     def _engine_kwargs(self):
         return {k: self.kwargs[k] for k in _ENGINE_KW if k in self.kwargs}
+
+    def _new_engine(self, n_slots, **kw):
+        """A self-play engine with this generator's search settings (forced_playouts among them; reset() comes after)."""
+        engine = SelfPlayEngine(self.game, n_slots, **kw, **self._engine_kwargs())
+        if self.forced_playouts is not None:
+            try:
+                engine.set_forced_playouts(*self.forced_playouts)
+            except Exception:
+                close_all(engine)
+                raise
+        return engine
 
     def _pool_device_list(self):
         """Devices of the reference's pools when this one process drives several GPUs, else None (one engine)."""
@@ -132,8 +163,8 @@ class ExampleGenerator:
         try:
             for i, dev in enumerate(devices):
                 with torch.cuda.device(dev):
-                    engines.append(SelfPlayEngine(self.game, n_slots, max_games=n_each, device=dev,
-                                                  seed=self.seed + 1000003 * self._generation + 7919 * i, **self._engine_kwargs()))
+                    engines.append(self._new_engine(n_slots, max_games=n_each, device=dev,
+                                                    seed=self.seed + 1000003 * self._generation + 7919 * i))
                     net = self.net if self.eval_backend == "fused" else copy.deepcopy(self.net)  # a torch pool gets its own copy
                     evaluators.append(make_evaluator(net, dev, self.eval_backend, self.eval_precision, n_slots, self.eval_dtype))
             progs = run_selfplay_pools(engines, evaluators, n_each, use_graph=self.use_graph)
@@ -171,8 +202,8 @@ class ExampleGenerator:
         if self._stream is None:
             n_slots = int(self.n_slots or min(n_local, 4096))
             cap = stream_capacity(n_local, n_slots, self.stream_capacity)
-            engine = SelfPlayEngine(self.game, n_slots, max_games=cap, device=self.device, seed=self.seed + 7919 * rank,
-                                    **self._engine_kwargs())  # (the seed of a first closed generation: same games, id for id)
+            engine = self._new_engine(n_slots, max_games=cap, device=self.device,
+                                      seed=self.seed + 7919 * rank)  # (the seed of a first closed generation: same games, id for id)
             evaluator = None
             try:
                 evaluator = make_evaluator(self.net, self.device, self.eval_backend, self.eval_precision, n_slots, self.eval_dtype)
@@ -237,8 +268,7 @@ class ExampleGenerator:
         carries "keep", the host copy of the mask of full-search moves, and the store takes only those moves (append_engine)."""
         n = int(n_games)
         n_slots = int(self.n_slots or min(n, 4096))
-        engine = SelfPlayEngine(self.game, n_slots, max_games=n, device=self.device,
-                                seed=self.seed + 1000003 * self._generation, **self._engine_kwargs())
+        engine = self._new_engine(n_slots, max_games=n, device=self.device, seed=self.seed + 1000003 * self._generation)
         evaluator = None
         try:
             if fork is not None:
@@ -282,8 +312,8 @@ class ExampleGenerator:
             self.net = self.net.to(self.device)
             azdist.broadcast_net(self.net, src=0)
         n_slots = int(self.n_slots or min(n_local, 4096))
-        engine = SelfPlayEngine(self.game, n_slots, max_games=n_local, device=self.device,
-                                seed=self.seed + 1000003 * self._generation + 7919 * rank, **self._engine_kwargs())
+        engine = self._new_engine(n_slots, max_games=n_local, device=self.device,
+                                  seed=self.seed + 1000003 * self._generation + 7919 * rank)
         evaluators = []
         try:
             sizes = [n for _, n in slot_groups(n_slots, self.overlap)] if self.overlap > 1 else [n_slots]

@@ -53,7 +53,12 @@ def main():
     ap.add_argument("--playout-cap", default=None, metavar="N_FAST:P_FULL",
                     help="playout cap randomisation: every move is searched with --playouts playouts with probability P_FULL and "
                          "with N_FAST otherwise, and only the full-search moves are trained on (e.g. 25:0.25; not with --continuous)")
+    ap.add_argument("--forced-playouts", type=float, default=0.0, metavar="K",
+                    help="forced playouts at the root and policy target pruning (KataGo, section 3.2) in every full search: a tried "
+                         "root child gets at least sqrt(K P N) visits, and the visits it did not earn leave the recorded pi (e.g. 2)")
     a = ap.parse_args()
+    if not 0.0 <= a.forced_playouts < float("inf"):
+        ap.error("--forced-playouts takes a finite K >= 0")
     cap = None
     if a.playout_cap:
         if a.continuous:
@@ -73,7 +78,8 @@ def main():
     generator, before = None, {"moves": 0, "sims": 0}
     if a.continuous:
         generator = ExampleGenerator(net, a.game, dev, continuous=True, n_slots=min(a.games, 4096), n_playouts=a.playouts,
-                                     backup=a.backup, eval_precision=a.precision, seed=1)
+                                     backup=a.backup, eval_precision=a.precision, seed=1,
+                                     forced_playouts=a.forced_playouts or None)
     for gen in range(1, a.generations + 1):
         t0 = time.perf_counter()
         net.eval()
@@ -86,6 +92,8 @@ def main():
         else:
             eng = E.SelfPlayEngine(game, min(a.games, 4096), n_playouts=a.playouts, backup=a.backup, max_games=a.games,
                                    device=dev, seed=gen)
+            if a.forced_playouts:
+                eng.set_forced_playouts(a.forced_playouts)                 # the records then hold the pruned counts
             if cap is not None:
                 eng.set_playout_cap(*cap)                                  # append_engine below keeps the full-search moves only
             prog = E.run_selfplay(eng, FusedNet(net, dev, max_boards=eng.G, precision=a.precision), a.games, use_graph=True)

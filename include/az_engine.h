@@ -299,6 +299,35 @@ int az_engine_set_playout_cap(az_engine *e, int32_t n_fast, double p_full);
 int az_engine_full_moves_device(az_engine *e, uint8_t *full_out_dev, int64_t n_games, void *stream);
 
 /*
+ * Forced playouts and policy target pruning (KataGo: Wu 2019, section 3.2) for SELF-PLAY: with root noise on, a root child that
+ * has been tried gets a minimum number of visits in proportion to its (noised) prior, so the search finds out whether a move the
+ * noise promoted is good; the visits it did not earn are then taken out of the recorded policy target again.  The reference has
+ * no counterpart; with nothing set every kernel computes what it computed before, bit for bit.
+ *
+ * az_engine_set_forced_playouts: plain PUCT self-play engines only (arena_agent == AZ_ARENA_SELF_PLAY, manual_moves == 0,
+ *   select_rule == AZ_SELECT_PUCT; closed generations and stream mode alike): the others return AZ_E_INVALID and az_last_error
+ *   names the reason.  k finite and >= 0 (k == 0 clears the setting), prune 0 or 1.  Call it before az_engine_reset or
+ *   az_engine_stream_begin (the next call the engine accepts): it holds for every later generation, and composes with a start
+ *   prefix, a game-start table, a playout cap, both rng_modes and keep_search_tree.
+ * Which searches: full ones.  Under a playout cap a fast move is searched and recorded exactly as without forcing; with no cap
+ *   every search is full.
+ * Forcing: at depth 0 of every playout, a root child with n > 0 visits, prior P (the node's own, after noise) and root count N
+ *   (the parent count of the PUCT term, mcts.py:78) is forced iff (double)n * (double)n < (k * P) * (double)N in f64, i.e.
+ *   n < sqrt(k P N) without a sqrt rounding.  A forced child's selection value is +infinity, so the first-maximum rule picks the
+ *   lowest forced child.  A NaN prior makes the comparison false (AZ_FAULT_BAD_PRIOR is raised as before).
+ * Pruning (prune == 1): once per full move, after the move has been chosen from the RAW counts (temperature, sampling, argmax
+ *   and the value targets do not change) and before the record is written.  N = the root's count, b = the first child with the
+ *   largest raw n, U(i) = (c_puct * P_i) * sqrt((double)N), V = Q_b + U(b) / (double)(n_b + 1).  For every child i != b with
+ *   n_i > 0: F_i = the largest integer f >= 0 with (double)f * (double)f <= (k * P_i) * (double)N; lo_i = max(n_i - F_i, 0);
+ *   m_i = the smallest integer in [lo_i, n_i] such that Q_i + U(i) / (double)(n + 1) < V for every n with m_i <= n < n_i; if
+ *   m_i < n_i and m_i == 1 then m_i = 0.  Child b keeps n_b, an unvisited child stays 0.
+ * Records: the child_visits row of a full move holds m WHERE THE RAW COUNTS WERE WRITTEN before; the raw counts are not kept.
+ *   The packed export, az_example_view, az_engine_stream_take_device and every az_replay_append_* entry therefore carry the
+ *   pruned target with no change.  With prune == 0 the records hold raw counts.  az_progress counts the playouts that were run.
+ */
+int az_engine_set_forced_playouts(az_engine *e, double k, int32_t prune);
+
+/*
  * One tick = MCTS.playout's select + expand + backup (mcts.py:126-153) for all slots, fused with the
  * agent's move step when a slot has finished its S playouts (alphazerobot.py:71-93,
  * game_utils.py:156-197, mcts.py:155-162,192-203) and the root Dirichlet expansion (mcts.py:182-190):
