@@ -295,8 +295,10 @@ class FusedNet:
     """Device handle: az_net_create / az_net_forward.  Call signature matches engine.DeviceEvaluator:
     evaluator(obs, priors_out, values_out)."""
 
-    def __init__(self, net, device, max_boards=4096, precision="f32x", *, packed=None):
-        """packed (tests only): a pack_net dict to hand to az_net_create in place of pack_net(net)'s."""
+    def __init__(self, net, device, max_boards=4096, precision="f32x", *, packed=None, wide=None):
+        """packed (tests only): a pack_net dict to hand to az_net_create in place of pack_net(net)'s.
+        wide (tests only): True skips pack_net and az_net_create and hands the net straight to az_net_create_wide, so that a net the
+        tuned kernels would take runs on the general path; None (the default) leaves the routing below alone."""
         from . import _lib
         if precision not in PRECISIONS:
             raise ValueError("precision must be one of %s" % (PRECISIONS,))
@@ -311,7 +313,7 @@ class FusedNet:
         # Routing: the tuned kernels (pack_net + az_net_create) whenever they take the net; the general layer-by-layer path
         # (az_net_create_wide) when pack_net refuses it (more than CPAD filters) or az_net_create does (conv weight range,
         # LDS budget: AZ_E_INVALID; a refused az_net_create frees what it allocated)
-        self.wide = net.n_filts > CPAD
+        self.wide = net.n_filts > CPAD or wide is True
         self._h = C.c_void_p()
         if not self.wide:
             self.packed = pack_net(net) if packed is None else packed

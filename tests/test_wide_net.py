@@ -26,13 +26,21 @@ def _drifted(net, seed):
     return net.eval()
 
 
-@pytest.mark.parametrize("shape,A,n_blocks,F", [([3, 6, 7], 7, 2, 64), ([3, 6, 6], 432, 2, 96), ([3, 5, 4], 240, 2, 128)])
+@pytest.mark.parametrize("shape,A,n_blocks,F", [
+    ([3, 6, 7], 7, 2, 64), ([3, 6, 6], 432, 2, 96), ([3, 5, 4], 240, 2, 128),
+    # the shapes of test_wide_net_edges_gpu: 3 and 1 input planes, fewer filters than input planes (arrays strided by C = 4), one
+    # filter, a 5x5 board with 65 filters, 63 cells with 255 filters and a single block
+    ([2, 6, 7], 7, 2, 70), ([0, 5, 4], 20, 2, 96), ([3, 6, 7], 7, 2, 3), ([3, 6, 7], 7, 2, 1), ([3, 5, 5], 300, 2, 65),
+    ([3, 7, 9], 63, 1, 255),
+])
 def test_fold_forward_matches_torch_fp64(shape, A, n_blocks, F):
     torch.manual_seed(F)
     net = _drifted(Net(shape, A, n_blocks=n_blocks, n_filters=F), F)
     obs = np.random.RandomState(F).randint(0, 2, size=(5, shape[0] + 1, shape[1], shape[2])).astype(np.float64)
     f = fusednet.fold_net(net)
-    assert f["conv_w"].shape == (2 * n_blocks, F, F, 3, 3) and f["skip_w"].shape == (F, shape[0] + 1)
+    C = max(F, shape[0] + 1)  # the conv arrays' input-channel stride
+    assert f["conv_w"].shape == (2 * n_blocks, F, C, 3, 3) and f["skip_w"].shape == (F, shape[0] + 1)
+    assert f["bn1_scale"].shape == (n_blocks, C) and not f["conv_w"][1:, :, F:].any()
     p, v, tower = fusednet.fold_forward(f, obs)
     ref = net.double()
     with torch.no_grad():
@@ -54,6 +62,16 @@ def test_fold_keeps_a_narrow_net_identity_skip():
         tp, tv = net.double()(torch.from_numpy(obs))
     p, v, _ = fusednet.fold_forward(f, obs)
     np.testing.assert_allclose(p, tp.numpy(), atol=1e-12)
+
+
+@pytest.mark.parametrize("wide", [True, False, 1])
+def test_the_wide_keyword_leaves_the_device_check_first(wide):
+    """FusedNet's tests-only wide= changes nothing before the routing: on a CPU device the error is the one it always was."""
+    net = Net([3, 6, 7], 7, n_blocks=1, n_filters=8).eval()
+    with pytest.raises(RuntimeError, match="needs a HIP device"):
+        fusednet.FusedNet(net, "cpu", wide=wide)
+    with pytest.raises(RuntimeError, match="needs a HIP device"):
+        fusednet.FusedNet(net, "cpu")
 
 
 def test_wide_desc_ctypes_layout_matches_c(tmp_path):
