@@ -1594,20 +1594,6 @@ template <typename T> static int dalloc(az_engine *e, T **out, size_t count) {
     return AZ_OK;
 }
 
-static void pw_build(PwPlan &pw, int lo, int n) { // numpy pairwise_sum recursion (PW_BLOCKSIZE 128)
-    if (n <= 128) {
-        pw.lo[pw.n_blocks] = lo;
-        pw.len[pw.n_blocks] = n;
-        pw.ops[pw.n_ops++] = pw.n_blocks++;
-        return;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    pw_build(pw, lo, n2);
-    pw_build(pw, lo + n2, n - n2);
-    pw.ops[pw.n_ops++] = -1;
-}
-
 extern "C" const char *az_last_error(const az_engine *e) { return e ? e->err.c_str() : g_create_err.c_str(); }
 
 extern "C" int az_engine_destroy(az_engine *e) {
@@ -1926,12 +1912,10 @@ extern "C" int64_t az_engine_stream_ready(az_engine *e, void *stream) {
     return (int64_t)k;
 }
 
-static void export_offsets(size_t n, size_t mp, size_t mc, size_t off[9]);
-
 extern "C" int64_t az_engine_stream_take_bytes(const az_engine *e, int64_t n_games) {
     if (!e || n_games < 1 || n_games > e->cfg.max_games) return AZ_E_INVALID;
     size_t off[9];
-    export_offsets((size_t)n_games, (size_t)e->p.max_plies, (size_t)e->p.maxc, off);
+    records_offsets((size_t)n_games, (size_t)e->p.max_plies, (size_t)e->p.maxc, off);
     return (int64_t)off[8];
 }
 
@@ -1949,18 +1933,12 @@ __device__ __forceinline__ void take_copy(char *__restrict__ dst, const char *__
         for (size_t i = (size_t)tid; i < bytes; i += n_threads) dst[i] = src[i];
     }
 }
-struct TakeOut { // the eight arrays of the packed layout, inside the caller's buffer
-    int *game_len;
-    float *game_ret0;
-    char *states, *move, *nchild, *child_action, *child_visits;
-    double *value;
-};
 // az_engine_stream_take_device: a workgroup per game.  Game first + j leaves row (first + j) % max_games of the ring for row j
 // of the packed arrays; its on-policy value targets are formed here from the result (game_utils.py:200-204: z_i = returns()[0] *
 // (-1)^i); the row's length is cleared (the mark of a finished game: az_engine_stream_ready), and the hand-out limit rises to
 // new_limit - the tick kernels that follow on the stream may hand out the ids whose rows this launch has just freed.
 #define TAKE_THREADS 256
-__global__ __launch_bounds__(TAKE_THREADS) void az_stream_take_kernel(Params p, TakeOut o, unsigned long long first, int n,
+__global__ __launch_bounds__(TAKE_THREADS) void az_stream_take_kernel(Params p, AzRecords o, unsigned long long first, int n,
                                                                       unsigned long long new_limit, int on_policy) {
     const int j = blockIdx.x, tid = threadIdx.x;
     if (j >= n) return;
@@ -1968,11 +1946,11 @@ __global__ __launch_bounds__(TAKE_THREADS) void az_stream_take_kernel(Params p, 
     const size_t mp = (size_t)p.max_plies, mc = (size_t)p.maxc;
     const int len = p.rec_len[r];
     const float ret0 = p.rec_ret0[r];
-    take_copy(o.states + (size_t)j * mp * 16, (const char *)p.rec_states + r * mp * 16, mp * 16, tid, TAKE_THREADS);
-    take_copy(o.move + (size_t)j * mp * 2, (const char *)p.rec_move + r * mp * 2, mp * 2, tid, TAKE_THREADS);
-    take_copy(o.nchild + (size_t)j * mp, (const char *)p.rec_nchild + r * mp, mp, tid, TAKE_THREADS);
-    take_copy(o.child_action + (size_t)j * mp * mc * 2, (const char *)p.rec_child_action + r * mp * mc * 2, mp * mc * 2, tid, TAKE_THREADS);
-    take_copy(o.child_visits + (size_t)j * mp * mc * 4, (const char *)p.rec_child_visits + r * mp * mc * 4, mp * mc * 4, tid, TAKE_THREADS);
+    take_copy((char *)o.states + (size_t)j * mp * 16, (const char *)p.rec_states + r * mp * 16, mp * 16, tid, TAKE_THREADS);
+    take_copy((char *)o.move + (size_t)j * mp * 2, (const char *)p.rec_move + r * mp * 2, mp * 2, tid, TAKE_THREADS);
+    take_copy((char *)o.n_children + (size_t)j * mp, (const char *)p.rec_nchild + r * mp, mp, tid, TAKE_THREADS);
+    take_copy((char *)o.child_action + (size_t)j * mp * mc * 2, (const char *)p.rec_child_action + r * mp * mc * 2, mp * mc * 2, tid, TAKE_THREADS);
+    take_copy((char *)o.child_visits + (size_t)j * mp * mc * 4, (const char *)p.rec_child_visits + r * mp * mc * 4, mp * mc * 4, tid, TAKE_THREADS);
     const int p0 = p.start.ply;
     for (int i = tid; i < (int)mp; i += TAKE_THREADS) {
         double v = p.rec_value[r * mp + i];
@@ -1997,7 +1975,7 @@ extern "C" int az_engine_stream_take_device(az_engine *e, int64_t n_games, void 
         return AZ_E_INVALID;
     }
     size_t off[9];
-    export_offsets((size_t)n_games, (size_t)e->p.max_plies, (size_t)e->p.maxc, off);
+    records_offsets((size_t)n_games, (size_t)e->p.max_plies, (size_t)e->p.maxc, off);
     if (bytes < (int64_t)off[8]) {
         e->err = "az_engine_stream_take_device: buffer of " + std::to_string(bytes) + " bytes is smaller than az_engine_stream_take_bytes(" +
                  std::to_string(n_games) + ") = " + std::to_string(off[8]);
@@ -2009,8 +1987,7 @@ extern "C" int az_engine_stream_take_device(az_engine *e, int64_t n_games, void 
         return AZ_E_STATE;
     }
     HIPCHK(e, hipSetDevice(e->cfg.device));
-    char *b = (char *)dev_buf;
-    TakeOut o = {(int *)(b + off[0]), (float *)(b + off[1]), b + off[2], b + off[3], b + off[4], b + off[5], b + off[6], (double *)(b + off[7])};
+    AzRecords o = records_in(dev_buf, (size_t)n_games, (size_t)e->p.max_plies, (size_t)e->p.maxc);
     int64_t limit = e->read_pos + n_games + e->cfg.max_games;
     if (limit > AZ_STREAM_MAX_ID) limit = AZ_STREAM_MAX_ID;
     hipLaunchKernelGGL(az_stream_take_kernel, dim3((unsigned)n_games), dim3(TAKE_THREADS), 0, (hipStream_t)stream, e->p, o,
@@ -2767,50 +2744,41 @@ extern "C" int az_engine_export(az_engine *e, az_example_view *out, void *stream
     HIPCHK(e, hipSetDevice(e->cfg.device));
     HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
     size_t ng = (size_t)e->n_games, mp = (size_t)e->p.max_plies, mc = (size_t)e->p.maxc;
-    e->h_len.resize(ng); e->h_ret0.resize(ng); e->h_states.resize(ng * mp * 2); e->h_move.resize(ng * mp);
-    e->h_nchild.resize(ng * mp); e->h_child_action.resize(ng * mp * mc); e->h_child_visits.resize(ng * mp * mc);
-    e->h_value.resize(ng * mp);
-    HIPCHK(e, hipMemcpy(e->h_len.data(), e->p.rec_len, ng * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIPCHK(e, hipMemcpy(e->h_ret0.data(), e->p.rec_ret0, ng * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(e, hipMemcpy(e->h_states.data(), e->p.rec_states, ng * mp * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIPCHK(e, hipMemcpy(e->h_move.data(), e->p.rec_move, ng * mp * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    HIPCHK(e, hipMemcpy(e->h_nchild.data(), e->p.rec_nchild, ng * mp, hipMemcpyDeviceToHost));
-    HIPCHK(e, hipMemcpy(e->h_child_action.data(), e->p.rec_child_action, ng * mp * mc * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    HIPCHK(e, hipMemcpy(e->h_child_visits.data(), e->p.rec_child_visits, ng * mp * mc * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIPCHK(e, hipMemcpy(e->h_value.data(), e->p.rec_value, ng * mp * sizeof(double), hipMemcpyDeviceToHost));
+    size_t sizes[AZ_RECORD_ARRAYS], off[AZ_RECORD_ARRAYS + 1];
+    records_sizes(ng, mp, mc, sizes);
+    records_offsets(ng, mp, mc, off);
+    e->h_records.resize(off[AZ_RECORD_ARRAYS] / 16);
+    const AzRecords h = records_in(e->h_records.data(), ng, mp, mc);
+    void *src[AZ_RECORD_ARRAYS], *dst[AZ_RECORD_ARRAYS];
+    records_ptrs(records_of(e->p), src);
+    records_ptrs(h, dst);
+    for (int i = 0; i < AZ_RECORD_ARRAYS; i++) HIPCHK(e, hipMemcpy(dst[i], src[i], sizes[i], hipMemcpyDeviceToHost));
     if (e->cfg.backup == AZ_BACKUP_ON_POLICY) // game_utils.py:200-204
         for (size_t g = 0; g < ng; g++) {
             const int p0 = e->game_starts ? e->h_start_ply[g] : e->p.start.ply; // the game's own start ply when a table is set
-            double reward = (double)e->h_ret0[g];
+            double reward = (double)h.game_ret0[g];
             if (p0 & 1) reward = -reward; // first recorded ply is player 1's
-            for (int i = 0; i < e->h_len[g]; i++) {
-                e->h_value[g * mp + (size_t)p0 + i] = reward;
+            for (int i = 0; i < h.game_len[g]; i++) {
+                h.value[g * mp + (size_t)p0 + i] = reward;
                 reward *= -1;
             }
         }
     out->n_games = (int64_t)ng;
     out->max_plies = (int32_t)mp;
     out->max_children = (int32_t)mc;
-    out->game_len = e->h_len.data();
-    out->game_ret0 = e->h_ret0.data();
-    out->states = e->h_states.data();
-    out->move = e->h_move.data();
-    out->n_children = e->h_nchild.data();
-    out->child_action = e->h_child_action.data();
-    out->child_visits = e->h_child_visits.data();
-    out->value = e->h_value.data();
+    out->game_len = h.game_len;
+    out->game_ret0 = h.game_ret0;
+    out->states = h.states;
+    out->move = h.move;
+    out->n_children = h.n_children;
+    out->child_action = h.child_action;
+    out->child_visits = h.child_visits;
+    out->value = h.value;
     return AZ_OK;
 }
 
 // ---- device-resident export: the generation's records packed into ONE caller-owned device buffer ----------------------
-// layout (every array 16-byte aligned, n = games of the generation, mp = max_plies, mc = max_children):
-//   game_len i32[n] | game_ret0 f32[n] | states u64[n][mp][2] | move u16[n][mp] | n_children u8[n][mp] |
-//   child_action u16[n][mp][mc] | child_visits u32[n][mp][mc] | value f64[n][mp]
-static void export_offsets(size_t n, size_t mp, size_t mc, size_t off[9]) {
-    const size_t sizes[8] = {n * 4, n * 4, n * mp * 16, n * mp * 2, n * mp, n * mp * mc * 2, n * mp * mc * 4, n * mp * 8};
-    off[0] = 0;
-    for (int i = 0; i < 8; i++) off[i + 1] = off[i] + ((sizes[i] + 15) & ~(size_t)15);
-}
+// (the layout: csrc/az_records.h)
 
 // start_plies: the games' own start plies (a game-start table), or null = start_ply for every game
 __global__ void fill_on_policy_values_kernel(const int *len, const float *ret0, double *value, int n_games, int max_plies, int start_ply,
@@ -2827,7 +2795,7 @@ extern "C" int64_t az_engine_export_device_bytes(const az_engine *e) {
     if (!e) return AZ_E_INVALID;
     if (refuse_in_stream(const_cast<az_engine *>(e), "az_engine_export_device_bytes")) return AZ_E_STATE; // (only the error text is written)
     size_t off[9];
-    export_offsets((size_t)e->n_games, (size_t)e->p.max_plies, (size_t)e->p.maxc, off);
+    records_offsets((size_t)e->n_games, (size_t)e->p.max_plies, (size_t)e->p.maxc, off);
     return (int64_t)off[8];
 }
 
@@ -2835,7 +2803,7 @@ extern "C" int az_engine_export_device(az_engine *e, void *dev_buf, int64_t byte
     if (!e || !dev_buf) return AZ_E_INVALID;
     if (refuse_in_stream(e, "az_engine_export_device")) return AZ_E_STATE;
     size_t n = (size_t)e->n_games, mp = (size_t)e->p.max_plies, mc = (size_t)e->p.maxc, off[9];
-    export_offsets(n, mp, mc, off);
+    records_offsets(n, mp, mc, off);
     if (bytes < (int64_t)off[8]) {
         e->err = "az_engine_export_device: buffer smaller than az_engine_export_device_bytes()";
         return AZ_E_INVALID;
@@ -2848,11 +2816,12 @@ extern "C" int az_engine_export_device(az_engine *e, void *dev_buf, int64_t byte
                            e->p.rec_ret0, e->p.rec_value, (int)n, (int)mp, e->p.start.ply, e->game_starts ? e->d_start_ply : nullptr);
         HIPCHK(e, hipGetLastError());
     }
-    char *b = (char *)dev_buf;
-    const void *src[8] = {e->p.rec_len, e->p.rec_ret0, e->p.rec_states, e->p.rec_move, e->p.rec_nchild, e->p.rec_child_action,
-                          e->p.rec_child_visits, e->p.rec_value};
-    const size_t sizes[8] = {n * 4, n * 4, n * mp * 16, n * mp * 2, n * mp, n * mp * mc * 2, n * mp * mc * 4, n * mp * 8};
-    for (int i = 0; i < 8; i++) HIPCHK(e, hipMemcpyAsync(b + off[i], src[i], sizes[i], hipMemcpyDeviceToDevice, st));
+    size_t sizes[AZ_RECORD_ARRAYS];
+    records_sizes(n, mp, mc, sizes);
+    void *src[AZ_RECORD_ARRAYS], *dst[AZ_RECORD_ARRAYS];
+    records_ptrs(records_of(e->p), src);
+    records_ptrs(records_in(dev_buf, n, mp, mc), dst);
+    for (int i = 0; i < AZ_RECORD_ARRAYS; i++) HIPCHK(e, hipMemcpyAsync(dst[i], src[i], sizes[i], hipMemcpyDeviceToDevice, st));
     return AZ_OK;
 }
 

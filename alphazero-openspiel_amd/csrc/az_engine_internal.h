@@ -9,6 +9,7 @@
 #include "../../include/az_engine.h"
 #include "az_games.h"
 #include "az_keychain.h"
+#include "az_records.h"
 
 #define NONE32 0xFFFFFFFFu
 
@@ -32,6 +33,19 @@ struct PwPlan { // numpy pairwise-sum recursion for a length-A vector, flattened
     int n_ops;
     int ops[32]; // >=0: push block i, -1: add top two
 };
+static inline void pw_build(PwPlan &pw, int lo, int n) { // numpy pairwise_sum recursion (PW_BLOCKSIZE 128)
+    if (n <= 128) {
+        pw.lo[pw.n_blocks] = lo;
+        pw.len[pw.n_blocks] = n;
+        pw.ops[pw.n_ops++] = pw.n_blocks++;
+        return;
+    }
+    int n2 = n / 2;
+    n2 -= n2 % 8;
+    pw_build(pw, lo, n2);
+    pw_build(pw, lo + n2, n - n2);
+    pw.ops[pw.n_ops++] = -1;
+}
 
 // Playout cap randomisation, device side (one record per engine, written by az_engine_set_playout_cap).  az_engine_reset draws the
 // generation's schedule into `sched` (one byte per game id and absolute ply, 1 = full search: az_cap_schedule_kernel); a slot that
@@ -124,6 +138,10 @@ struct Params {
     double forced_k;
 };
 
+// The engine's own record arrays as a view (az_records.h); the tick kernel keeps reading p.rec_* itself.
+static inline AzRecords records_of(const Params &p) {
+    return AzRecords{p.rec_len, p.rec_ret0, p.rec_states, p.rec_move, p.rec_nchild, p.rec_child_action, p.rec_child_visits, p.rec_value};
+}
 
 struct az_engine {
     az_config cfg;
@@ -158,14 +176,9 @@ struct az_engine {
     int64_t ready_known = 0;  // ... and how many consecutive finished games the last az_engine_stream_ready found from there
     std::vector<int32_t> h_ring; // ... host copy of the rec_len ring for that scan
     bool may_compact = false; // a pool cannot hold a whole game: re-rooting may have to compact (launches carry extra workgroups)
-    // host mirrors for export
-    std::vector<int32_t> h_len;
-    std::vector<float> h_ret0;
-    std::vector<uint64_t> h_states;
-    std::vector<uint16_t> h_move, h_child_action;
-    std::vector<uint8_t> h_nchild;
-    std::vector<uint32_t> h_child_visits;
-    std::vector<double> h_value;
+    // az_engine_export's host copy of the records, in the packed layout (az_records.h); 16-byte elements keep it aligned
+    struct alignas(16) HostBlock { unsigned char b[16]; };
+    std::vector<HostBlock> h_records;
 };
 
 // The packed root export (layout: include/az_engine.h, az_engine_export_roots_device): written by az_engine.hip, read by the

@@ -82,20 +82,6 @@ extern "C" int az_replay_destroy(az_replay *r) {
     return AZ_OK;
 }
 
-static void pw_build_r(PwPlan &pw, int lo, int n) { // numpy pairwise_sum recursion (PW_BLOCKSIZE 128)
-    if (n <= 128) {
-        pw.lo[pw.n_blocks] = lo;
-        pw.len[pw.n_blocks] = n;
-        pw.ops[pw.n_ops++] = pw.n_blocks++;
-        return;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    pw_build_r(pw, lo, n2);
-    pw_build_r(pw, lo + n2, n - n2);
-    pw.ops[pw.n_ops++] = -1;
-}
-
 extern "C" int az_replay_create(const az_replay_config *cfg, az_replay **out) {
     if (!cfg || !out) {
         g_replay_err = "null argument";
@@ -125,7 +111,7 @@ extern "C" int az_replay_create(const az_replay_config *cfg, az_replay **out) {
     r->maxc = az_max_children(c.game, c.rows, c.cols);
     r->max_plies = az_max_plies(c.game, c.rows, c.cols);
     memset(&r->pw, 0, sizeof r->pw);
-    pw_build_r(r->pw, 0, r->A);
+    pw_build(r->pw, 0, r->A);
     r->cap = c.max_examples;
     r->capacity_games = c.max_games;
     if (hipSetDevice(c.device) != hipSuccess) {
@@ -184,14 +170,7 @@ extern "C" int az_replay_stats_get(az_replay *r, az_replay_stats *out) {
 __device__ __forceinline__ uint64_t mix64(uint64_t h, uint64_t v) { return az_key_mix64(h, v); } // (the device index draws use it too)
 
 struct AppendArgs {
-    // source (one generation of games, layout of az_example_view / the engine's record store), device pointers
-    const int *game_len;
-    const float *game_ret0;
-    const uint64_t *states;
-    const uint16_t *move, *child_action;
-    const uint8_t *nchild;
-    const uint32_t *child_visits;
-    const double *value;
+    AzRecords src; // one generation of games (the engine's record store, or a packed buffer), device pointers; read only
     const long long *dst_first; // [n_src_games] logical index of the game's first example, -1 = skip
     int n_src_games, max_plies, maxc, start_ply, A, on_policy;
     // a start per GAME (az_engine_set_game_starts, az_replay_append_device_starts): start_plies [n_src_games] replaces start_ply
@@ -265,7 +244,7 @@ __global__ void replay_append_kernel(AppendArgs a) {
     int g = (int)(t / a.max_plies), i = (int)(t % a.max_plies);
     if (g >= a.n_src_games) return;
     long long first = a.dst_first[g];
-    int len = a.game_len[g];
+    int len = a.src.game_len[g];
     if (first < 0 || i >= len) return;
     const int sp = a.start_plies ? a.start_plies[g] : a.start_ply;
     size_t src = (size_t)g * a.max_plies + sp + i;
@@ -276,17 +255,17 @@ __global__ void replay_append_kernel(AppendArgs a) {
         for (int j = 0; j < i; j++) rank += a.keep[src - i + j] != 0;
     }
     long long dst = (a.head + first + rank) % a.cap;
-    a.bb0[dst] = a.states[src * 2];
-    a.bb1[dst] = a.states[src * 2 + 1];
+    a.bb0[dst] = a.src.states[src * 2];
+    a.bb1[dst] = a.src.states[src * 2 + 1];
     a.ply[dst] = sp + i;
-    double zz = a.value[src];
+    double zz = a.src.value[src];
     if (a.on_policy) { // game_utils.py:200-204: z_i = returns()[0] * (-1)^i, i the ABSOLUTE ply
-        zz = (double)a.game_ret0[g];
+        zz = (double)a.src.game_ret0[g];
         if ((sp + i) & 1) zz = -zz;
     }
     a.z[dst] = zz;
-    int nc = a.nchild[src] < a.maxc ? a.nchild[src] : a.maxc;
-    pi_from_root_visits(a.pw, a.A, nc, a.child_visits + src * a.maxc, a.child_action + src * a.maxc, a.pi + (size_t)dst * a.A);
+    int nc = a.src.n_children[src] < a.maxc ? a.src.n_children[src] : a.maxc;
+    pi_from_root_visits(a.pw, a.A, nc, a.src.child_visits + src * a.maxc, a.src.child_action + src * a.maxc, a.pi + (size_t)dst * a.A);
 }
 
 // one thread per game: key chain over its moves (key of ply i = hash of the first i actions)
@@ -295,7 +274,7 @@ __global__ void replay_keys_kernel(AppendArgs a) {
     if (g >= a.n_src_games) return;
     long long first = a.dst_first[g];
     if (first < 0) return;
-    int len = a.game_len[g];
+    int len = a.src.game_len[g];
     const int sp = a.start_plies ? a.start_plies[g] : a.start_ply;
     size_t s0 = (size_t)g * a.max_plies + sp;
     // The two chains (az_keychain.h): the reference keys on the EXACT information-state string (train.py:177); (key, key2)
@@ -309,7 +288,7 @@ __global__ void replay_keys_kernel(AppendArgs a) {
         k.key2 = a.start_keys[2 * (size_t)g + 1];
         base = sp;
     } else if (len > 0) { // (a game without a recorded ply has no start state to read)
-        k = az_key_seed(sp, a.states[s0 * 2], a.states[s0 * 2 + 1]);
+        k = az_key_seed(sp, a.src.states[s0 * 2], a.src.states[s0 * 2 + 1]);
     }
     for (int i = 0, rank = 0; i < len; i++) { // (the chains step over EVERY move: a kept example carries the key of its full history)
         if (!a.keep || a.keep[s0 + i]) {
@@ -317,7 +296,7 @@ __global__ void replay_keys_kernel(AppendArgs a) {
             a.key2[(a.head + first + rank) % a.cap] = k.key2;
             rank++;
         }
-        k = az_key_step(k, (uint32_t)a.move[s0 + i], base + i + 1);
+        k = az_key_step(k, (uint32_t)a.src.move[s0 + i], base + i + 1);
     }
 }
 
@@ -335,14 +314,19 @@ static int append_common(az_replay *r, AppendArgs &a, const std::vector<int32_t>
         return AZ_E_INVALID;
     }
     r->epoch++; // from here on the indices of an earlier az_replay_gather_states may name other records
-    // make room in the example ring first (evict oldest games if the ring would overflow)
-    while (r->n + add > r->cap && !r->game_len.empty()) {
-        r->head = (r->head + r->game_len.front()) % r->cap;
-        r->n -= r->game_len.front();
-        for (auto &f : first)
-            if (f >= 0) f -= r->game_len.front();
+    auto drop_oldest = [r]() -> int32_t { // the oldest game leaves the ring; -> its length
+        const int32_t len = r->game_len.front();
+        r->head = (r->head + len) % r->cap;
+        r->n -= len;
         r->game_len.pop_front();
         r->dropped++;
+        return len;
+    };
+    // make room in the example ring first (evict oldest games if the ring would overflow)
+    while (r->n + add > r->cap && !r->game_len.empty()) {
+        const int32_t len = drop_oldest();
+        for (auto &f : first)
+            if (f >= 0) f -= len;
     }
     long long *d_first = nullptr;
     RCHK(r, hipMalloc((void **)&d_first, sizeof(long long) * first.size()));
@@ -369,12 +353,7 @@ static int append_common(az_replay *r, AppendArgs &a, const std::vector<int32_t>
         if (lens[g] > 0) r->game_len.push_back(lens[g]);
     r->n += add;
     // `while len(self.buffer) > self.n_games_buffer: del self.buffer[0]` (train.py:233-236)
-    while ((int64_t)r->game_len.size() > r->capacity_games) {
-        r->head = (r->head + r->game_len.front()) % r->cap;
-        r->n -= r->game_len.front();
-        r->game_len.pop_front();
-        r->dropped++;
-    }
+    while ((int64_t)r->game_len.size() > r->capacity_games) drop_oldest();
     r->n_unique = 0;
     return AZ_OK;
 }
@@ -420,14 +399,7 @@ extern "C" int az_replay_append_engine(az_replay *r, az_engine *e, void *stream)
     RCHK(r, hipMemcpy(lens.data(), e->p.rec_len, lens.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     AppendArgs a;
     memset(&a, 0, sizeof a);
-    a.game_len = e->p.rec_len;
-    a.game_ret0 = e->p.rec_ret0;
-    a.states = e->p.rec_states;
-    a.move = e->p.rec_move;
-    a.child_action = e->p.rec_child_action;
-    a.nchild = e->p.rec_nchild;
-    a.child_visits = e->p.rec_child_visits;
-    a.value = e->p.rec_value;
+    a.src = records_of(e->p);
     a.n_src_games = (int)e->n_games;
     a.max_plies = e->p.max_plies;
     a.maxc = e->p.maxc;
@@ -456,9 +428,9 @@ extern "C" int az_replay_append_engine(az_replay *r, az_engine *e, void *stream)
 }
 
 // A game length the kernels may run with: rows [start_ply, start_ply + len) of a record array with max_plies rows per game.
-static bool game_len_ok(az_replay *r, int64_t g, int32_t len, int32_t max_plies, int32_t start_ply) {
+static bool game_len_ok(az_replay *r, const char *what, int64_t g, int32_t len, int32_t max_plies, int32_t start_ply) {
     if (len >= 0 && len <= max_plies - start_ply) return true;
-    r->err = "game_len[" + std::to_string(g) + "] = " + std::to_string(len) + " is outside [0, max_plies - start_ply = " +
+    r->err = std::string(what) + ": game_len[" + std::to_string(g) + "] = " + std::to_string(len) + " is outside [0, max_plies - start_ply = " +
              std::to_string(max_plies - start_ply) + "]";
     return false;
 }
@@ -472,7 +444,7 @@ extern "C" int az_replay_append_host(az_replay *r, const az_example_view *v, int
     // everything the kernels index with is checked here, before any copy or launch: the store stays as it was
     for (int64_t g = 0; g < v->n_games; g++) {
         int32_t len = v->game_len[g];
-        if (!game_len_ok(r, g, len, v->max_plies, start_ply)) return AZ_E_INVALID;
+        if (!game_len_ok(r, "az_replay_append_host", g, len, v->max_plies, start_ply)) return AZ_E_INVALID;
         for (int32_t i = 0; i < len; i++) {
             size_t src = (size_t)g * v->max_plies + start_ply + i;
             int nc = v->n_children[src];
@@ -492,28 +464,23 @@ extern "C" int az_replay_append_host(az_replay *r, const az_example_view *v, int
     hipStream_t st = (hipStream_t)stream;
     RCHK(r, hipSetDevice(r->cfg.device));
     size_t ng = (size_t)v->n_games, mp = (size_t)v->max_plies, mc = (size_t)v->max_children;
-    size_t sizes[8] = {ng * 4, ng * 4, ng * mp * 16, ng * mp * 2, ng * mp * mc * 2, ng * mp, ng * mp * mc * 4, ng * mp * 8};
-    const void *srcs[8] = {v->game_len, v->game_ret0, v->states, v->move, v->child_action, v->n_children, v->child_visits, v->value};
-    size_t off[9] = {0};
-    for (int i = 0; i < 8; i++) off[i + 1] = off[i] + ((sizes[i] + 15) & ~(size_t)15);
-    if (off[8] > r->stage_bytes) {
+    size_t sizes[AZ_RECORD_ARRAYS], off[AZ_RECORD_ARRAYS + 1];
+    records_sizes(ng, mp, mc, sizes);
+    records_offsets(ng, mp, mc, off);
+    if (off[AZ_RECORD_ARRAYS] > r->stage_bytes) {
         (void)hipFree(r->stage);
         r->stage = nullptr;
-        RCHK(r, hipMalloc(&r->stage, off[8]));
-        r->stage_bytes = off[8];
+        r->stage_bytes = 0;
+        RCHK(r, hipMalloc(&r->stage, off[AZ_RECORD_ARRAYS]));
+        r->stage_bytes = off[AZ_RECORD_ARRAYS];
     }
-    for (int i = 0; i < 8; i++) RCHK(r, hipMemcpyAsync((char *)r->stage + off[i], srcs[i], sizes[i], hipMemcpyHostToDevice, st));
     AppendArgs a;
     memset(&a, 0, sizeof a);
-    char *b = (char *)r->stage;
-    a.game_len = (const int *)(b + off[0]);
-    a.game_ret0 = (const float *)(b + off[1]);
-    a.states = (const uint64_t *)(b + off[2]);
-    a.move = (const uint16_t *)(b + off[3]);
-    a.child_action = (const uint16_t *)(b + off[4]);
-    a.nchild = (const uint8_t *)(b + off[5]);
-    a.child_visits = (const uint32_t *)(b + off[6]);
-    a.value = (const double *)(b + off[7]);
+    a.src = records_in(r->stage, ng, mp, mc);
+    const void *srcs[AZ_RECORD_ARRAYS] = {v->game_len, v->game_ret0, v->states, v->move, v->n_children, v->child_action, v->child_visits, v->value};
+    void *dsts[AZ_RECORD_ARRAYS];
+    records_ptrs(a.src, dsts);
+    for (int i = 0; i < AZ_RECORD_ARRAYS; i++) RCHK(r, hipMemcpyAsync(dsts[i], srcs[i], sizes[i], hipMemcpyHostToDevice, st));
     a.n_src_games = (int)ng;
     a.max_plies = (int)mp;
     a.maxc = (int)mc;
@@ -523,99 +490,40 @@ extern "C" int az_replay_append_host(az_replay *r, const az_example_view *v, int
     return append_common(r, a, lens, st);
 }
 
-// The packed layout of az_engine_export_device (n_games games, the store's board geometry) as the source arrays of an append:
-// the ONE place the replay store spells that layout out.  on_policy = 0: az_engine_export_device has filled those targets in.
-static AppendArgs packed_export_args(const az_replay *r, const void *dev_buf, int64_t n_games) {
-    size_t ng = (size_t)n_games, mp = (size_t)r->max_plies, mc = (size_t)r->maxc;
-    const size_t sizes[8] = {ng * 4, ng * 4, ng * mp * 16, ng * mp * 2, ng * mp, ng * mp * mc * 2, ng * mp * mc * 4, ng * mp * 8};
-    size_t off[9] = {0};
-    for (int i = 0; i < 8; i++) off[i + 1] = off[i] + ((sizes[i] + 15) & ~(size_t)15);
-    const char *b = (const char *)dev_buf;
+// One body for the three device append entries.  dev_buf: a packed export of n_games games in the store's board geometry
+// (az_records.h; on_policy = 0: the export has filled those targets in).  start_ply_dev non-null = a start ply per game (replaces
+// start_ply), with keys_dev = the games' given key pairs or null; keep_dev non-null = a keep mask (kept_counts).  Everything the
+// kernels index with is read back and checked here, before any launch: a refused call leaves the store as it was.
+static int append_packed(az_replay *r, const char *what, const void *dev_buf, int64_t n_games, int32_t start_ply,
+                         const int32_t *start_ply_dev, const uint64_t *keys_dev, const uint8_t *keep_dev, hipStream_t st) {
+    if (!r) return AZ_E_INVALID;
+    if (!dev_buf || n_games < 1 || (!start_ply_dev && (start_ply < 0 || start_ply > r->max_plies))) {
+        r->err = std::string(what) + ": bad device export (null buffer, n_games < 1, or - without a start ply per game - start_ply outside "
+                 "[0, max_plies])";
+        return AZ_E_INVALID;
+    }
+    RCHK(r, hipSetDevice(r->cfg.device));
+    const size_t ng = (size_t)n_games;
     AppendArgs a;
     memset(&a, 0, sizeof a);
-    a.game_len = (const int *)(b + off[0]);
-    a.game_ret0 = (const float *)(b + off[1]);
-    a.states = (const uint64_t *)(b + off[2]);
-    a.move = (const uint16_t *)(b + off[3]);
-    a.nchild = (const uint8_t *)(b + off[4]);
-    a.child_action = (const uint16_t *)(b + off[5]);
-    a.child_visits = (const uint32_t *)(b + off[6]);
-    a.value = (const double *)(b + off[7]);
+    a.src = records_in(const_cast<void *>(dev_buf), ng, (size_t)r->max_plies, (size_t)r->maxc);
     a.n_src_games = (int)ng;
-    a.max_plies = (int)mp;
-    a.maxc = (int)mc;
-    return a;
-}
-
-extern "C" int az_replay_append_device(az_replay *r, const void *dev_buf, int64_t n_games, int32_t start_ply, void *stream) {
-    if (!r || !dev_buf || n_games < 1 || start_ply < 0 || start_ply > r->max_plies) {
-        if (r) r->err = "bad device export (null buffer, n_games < 1 or start_ply outside [0, max_plies])";
-        return AZ_E_INVALID;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    RCHK(r, hipSetDevice(r->cfg.device));
-    size_t ng = (size_t)n_games;
-    AppendArgs a = packed_export_args(r, dev_buf, n_games);
-    a.start_ply = start_ply;
-    std::vector<int32_t> lens(ng);
-    RCHK(r, hipMemcpyAsync(lens.data(), a.game_len, ng * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    RCHK(r, hipStreamSynchronize(st));
-    for (size_t g = 0; g < ng; g++) // before any launch: a length outside the record rows would run the kernels off the arrays
-        if (!game_len_ok(r, (int64_t)g, lens[g], r->max_plies, start_ply)) return AZ_E_INVALID;
-    return append_common(r, a, lens, st);
-}
-
-extern "C" int az_replay_append_device_starts(az_replay *r, const void *dev_buf, int64_t n_games, const int32_t *start_ply_dev,
-                                              const uint64_t *keys_dev, void *stream) {
-    if (!r || !dev_buf || !start_ply_dev || n_games < 1) {
-        if (r) r->err = "bad device export (null buffer, null start_ply_dev or n_games < 1)";
-        return AZ_E_INVALID;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    RCHK(r, hipSetDevice(r->cfg.device));
-    size_t ng = (size_t)n_games;
-    AppendArgs a = packed_export_args(r, dev_buf, n_games);
-    a.start_plies = start_ply_dev;
-    a.start_keys = keys_dev;
-    std::vector<int32_t> lens(ng), plies(ng);
-    RCHK(r, hipMemcpyAsync(lens.data(), a.game_len, ng * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    RCHK(r, hipMemcpyAsync(plies.data(), start_ply_dev, ng * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    RCHK(r, hipStreamSynchronize(st));
-    for (size_t g = 0; g < ng; g++) { // before any launch: rows [start_ply, start_ply + len) must lie inside the game's record rows
-        if (plies[g] < 0 || plies[g] > r->max_plies) {
-            r->err = "start_ply[" + std::to_string(g) + "] = " + std::to_string(plies[g]) + " is outside [0, max_plies = " +
-                     std::to_string(r->max_plies) + "]";
-            return AZ_E_INVALID;
-        }
-        if (!game_len_ok(r, (int64_t)g, lens[g], r->max_plies, plies[g])) return AZ_E_INVALID;
-    }
-    return append_common(r, a, lens, st);
-}
-
-extern "C" int az_replay_append_device_kept(az_replay *r, const void *dev_buf, int64_t n_games, int32_t start_ply,
-                                            const int32_t *start_ply_dev, const uint64_t *keys_dev, const uint8_t *keep_dev, void *stream) {
-    if (!r || !dev_buf || n_games < 1 || (!start_ply_dev && (start_ply < 0 || start_ply > r->max_plies))) {
-        if (r) r->err = "bad device export (null buffer, n_games < 1, or - without start_ply_dev - start_ply outside [0, max_plies])";
-        return AZ_E_INVALID;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    RCHK(r, hipSetDevice(r->cfg.device));
-    size_t ng = (size_t)n_games;
-    AppendArgs a = packed_export_args(r, dev_buf, n_games);
+    a.max_plies = r->max_plies;
+    a.maxc = r->maxc;
     a.start_ply = start_ply;
     a.start_plies = start_ply_dev;
     a.start_keys = keys_dev;
     std::vector<int32_t> lens(ng), plies(ng, start_ply);
-    RCHK(r, hipMemcpyAsync(lens.data(), a.game_len, ng * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    RCHK(r, hipMemcpyAsync(lens.data(), a.src.game_len, ng * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if (start_ply_dev) RCHK(r, hipMemcpyAsync(plies.data(), start_ply_dev, ng * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     RCHK(r, hipStreamSynchronize(st));
-    for (size_t g = 0; g < ng; g++) { // before any launch: rows [start_ply, start_ply + len) must lie inside the game's record rows
+    for (size_t g = 0; g < ng; g++) { // rows [start_ply, start_ply + len) must lie inside the game's record rows
         if (plies[g] < 0 || plies[g] > r->max_plies) {
-            r->err = "start_ply[" + std::to_string(g) + "] = " + std::to_string(plies[g]) + " is outside [0, max_plies = " +
-                     std::to_string(r->max_plies) + "]";
+            r->err = std::string(what) + ": start_ply[" + std::to_string(g) + "] = " + std::to_string(plies[g]) +
+                     " is outside [0, max_plies = " + std::to_string(r->max_plies) + "]";
             return AZ_E_INVALID;
         }
-        if (!game_len_ok(r, (int64_t)g, lens[g], r->max_plies, plies[g])) return AZ_E_INVALID;
+        if (!game_len_ok(r, what, (int64_t)g, lens[g], r->max_plies, plies[g])) return AZ_E_INVALID;
     }
     if (!keep_dev) return append_common(r, a, lens, st);
     std::vector<int32_t> kept;
@@ -623,6 +531,25 @@ extern "C" int az_replay_append_device_kept(az_replay *r, const void *dev_buf, i
     if (rc != AZ_OK) return rc;
     a.keep = keep_dev;
     return append_common(r, a, kept, st);
+}
+
+extern "C" int az_replay_append_device(az_replay *r, const void *dev_buf, int64_t n_games, int32_t start_ply, void *stream) {
+    return append_packed(r, "az_replay_append_device", dev_buf, n_games, start_ply, nullptr, nullptr, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int az_replay_append_device_starts(az_replay *r, const void *dev_buf, int64_t n_games, const int32_t *start_ply_dev,
+                                              const uint64_t *keys_dev, void *stream) {
+    if (r && !start_ply_dev) {
+        r->err = "az_replay_append_device_starts: null start_ply_dev";
+        return AZ_E_INVALID;
+    }
+    return append_packed(r, "az_replay_append_device_starts", dev_buf, n_games, 0, start_ply_dev, keys_dev, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int az_replay_append_device_kept(az_replay *r, const void *dev_buf, int64_t n_games, int32_t start_ply,
+                                            const int32_t *start_ply_dev, const uint64_t *keys_dev, const uint8_t *keep_dev, void *stream) {
+    return append_packed(r, "az_replay_append_device_kept", dev_buf, n_games, start_ply, start_ply_dev, keys_dev, keep_dev,
+                         (hipStream_t)stream);
 }
 
 // A fork: the positions of az_replay_gather_states with the stored history key pair of each example, the three inputs of

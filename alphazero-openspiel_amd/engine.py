@@ -446,6 +446,15 @@ def pack_histories(histories):
     return actions, lengths, stride
 
 
+def _packed_layout(spec):
+    """(name, dtype, shape) per array -> ([(name, dtype, shape, byte offset)], total bytes), every array 16-byte aligned."""
+    out, off = [], 0
+    for name, dt, shape in spec:
+        out.append((name, dt, shape, off))
+        off += (int(np.prod(shape)) * np.dtype(dt).itemsize + 15) & ~15
+    return out, off
+
+
 def roots_export_layout(n_slots, max_children):
     """(name, dtype, shape, byte offset) of every array in the packed root export (include/az_engine.h,
     az_engine_export_roots_device) + total bytes."""
@@ -454,11 +463,7 @@ def roots_export_layout(n_slots, max_children):
             ("sims_done", np.int32, (G,)), ("n_children", np.int32, (G,)), ("root_n", np.uint32, (G,)),
             ("root_q", np.float64, (G,)), ("child_action", np.int32, (G, mc)), ("child_n", np.uint32, (G, mc)),
             ("child_q", np.float64, (G, mc)), ("child_p", np.float64, (G, mc)))
-    out, off = [], 0
-    for name, dt, shape in spec:
-        out.append((name, dt, shape, off))
-        off += (int(np.prod(shape)) * np.dtype(dt).itemsize + 15) & ~15
-    return out, off
+    return _packed_layout(spec)
 
 
 def unpack_roots_export(host_bytes, n_slots, max_children):
@@ -488,11 +493,7 @@ def lines_export_layout(n_slots, max_depth):
     spec = (("header", np.int32, (4,)), ("game_id", np.int32, (G,)), ("phase", np.int32, (G,)), ("ply", np.int32, (G,)),
             ("depth", np.int32, (G,)), ("leaf_n", np.uint32, (G,)), ("value", np.float64, (G,)),
             ("line_action", np.int32, (G, D)), ("line_n", np.uint32, (G, D)), ("line_q", np.float64, (G, D)))
-    out, off = [], 0
-    for name, dt, shape in spec:
-        out.append((name, dt, shape, off))
-        off += (int(np.prod(shape)) * np.dtype(dt).itemsize + 15) & ~15
-    return out, off
+    return _packed_layout(spec)
 
 
 def read_lines(buf):
@@ -523,16 +524,12 @@ def read_lines(buf):
 
 
 def device_export_layout(n_games, max_plies, max_children):
-    """(name, dtype, shape, byte offset) of every array in the packed device export + total bytes."""
+    """(name, dtype, shape, byte offset) of every array in the packed device export (csrc/az_records.h) + total bytes."""
     n, mp, mc = int(n_games), int(max_plies), int(max_children)
     spec = (("game_len", np.int32, (n,)), ("game_ret0", np.float32, (n,)), ("states", np.uint64, (n, mp, 2)),
             ("move", np.uint16, (n, mp)), ("n_children", np.uint8, (n, mp)), ("child_action", np.uint16, (n, mp, mc)),
             ("child_visits", np.uint32, (n, mp, mc)), ("value", np.float64, (n, mp)))
-    out, off = [], 0
-    for name, dt, shape in spec:
-        out.append((name, dt, shape, off))
-        off += (int(np.prod(shape)) * np.dtype(dt).itemsize + 15) & ~15
-    return out, off
+    return _packed_layout(spec)
 
 
 def unpack_device_export(host_bytes, n_games, max_plies, max_children, start_ply=0):

@@ -101,32 +101,24 @@ class DeviceReplay:
         need = device_export_layout(n_games, self.game.max_game_length(), self.game.max_children())[1]
         if buf.numel() < need:
             raise RuntimeError("export buffer holds %d bytes, %d games need %d" % (buf.numel(), n_games, need))
-        if keep is not None:
-            n, per_game = int(n_games), torch.is_tensor(start_ply)
-            if keys is not None and not per_game:
-                raise ValueError("keys go with a start ply per game: give start_ply as an int32 tensor [n_games]")
-            for t, dt, shape in ((start_ply if per_game else None, torch.int32, (n,)), (keys, torch.int64, (n, 2)),
-                                 (keep, torch.uint8, (n, self.game.max_game_length()))):
-                if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != self.device or tuple(t.shape) != shape):
-                    raise RuntimeError("append_device expects a contiguous %s %s tensor on %s" % (dt, shape, self.device))
-            self._check(self.lib.az_replay_append_device_kept(
-                self._h, C.c_void_p(buf.data_ptr()), n, 0 if per_game else int(start_ply),
-                C.c_void_p(start_ply.data_ptr()) if per_game else None, C.c_void_p(keys.data_ptr()) if keys is not None else None,
-                C.c_void_p(keep.data_ptr()), self._stream()))
-            return
-        if not torch.is_tensor(start_ply):
-            if keys is not None:
-                raise ValueError("keys go with a start ply per game: give start_ply as an int32 tensor [n_games]")
-            self._check(self.lib.az_replay_append_device(self._h, C.c_void_p(buf.data_ptr()), int(n_games), int(start_ply),
-                                                         self._stream()))
-            return
-        n = int(n_games)
-        for t, dt, shape in ((start_ply, torch.int32, (n,)), (keys, torch.int64, (n, 2))):
+        n, per_game = int(n_games), torch.is_tensor(start_ply)
+        if keys is not None and not per_game:
+            raise ValueError("keys go with a start ply per game: give start_ply as an int32 tensor [n_games]")
+        for t, dt, shape in ((start_ply if per_game else None, torch.int32, (n,)), (keys, torch.int64, (n, 2)),
+                             (keep, torch.uint8, (n, self.game.max_game_length()))):
             if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != self.device or tuple(t.shape) != shape):
                 raise RuntimeError("append_device expects a contiguous %s %s tensor on %s" % (dt, shape, self.device))
-        self._check(self.lib.az_replay_append_device_starts(
-            self._h, C.c_void_p(buf.data_ptr()), n, C.c_void_p(start_ply.data_ptr()),
-            C.c_void_p(keys.data_ptr()) if keys is not None else None, self._stream()))
+        head = (self._h, C.c_void_p(buf.data_ptr()), n)
+        ply = C.c_void_p(start_ply.data_ptr()) if per_game else None
+        key_ptr = C.c_void_p(keys.data_ptr()) if keys is not None else None
+        if keep is not None:    # the narrowest of the three entries that takes what was given
+            rc = self.lib.az_replay_append_device_kept(*head, 0 if per_game else int(start_ply), ply, key_ptr,
+                                                       C.c_void_p(keep.data_ptr()), self._stream())
+        elif per_game:
+            rc = self.lib.az_replay_append_device_starts(*head, ply, key_ptr, self._stream())
+        else:
+            rc = self.lib.az_replay_append_device(*head, int(start_ply), self._stream())
+        self._check(rc)
 
     def dedupe(self):
         """Trainer.remove_duplicates over the flattened buffer; returns the number of unique examples."""
