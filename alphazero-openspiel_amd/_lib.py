@@ -137,6 +137,7 @@ PROTOTYPES = [
                                       C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double)]),
     ("az_engine_read_slot", C.c_int, [_vp, C.c_int32, C.POINTER(AzSlotInfo)]),
+    ("az_engine_read_root_noise", C.c_int, [_vp, C.c_int32, C.POINTER(C.c_double)]),
     ("az_engine_read_tree", C.c_int64, [_vp, C.c_int32, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("az_net_create", C.c_int, [C.POINTER(AzNetDesc), C.POINTER(_vp)]),

@@ -958,10 +958,10 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
                 if (j == 0) e0 = x; else if (j == 1) e1 = x; else e2 = x;
                 part += x;
             }
-            double inv = 1.0 / wave_sum_d(part);
-            if (mine > 0) p.eta_buf[(size_t)g * p.maxc + k[0]] = e0 * inv;
-            if (mine > 1) p.eta_buf[(size_t)g * p.maxc + k[1]] = e1 * inv;
-            if (mine > 2) p.eta_buf[(size_t)g * p.maxc + k[2]] = e2 * inv;
+            const double sum = wave_sum_d(part); // divided, not multiplied by 1 / sum: x * (1 / x) is 1 - 2^-53 for some x, and a
+            if (mine > 0) p.eta_buf[(size_t)g * p.maxc + k[0]] = e0 / sum; // root with ONE legal move takes eta = 1.0 exactly
+            if (mine > 1) p.eta_buf[(size_t)g * p.maxc + k[1]] = e1 / sum;
+            if (mine > 2) p.eta_buf[(size_t)g * p.maxc + k[2]] = e2 / sum;
         }
         write_obs<GAME>(p, sr.rs, obs_row, lane);
         st_evals++;
@@ -3058,6 +3058,28 @@ extern "C" int az_engine_read_slot(az_engine *e, int32_t slot, az_slot_info *o) 
         o->sims_done -= base;
     }
 #undef RD
+    return AZ_OK;
+}
+
+extern "C" int az_engine_read_root_noise(az_engine *e, int32_t slot, double *eta_out) {
+    if (!e || !eta_out || slot < 0 || slot >= e->p.G) return AZ_E_INVALID;
+    if (e->cfg.rng_mode != AZ_RNG_PHILOX || !e->cfg.use_dirichlet) {
+        e->err = "az_engine_read_root_noise: the engine draws no root noise on the device (rng_mode = AZ_RNG_PHILOX with use_dirichlet only)";
+        return AZ_E_INVALID;
+    }
+    if (!e->reset_done) {
+        e->err = "az_engine_read_root_noise before az_engine_reset";
+        return AZ_E_STATE;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, hipDeviceSynchronize());
+    int ph = PH_IDLE;
+    HIPCHK(e, hipMemcpy(&ph, e->p.phase + slot, sizeof ph, hipMemcpyDeviceToHost));
+    if (ph != PH_WAIT_ROOT) { // any other phase: the row is a vector an earlier tick has consumed (or nothing yet)
+        e->err = "az_engine_read_root_noise: the slot is not waiting for its root evaluation (phase 3)";
+        return AZ_E_STATE;
+    }
+    HIPCHK(e, hipMemcpy(eta_out, e->p.eta_buf + (size_t)slot * e->p.maxc, sizeof(double) * (size_t)e->p.maxc, hipMemcpyDeviceToHost));
     return AZ_OK;
 }
 

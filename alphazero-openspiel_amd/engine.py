@@ -325,6 +325,13 @@ class SelfPlayEngine:
                 "alloc": s.alloc, "bb": [s.bb[0], s.bb[1]], "leaf_bb": [s.leaf_bb[0], s.leaf_bb[1]],
                 "leaf_ply": s.leaf_ply, "depth": s.depth}
 
+    def read_root_noise(self, slot):
+        """The Dirichlet vector a Philox engine staged with the slot's root request (az_engine_read_root_noise) -> float64
+        array [max_children]; only the first n_legal entries belong to the draw.  EngineError unless the slot is in phase 3."""
+        eta = np.zeros(self.max_children, dtype=np.float64)
+        self._check(self.lib.az_engine_read_root_noise(self._h, int(slot), eta.ctypes.data_as(C.POINTER(C.c_double))))
+        return eta
+
     def read_tree(self, slot):
         """Whole tree of a slot, breadth-first: dict of numpy arrays parent/action/N/Q/P."""
         n = self._check(self.lib.az_engine_read_tree(self._h, slot, 0, None, None, None, None, None))

@@ -493,6 +493,17 @@ typedef struct az_slot_info {
 } az_slot_info;
 int az_engine_read_slot(az_engine *e, int32_t slot, az_slot_info *out);
 
+/* test / parity read-back of the root noise a slot has STAGED: the Dirichlet vector that the tick which issued the slot's root
+ * request drew on the device (AZ_RNG_PHILOX with use_dirichlet; np.random.dirichlet, mcts.py:187) and that the next tick mixes into
+ * the root priors.  eta_out: host array of max_children doubles, entry k = the draw of the k-th legal action in ascending order.
+ * Entries at and beyond the position's number of legal actions are NOT part of the draw: they hold whatever an earlier ply of the
+ * slot left there (on a fresh engine: unset device memory) and nothing reads them.  The row is the vector the next tick
+ * consumes only while the slot waits for its root evaluation (az_slot_info.phase == 3): in any other phase the call returns
+ * AZ_E_STATE, as it does before az_engine_reset.  AZ_E_INVALID: a bad slot, a NULL pointer, an AZ_RNG_INJECTED engine or one
+ * without use_dirichlet (their draws are the caller's own tables, or none).  Host code only: no kernel runs.  Synchronises the
+ * device as az_engine_read_slot. */
+int az_engine_read_root_noise(az_engine *e, int32_t slot, double *eta_out);
+
 #ifdef __cplusplus
 }
 #endif

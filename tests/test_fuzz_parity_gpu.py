@@ -26,10 +26,15 @@ def _config(seed):
               c_puct=float(r.choice([0.5, 1.0, 2.5, 4.0])), dirichlet_ratio=float(r.choice([0.1, 0.25, 0.5])),
               num_probabilistic_actions=int(r.choice([1000, 1000, 0, 3, 7])), use_puct=bool(r.rand() < 0.8))
     eng_only = dict(max_sims_per_tick=int(r.choice([0, 1, 3])), chain_window_us=int(r.choice([0, -1, 2])))
+    # generic temperatures (np_pow's pow() branch; the oracle's is libm's): every seed from 24 to 31, a third of the later ones -
+    # drawn from a generator of their own, so the configurations of seeds 0..23 are the ones they always were
+    # (of seeds 24..31 all but 27, which never samples - num_probabilistic_actions = 0 -, choose sampled moves through pow)
+    if seed >= 24 and (seed < 32 or np.random.RandomState(7000 + seed).rand() < 1.0 / 3.0):
+        kw["temperature"] = [0.7, 1.5][seed & 1]
     return game, n_games, int(r.randint(1, n_games + 1)), int(r.randint(100)), bool(r.rand() < 0.3), kw, eng_only, r
 
 
-@pytest.mark.parametrize("seed", range(int(__import__("os").environ.get("AZ_FUZZ_N", "24"))))  # AZ_FUZZ_N=600 for a long hunt
+@pytest.mark.parametrize("seed", range(int(__import__("os").environ.get("AZ_FUZZ_N", "32"))))  # AZ_FUZZ_N=600 for a long hunt
 def test_random_configuration_equals_the_oracle(seed):
     from test_engine_parity import _run_games
     from alphazero_openspiel_amd import engine as E
