@@ -19,7 +19,7 @@ __device__ __forceinline__ half8 frag_from_rows(half8 v, int lane) {
 
 // ------------------------------------------------------------------------------------------------
 // fc1 + softmax + tanh (network.py:61-64).  One workgroup = 16 boards; the K = HW*64 reduction is split
-// over the 4 waves (k-step ks goes to wave ks & 3), partial tiles are summed through LDS.
+// over the HEAD_NW = 8 waves (k-step ks goes to wave ks & 7), partial tiles are summed through LDS.
 // X3: split-fp16 operands (see az_tower_x3_kernel): three MFMAs per product, result = acc + acc2 / 2048.
 template <bool X3> __global__ __launch_bounds__(HEAD_NW * 64) void az_head_kernel(HeadParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];

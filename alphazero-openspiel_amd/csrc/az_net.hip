@@ -771,7 +771,13 @@ extern "C" int az_net_reserve(az_net *n, int32_t max_boards) {
     if (n->scheme == NetScheme::WIDE) return wide_reserve(n, max_boards);
     if (n->xout) (void)hipFree(n->xout);
     n->xout = nullptr;
-    // (+ 64 bytes: the last k-step of fc1 may reach past a board's row - into the next board's, times zero weights)
+    // The cross-board read under the K tail.  With the 52-channel stride K = H*W*52 need not be a multiple of 32 (6x7: 68 k-steps +
+    // 24 halves, 6x6: 58 + 16), and the last fc1 k-step of board b then reads the first 8 / 16 halves of board b + 1's row.  The
+    // repacked fc stream (repack_fc) holds zeros at k >= K, so what is read there counts for nothing AS LONG AS IT IS FINITE: a NaN
+    // or Inf in the first channels of board b + 1 would turn board b's logits into NaN (0 * Inf).  Rows past a forward's n_boards
+    // hold what an earlier, larger forward left (finite tower outputs) or the zeros written here; the + 64 bytes are that read for
+    // the last row of the buffer.  tests/test_head_kernels_gpu.py::test_a_board_keeps_its_bits pins that a small batch after a
+    // larger one of other boards gives the bits of a fresh handle.
     size_t bytes = (size_t)max_boards * n->d.rows * n->d.cols * n->xc * 2 + 64;
     NCHK(n, hipMalloc((void **)&n->xout, bytes));
     NCHK(n, hipMemset(n->xout, 0, bytes));

@@ -54,3 +54,93 @@ def max_activation_fp64(net, obs):
     for h in hooks:
         h.remove()
     return max(top)
+
+
+def trained_head(net, seed, gate=1.0):
+    """Rewrite net.fc1 in place (the tower is left alone) so that the head looks trained:
+
+        weight[o] = s_o * (gate * u + 0.05 * W0[o]),    bias[o] = +-[0.25, 1.5], seeded: all distinct, none zero
+
+    W0: seeded rows uniform in +-1 / sqrt(K).  u: ONE direction shared by every row, (a seeded sign per channel) x (a checkerboard
+    sign per cell) / sqrt(K): u . x, the "gate", has a mean near zero over boards (neighbouring cells cancel), so it is near zero on
+    some boards - every logit is then its bias: a flat softmax, tanh in its linear part - and large on others.  s_o: the row's own
+    scale, magnitude log-uniform in [0.5, 16] with a seeded sign; rows A // 3 and 2 A // 3 have +32 and -32 (one of them wins by
+    far wherever the gate is open: a prior near 1, the others down to 1e-20 and less) and the value row 12.  `gate` scales u per
+    net so that the widest policy spans 50 to 140 logits (head_cases.GATE).
+    Then 3 % of the weights, chosen at random, are replaced by values of their sign and a magnitude log-uniform in [1e-9, 6e-5]:
+    the fp16 hi half of each is subnormal (below 6.1e-5), and a third of them lie below 3e-8, where the lo half of the f32x pair,
+    scaled by 2048, is subnormal as well.
+    The shares that tests/test_head_cases_host.py asserts for every net of head_cases.NETS over its boards, from the float64 forward
+    alone (measured: the figures in brackets): some board's policy logits span more than 40 units (47 .. 137) and at least 5 % of
+    the boards' more than 30 (5.7 .. 58 %); at least 5 % of the boards have a prior above 0.99 (7 .. 85 %) and some prior is below
+    1e-12 (1.8e-21 and less); at least 3 % of the boards are near uniform, entropy above 0.8 ln A (3.1 .. 31 %); the value is beyond
+    +-0.999 on at least 5 % (31 .. 61 %) and inside +-0.5 on at least 3 % (4.6 .. 11 %); at least 2 % of the weights are below 6.1e-5
+    (2.9 .. 3.4 %) and at least 0.5 % below 3e-8 (0.87 .. 1.4 %), none is zero; no activation reaches 65504 and every logit is finite in
+    float32 (the largest: 72)."""
+    g = torch.Generator().manual_seed(seed)
+    fc = net.fc1
+    A1, K = fc.weight.shape
+    F, HW = net.n_filts, net.height * net.width
+    with torch.no_grad():
+        w0 = (2.0 * torch.rand(A1, K, generator=g, dtype=torch.float64) - 1.0) / K ** 0.5
+        cell = torch.arange(HW)
+        checker = 1.0 - 2.0 * ((cell // net.width + cell % net.width) % 2).double()
+        u = (torch.where(torch.rand(F, generator=g) < 0.5, -1.0, 1.0).double()[:, None] * checker[None, :]).reshape(K) / K ** 0.5
+        s = 0.5 * 32.0 ** torch.rand(A1, generator=g, dtype=torch.float64)
+        s = s * torch.where(torch.rand(A1, generator=g) < 0.5, -1.0, 1.0).double()
+        s[(A1 - 1) // 3], s[2 * (A1 - 1) // 3], s[A1 - 1] = 32.0, -32.0, 12.0
+        w = s[:, None] * (gate * u[None, :] + 0.05 * w0)
+        tiny = torch.rand(A1, K, generator=g) < 0.03
+        mag = 1e-9 * 6e4 ** torch.rand(A1, K, generator=g, dtype=torch.float64)
+        w = torch.where(tiny, torch.sign(w) * mag, w)
+        b = (0.25 + 1.25 * torch.rand(A1, generator=g, dtype=torch.float64)) * torch.where(torch.rand(A1, generator=g) < 0.5, -1.0, 1.0)
+        fc.weight.copy_(w.float())
+        fc.bias.copy_(b.float())
+    return net
+
+
+# ---- the head alone: fc1 + softmax + tanh from given operands ------------------------------------------------------------------
+def head_weights(net, mode):
+    """fc1's weights as a device path holds them, float64 [A + 1][H*W][F] (K index = position * stride + channel): "exact" - the
+    float32 parameters; "tuned" - fusednet.split_fp16's hi + lo / 2048; "wide" - fp16 hi and fp16((w - hi) * 2048) (the same
+    arithmetic, restated from az_net_create_wide); "f16" - the hi half alone."""
+    F, HW = net.n_filts, net.height * net.width
+    w = net.fc1.weight.detach().double().numpy().reshape(-1, F, HW).transpose(0, 2, 1)
+    if mode == "exact":
+        return np.ascontiguousarray(w)
+    if mode == "tuned":
+        hi, lo = fusednet.split_fp16(w)
+    else:
+        hi = w.astype(np.float16)
+        lo = ((w - hi.astype(np.float64)) * 2048.0).astype(np.float16)
+    if mode == "f16":
+        return hi.astype(np.float64)
+    assert mode in ("tuned", "wide"), mode
+    return hi.astype(np.float64) + lo.astype(np.float64) / 2048.0
+
+
+def head_fp64(x, w, bias, A):
+    """(priors [B][A], values [B], logits [B][A + 1]) in float64 of the head on the tower output x [B][H*W][>= F] (channels past
+    F are ignored: their weights are zero on the device), weights w [A + 1][H*W][F] and the float32 bias."""
+    F = w.shape[2]
+    x = np.asarray(x, dtype=np.float64)[:, :, :F]
+    B = x.shape[0]
+    logits = x.reshape(B, -1) @ w.reshape(A + 1, -1).T + np.asarray(bias, dtype=np.float64)[None, :]
+    lp = logits[:, :A]
+    e = np.exp(lp - lp.max(1, keepdims=True))
+    return e / e.sum(1, keepdims=True), np.tanh(logits[:, A]), logits
+
+
+def head_fp32(x, w, bias, A, fast_exp=False):
+    """The same head on the same operands in numpy float32 - a float32 matmul, float32 exp and tanh; fast_exp: the exponential as
+    exp2(float32(d * float32(log2 e))), the model of the f16 heads' __expf."""
+    F = w.shape[2]
+    x = np.ascontiguousarray(np.asarray(x)[:, :, :F], dtype=np.float32)
+    B = x.shape[0]
+    logits = x.reshape(B, -1) @ np.ascontiguousarray(w.reshape(A + 1, -1).T, dtype=np.float32) + np.asarray(bias, dtype=np.float32)[None, :]
+    assert logits.dtype == np.float32
+    d = logits[:, :A] - logits[:, :A].max(1, keepdims=True)
+    e = np.exp2((d * np.float32(np.log2(np.e))).astype(np.float32)) if fast_exp else np.exp(d)
+    p = e / e.sum(1, keepdims=True, dtype=np.float32)
+    assert p.dtype == np.float32
+    return p, np.tanh(logits[:, A])
