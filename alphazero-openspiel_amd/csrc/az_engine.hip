@@ -1570,15 +1570,6 @@ __global__ void az_reset_kernel(Params p) {
 // host side: C ABI
 static std::string g_create_err;
 
-#define HIPCHK(e, call)                                                                      \
-    do {                                                                                     \
-        hipError_t _s = (call);                                                              \
-        if (_s != hipSuccess) {                                                              \
-            (e)->err = std::string(#call) + ": " + hipGetErrorString(_s);                    \
-            return AZ_E_HIP;                                                                 \
-        }                                                                                    \
-    } while (0)
-
 template <typename T> static int dalloc(az_engine *e, T **out, size_t count) {
     void *ptr = nullptr;
     size_t bytes = count * sizeof(T);
@@ -1603,10 +1594,8 @@ extern "C" int az_engine_destroy(az_engine *e) {
     if (e->d_etas) (void)hipFree(e->d_etas);
     if (e->d_us) (void)hipFree(e->d_us);
     if (e->d_actions) (void)hipFree(e->d_actions);
-    if (e->d_starts) (void)hipFree(e->d_starts);
-    if (e->d_start_ply) (void)hipFree(e->d_start_ply);
-    if (e->d_start_keys) (void)hipFree(e->d_start_keys);
-    if (e->d_start_check) (void)hipFree(e->d_start_check);
+    start_table_free(e->start);
+    if (e->start.check) (void)hipFree(e->start.check);
     delete e;
     return AZ_OK;
 }
@@ -1850,7 +1839,7 @@ extern "C" int az_engine_reset(az_engine *e, uint64_t seed, int64_t n_games, voi
         e->err = "n_games must be in [1, max_games]";
         return AZ_E_INVALID;
     }
-    if (e->p.starts && n_games > e->starts_n) {
+    if (start_table_n(e) && n_games > start_table_n(e)) {
         e->err = "n_games exceeds the games given to az_engine_set_start_positions / az_engine_set_game_starts (the start table)";
         return AZ_E_INVALID;
     }
@@ -1866,8 +1855,8 @@ extern "C" int az_engine_stream_begin(az_engine *e, uint64_t seed, void *stream)
     if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) why = "an arena engine (game id i fixes the agent's side, records are read by id)";
     else if (e->cfg.manual_moves) why = "a manual_moves engine (its slots are re-armed by the caller)";
     else if (e->cfg.rng_mode == AZ_RNG_INJECTED) why = "rng_mode = AZ_RNG_INJECTED (injected draws are tables indexed by game id)";
-    else if (e->has_prefix) why = "a start prefix is set (az_engine_set_start_prefix)";
-    else if (e->p.starts) why = "a start-position table is set (az_engine_set_start_positions / az_engine_set_game_starts)";
+    else if (start_prefixed(e)) why = "a start prefix is set (az_engine_set_start_prefix)";
+    else if (start_table_n(e)) why = "a start-position table is set (az_engine_set_start_positions / az_engine_set_game_starts)";
     else if (e->p.capdev) why = "a playout cap is set (az_engine_set_playout_cap: the mask of full-search moves does not travel with a take)";
     else if (e->cfg.max_games < e->cfg.n_slots) why = "max_games < n_slots (slots 0..G-1 start ids 0..G-1, each needs a row of the ring)";
     if (why) {
@@ -2020,330 +2009,6 @@ extern "C" int az_engine_set_injected_rng(az_engine *e, const double *etas, cons
     return AZ_OK;
 }
 
-// Replay an action prefix from the initial position on the host, with the legality checks of the game: 0 = ok (s = the position),
-// 1 = an illegal action, 2 = the prefix ends the game.
-static int replay_prefix(const az_engine *e, const int32_t *actions, int32_t n, AzState &s) {
-    float ret0 = 0.f;
-    int term = 0;
-    if (e->cfg.game == AZ_GAME_CONNECT_FOUR) {
-        az_init_state<AZG_CONNECT_FOUR>(s, e->p.geom);
-        for (int i = 0; i < n && !term; i++) {
-            if (actions[i] < 0 || actions[i] > 6 || !((az_c4_legal_mask(s) >> actions[i]) & 1u)) return 1;
-            term = az_apply<AZG_CONNECT_FOUR>(s, e->p.geom, actions[i], &ret0);
-        }
-    } else {
-        az_init_state<AZG_BREAKTHROUGH>(s, e->p.geom);
-        for (int i = 0; i < n && !term; i++) {
-            int a = actions[i];
-            if (a < 0 || a >= e->p.A) return 1;
-            int d = (a >> 1) % 6, cell = (a >> 1) / 6, me = s.ply & 1;
-            uint32_t mv = az_bt_cell_moves(s, e->p.geom, cell);
-            int dd = d - (me ? 3 : 0);
-            if (dd < 0 || dd > 2 || !(mv & (1u << dd)) || (int)((mv >> (4 + dd)) & 1u) != (a & 1)) return 1;
-            term = az_apply<AZG_BREAKTHROUGH>(s, e->p.geom, a, &ret0);
-        }
-    }
-    return term ? 2 : 0;
-}
-
-extern "C" int az_engine_set_start_prefix(az_engine *e, const int32_t *actions, int32_t n) {
-    if (!e || (n > 0 && !actions)) return AZ_E_INVALID;
-    AzState s;
-    int bad = replay_prefix(e, actions, n, s);
-    if (bad) {
-        e->err = bad == 1 ? "illegal prefix action" : "prefix ends the game";
-        return AZ_E_INVALID;
-    }
-    e->p.start = s;
-    e->has_prefix = n > 0;
-    e->p.starts = nullptr; // one prefix for every game again
-    e->starts_n = 0;
-    e->game_starts = e->starts_keyed = false;
-    e->reset_done = false; // caller must reset again so that slots pick the new start up
-    return AZ_OK;
-}
-
-// The table behind Params::starts holds at least n_games states (a table that has to grow is out of force until it is filled).
-static int starts_reserve(az_engine *e, int64_t n_games) {
-    if (n_games <= e->starts_cap) return AZ_OK;
-    if (e->d_starts) (void)hipFree(e->d_starts);
-    if (e->d_start_ply) (void)hipFree(e->d_start_ply);
-    if (e->d_start_keys) (void)hipFree(e->d_start_keys);
-    e->d_starts = nullptr;
-    e->d_start_ply = nullptr;
-    e->d_start_keys = nullptr;
-    e->starts_cap = 0;
-    e->p.starts = nullptr;
-    e->starts_n = 0;
-    e->game_starts = e->starts_keyed = false;
-    HIPCHK(e, hipMalloc((void **)&e->d_starts, (size_t)n_games * sizeof(AzState)));
-    HIPCHK(e, hipMalloc((void **)&e->d_start_ply, (size_t)n_games * sizeof(int32_t)));
-    HIPCHK(e, hipMalloc((void **)&e->d_start_keys, (size_t)n_games * 2 * sizeof(uint64_t)));
-    e->starts_cap = n_games;
-    return AZ_OK;
-}
-// ... and its first n_games entries are the start positions from now on.
-static void starts_in_force(az_engine *e, int64_t n_games) {
-    if (e->cfg.game == AZ_GAME_CONNECT_FOUR) az_init_state<AZG_CONNECT_FOUR>(e->p.start, e->p.geom); // supersedes a single prefix
-    else az_init_state<AZG_BREAKTHROUGH>(e->p.start, e->p.geom);
-    e->p.starts = e->d_starts;
-    e->starts_n = n_games;
-    e->game_starts = e->starts_keyed = false; // (the game-start setters raise them after this)
-    e->reset_done = false; // caller must reset again so that slots pick the new starts up
-}
-
-extern "C" int az_engine_set_start_positions(az_engine *e, const int32_t *actions, const int32_t *lengths, int64_t stride,
-                                             int64_t n_games) {
-    if (!e) return AZ_E_INVALID;
-    if (!e->cfg.manual_moves) {
-        e->err = "az_engine_set_start_positions needs an engine created with manual_moves = 1: self-play and arena engines keep "
-                 "ONE start ply for the record offset, the value targets, the replay append and the side assignment";
-        return AZ_E_INVALID;
-    }
-    if (!lengths || n_games < 1 || n_games > e->cfg.max_games || stride < 0) {
-        e->err = "az_engine_set_start_positions: n_games must be in [1, max_games], lengths non-null, stride >= 0";
-        return AZ_E_INVALID;
-    }
-    std::vector<AzState> tab((size_t)n_games);
-    for (int64_t i = 0; i < n_games; i++) {
-        const int32_t n = lengths[i];
-        if (n < 0 || n > stride || (n > 0 && !actions)) {
-            e->err = "az_engine_set_start_positions: game " + std::to_string(i) + ": prefix length " + std::to_string(n) +
-                     " outside [0, stride]";
-            return AZ_E_INVALID;
-        }
-        int bad = replay_prefix(e, n > 0 ? actions + i * stride : nullptr, n, tab[(size_t)i]);
-        if (bad) {
-            e->err = "az_engine_set_start_positions: game " + std::to_string(i) +
-                     (bad == 1 ? ": illegal prefix action" : ": prefix ends the game");
-            return AZ_E_INVALID;
-        }
-    }
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    HIPCHK(e, hipDeviceSynchronize()); // a reset of the previous chunk may still be reading the table
-    int rc = starts_reserve(e, n_games);
-    if (rc != AZ_OK) return rc;
-    HIPCHK(e, hipMemcpy(e->d_starts, tab.data(), (size_t)n_games * sizeof(AzState), hipMemcpyHostToDevice));
-    starts_in_force(e, n_games);
-    return AZ_OK;
-}
-
-// The device form: the states come as bitboards and plies in device memory (az_replay_gather_states writes them).  One thread
-// per state runs az_check_state; the lowest offending index and its rule reach the host as one word, (index << 8) | rule, through
-// a 64-bit atomicMin, and only a clean pass is followed by the kernel that fills the table.
-#define START_CHECK_CLEAN ~0ull
-template <int GAME>
-__global__ void az_check_start_states_kernel(AzGeom geom, int max_plies, const uint64_t *bb, const int32_t *ply, long long n,
-                                             unsigned long long *result) {
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    AzState s;
-    s.bb0 = bb[2 * i];
-    s.bb1 = bb[2 * i + 1];
-    s.ply = ply[i];
-    int rule = az_check_state<GAME>(s, geom, max_plies);
-    if (rule != AZ_STATE_OK) atomicMin(result, ((unsigned long long)i << 8) | (unsigned long long)rule);
-}
-__global__ void az_fill_start_states_kernel(const uint64_t *bb, const int32_t *ply, long long n, AzState *tab) {
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    AzState s;
-    s.bb0 = bb[2 * i];
-    s.bb1 = bb[2 * i + 1];
-    s.ply = ply[i];
-    tab[i] = s;
-}
-
-// The validity pass of both device-form start entries: every state through az_check_state on the device, the lowest offending
-// index named in az_last_error as "<what>: game <i>: <rule>".  plies_out (may be null) receives a host copy of ply_dev.
-// Synchronises the device first (the states are written, and nothing reads the table any more) and `st` at the end.
-static int check_start_states_device(az_engine *e, const char *what, const uint64_t *bb_dev, const int32_t *ply_dev, int64_t n_games,
-                                     hipStream_t st, std::vector<int32_t> *plies_out) {
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    HIPCHK(e, hipDeviceSynchronize());
-    if (!e->d_start_check) HIPCHK(e, hipMalloc((void **)&e->d_start_check, sizeof(unsigned long long)));
-    unsigned long long res = START_CHECK_CLEAN;
-    HIPCHK(e, hipMemcpyAsync(e->d_start_check, &res, sizeof res, hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)((n_games + 255) / 256)), block(256);
-    if (e->cfg.game == AZ_GAME_CONNECT_FOUR)
-        hipLaunchKernelGGL(az_check_start_states_kernel<AZG_CONNECT_FOUR>, grid, block, 0, st, e->p.geom, e->p.max_plies, bb_dev, ply_dev,
-                           (long long)n_games, e->d_start_check);
-    else
-        hipLaunchKernelGGL(az_check_start_states_kernel<AZG_BREAKTHROUGH>, grid, block, 0, st, e->p.geom, e->p.max_plies, bb_dev, ply_dev,
-                           (long long)n_games, e->d_start_check);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipMemcpyAsync(&res, e->d_start_check, sizeof res, hipMemcpyDeviceToHost, st));
-    if (plies_out) {
-        plies_out->resize((size_t)n_games);
-        HIPCHK(e, hipMemcpyAsync(plies_out->data(), ply_dev, (size_t)n_games * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(e, hipStreamSynchronize(st));
-    if (res != START_CHECK_CLEAN) {
-        e->err = std::string(what) + ": game " + std::to_string(res >> 8) + ": " + az_state_rule_name((int)(res & 0xFF));
-        return AZ_E_INVALID;
-    }
-    return AZ_OK;
-}
-
-extern "C" int az_engine_set_start_states_device(az_engine *e, const uint64_t *bb_dev, const int32_t *ply_dev, int64_t n_games,
-                                                 void *stream) {
-    if (!e) return AZ_E_INVALID;
-    if (!e->cfg.manual_moves) {
-        e->err = "az_engine_set_start_states_device needs an engine created with manual_moves = 1: self-play and arena engines keep "
-                 "ONE start ply for the record offset, the value targets, the replay append and the side assignment";
-        return AZ_E_INVALID;
-    }
-    if (!bb_dev || !ply_dev || n_games < 1 || n_games > e->cfg.max_games) {
-        e->err = "az_engine_set_start_states_device: n_games must be in [1, max_games], bb_dev and ply_dev non-null";
-        return AZ_E_INVALID;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    int rc = check_start_states_device(e, "az_engine_set_start_states_device", bb_dev, ply_dev, n_games, st, nullptr);
-    if (rc != AZ_OK) return rc;
-    rc = starts_reserve(e, n_games);
-    if (rc != AZ_OK) return rc;
-    const dim3 grid((unsigned)((n_games + 255) / 256)), block(256);
-    hipLaunchKernelGGL(az_fill_start_states_kernel, grid, block, 0, st, bb_dev, ply_dev, (long long)n_games, e->d_starts);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipStreamSynchronize(st));
-    starts_in_force(e, n_games);
-    return AZ_OK;
-}
-
-// ---- a start position per game for SELF-PLAY (include/az_engine.h: az_engine_set_game_starts) --------------------------------
-// The same table as above, on a plain self-play engine, with each game's start ply and history key pair beside it.
-static int game_starts_refusal(az_engine *e, const char *what) {
-    const char *why = nullptr;
-    if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) why = "an arena engine (game id i fixes the agent's side from ONE start ply)";
-    else if (e->cfg.manual_moves) why = "a manual_moves engine (az_engine_set_start_positions / az_engine_set_start_states_device are its entries)";
-    else if (e->streaming) why = "an engine in stream mode (az_engine_stream_begin: game ids are open-ended, a table is not)";
-    if (!why) return AZ_OK;
-    e->err = std::string(what) + " is for plain self-play engines in a closed generation: refused for " + why;
-    return AZ_E_INVALID;
-}
-
-extern "C" int az_engine_set_game_starts(az_engine *e, const int32_t *actions, const int32_t *lengths, int64_t stride, int64_t n_games) {
-    if (!e) return AZ_E_INVALID;
-    if (game_starts_refusal(e, "az_engine_set_game_starts")) return AZ_E_INVALID;
-    if (!lengths || n_games < 1 || n_games > e->cfg.max_games || stride < 0) {
-        e->err = "az_engine_set_game_starts: n_games must be in [1, max_games], lengths non-null, stride >= 0";
-        return AZ_E_INVALID;
-    }
-    std::vector<AzState> tab((size_t)n_games);
-    std::vector<int32_t> plies((size_t)n_games);
-    std::vector<uint64_t> keys((size_t)n_games * 2);
-    AzState init;
-    if (e->cfg.game == AZ_GAME_CONNECT_FOUR) az_init_state<AZG_CONNECT_FOUR>(init, e->p.geom);
-    else az_init_state<AZG_BREAKTHROUGH>(init, e->p.geom);
-    for (int64_t i = 0; i < n_games; i++) {
-        const int32_t n = lengths[i];
-        if (n < 0 || n > stride || (n > 0 && !actions)) {
-            e->err = "az_engine_set_game_starts: game " + std::to_string(i) + ": prefix length " + std::to_string(n) + " outside [0, stride]";
-            return AZ_E_INVALID;
-        }
-        const int32_t *pre = n > 0 ? actions + i * stride : nullptr;
-        int bad = replay_prefix(e, pre, n, tab[(size_t)i]);
-        if (bad) {
-            e->err = "az_engine_set_game_starts: game " + std::to_string(i) + (bad == 1 ? ": illegal prefix action" : ": prefix ends the game");
-            return AZ_E_INVALID;
-        }
-        // the pair of an ordinary game from the initial position after these moves (az_keychain.h): the j-th move steps with index j
-        AzKeyPair k = az_key_seed(init.ply, init.bb0, init.bb1);
-        for (int32_t j = 0; j < n; j++) k = az_key_step(k, (uint32_t)pre[j], j + 1);
-        plies[(size_t)i] = tab[(size_t)i].ply;
-        keys[(size_t)i * 2] = k.key;
-        keys[(size_t)i * 2 + 1] = k.key2;
-    }
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    HIPCHK(e, hipDeviceSynchronize()); // a generation that still plays, or an append, may be reading the table
-    int rc = starts_reserve(e, n_games);
-    if (rc != AZ_OK) return rc;
-    HIPCHK(e, hipMemcpy(e->d_starts, tab.data(), (size_t)n_games * sizeof(AzState), hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(e->d_start_ply, plies.data(), (size_t)n_games * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(e, hipMemcpy(e->d_start_keys, keys.data(), (size_t)n_games * 2 * sizeof(uint64_t), hipMemcpyHostToDevice));
-    starts_in_force(e, n_games);
-    e->has_prefix = false;
-    e->h_start_ply = plies;
-    e->game_starts = e->starts_keyed = true;
-    return AZ_OK;
-}
-
-// keys == null: every game's pair is its start state's own seed (what an ordinary game starting there carries at its first ply)
-__global__ void az_fill_game_starts_kernel(const uint64_t *bb, const int32_t *ply, const uint64_t *keys, long long n, AzState *tab,
-                                           int32_t *ply_tab, uint64_t *key_tab) {
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    AzState s;
-    s.bb0 = bb[2 * i];
-    s.bb1 = bb[2 * i + 1];
-    s.ply = ply[i];
-    tab[i] = s;
-    ply_tab[i] = s.ply;
-    AzKeyPair k;
-    if (keys) k.key = keys[2 * i], k.key2 = keys[2 * i + 1];
-    else k = az_key_seed(s.ply, s.bb0, s.bb1);
-    key_tab[2 * i] = k.key;
-    key_tab[2 * i + 1] = k.key2;
-}
-
-extern "C" int az_engine_set_game_starts_device(az_engine *e, const uint64_t *bb_dev, const int32_t *ply_dev, const uint64_t *keys_dev,
-                                                int64_t n_games, void *stream) {
-    if (!e) return AZ_E_INVALID;
-    if (game_starts_refusal(e, "az_engine_set_game_starts_device")) return AZ_E_INVALID;
-    if (!bb_dev || !ply_dev || n_games < 1 || n_games > e->cfg.max_games) {
-        e->err = "az_engine_set_game_starts_device: n_games must be in [1, max_games], bb_dev and ply_dev non-null";
-        return AZ_E_INVALID;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    std::vector<int32_t> plies;
-    int rc = check_start_states_device(e, "az_engine_set_game_starts_device", bb_dev, ply_dev, n_games, st, &plies);
-    if (rc != AZ_OK) return rc;
-    rc = starts_reserve(e, n_games);
-    if (rc != AZ_OK) return rc;
-    const dim3 grid((unsigned)((n_games + 255) / 256)), block(256);
-    hipLaunchKernelGGL(az_fill_game_starts_kernel, grid, block, 0, st, bb_dev, ply_dev, keys_dev, (long long)n_games, e->d_starts,
-                       e->d_start_ply, e->d_start_keys);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipStreamSynchronize(st));
-    starts_in_force(e, n_games);
-    e->has_prefix = false;
-    e->h_start_ply = plies;
-    e->game_starts = true;
-    e->starts_keyed = keys_dev != nullptr;
-    return AZ_OK;
-}
-
-// table == null: the uniform start of every game, and its seed pair
-__global__ void az_game_starts_out_kernel(AzState start, const int32_t *ply_tab, const uint64_t *key_tab, long long n, int32_t *ply_out,
-                                          uint64_t *keys_out) {
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    ply_out[i] = ply_tab ? ply_tab[i] : start.ply;
-    if (!keys_out) return;
-    if (key_tab) {
-        keys_out[2 * i] = key_tab[2 * i];
-        keys_out[2 * i + 1] = key_tab[2 * i + 1];
-    } else {
-        const AzKeyPair k = az_key_seed(start.ply, start.bb0, start.bb1);
-        keys_out[2 * i] = k.key;
-        keys_out[2 * i + 1] = k.key2;
-    }
-}
-
-extern "C" int az_engine_game_starts_device(az_engine *e, int32_t *ply_out_dev, uint64_t *keys_out_dev, int64_t n_games, void *stream) {
-    if (!e) return AZ_E_INVALID;
-    if (!ply_out_dev || n_games < 1 || n_games > e->cfg.max_games || (e->game_starts && n_games > e->starts_n)) {
-        e->err = "az_engine_game_starts_device: ply_out_dev non-null, n_games in [1, max_games] and within the table";
-        return AZ_E_INVALID;
-    }
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    hipLaunchKernelGGL(az_game_starts_out_kernel, dim3((unsigned)((n_games + 255) / 256)), dim3(256), 0, (hipStream_t)stream, e->p.start,
-                       e->game_starts ? e->d_start_ply : nullptr, e->game_starts ? e->d_start_keys : nullptr, (long long)n_games,
-                       ply_out_dev, keys_out_dev);
-    HIPCHK(e, hipGetLastError());
-    return e->game_starts && e->starts_keyed ? 1 : 0;
-}
-
 // ---- playout cap randomisation (include/az_engine.h: az_engine_set_playout_cap) ------------------------------------------------
 extern "C" int az_engine_set_playout_cap(az_engine *e, int32_t n_fast, double p_full) {
     if (!e) return AZ_E_INVALID;
@@ -2409,14 +2074,14 @@ __global__ void az_full_moves_kernel(const int *len, const uint8_t *rec_full, in
 extern "C" int az_engine_full_moves_device(az_engine *e, uint8_t *full_out_dev, int64_t n_games, void *stream) {
     if (!e) return AZ_E_INVALID;
     if (refuse_in_stream(e, "az_engine_full_moves_device")) return AZ_E_STATE;
-    if (!full_out_dev || n_games < 1 || n_games > e->cfg.max_games || (e->game_starts && n_games > e->starts_n)) {
+    if (!full_out_dev || n_games < 1 || n_games > e->cfg.max_games || (start_plies_dev(e) && n_games > start_table_n(e))) {
         e->err = "az_engine_full_moves_device: full_out_dev non-null, n_games in [1, max_games] and within the game-start table";
         return AZ_E_INVALID;
     }
     HIPCHK(e, hipSetDevice(e->cfg.device));
     const long long threads = (long long)n_games * e->p.max_plies;
     hipLaunchKernelGGL(az_full_moves_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, e->p.rec_len,
-                       e->p.capdev ? e->cap.rec_full : nullptr, e->p.start.ply, e->game_starts ? e->d_start_ply : nullptr, (long long)n_games, e->p.max_plies,
+                       e->p.capdev ? e->cap.rec_full : nullptr, e->p.start.ply, start_plies_dev(e), (long long)n_games, e->p.max_plies,
                        full_out_dev);
     HIPCHK(e, hipGetLastError());
     return e->p.capdev ? 1 : 0;
@@ -2755,7 +2420,7 @@ extern "C" int az_engine_export(az_engine *e, az_example_view *out, void *stream
     for (int i = 0; i < AZ_RECORD_ARRAYS; i++) HIPCHK(e, hipMemcpy(dst[i], src[i], sizes[i], hipMemcpyDeviceToHost));
     if (e->cfg.backup == AZ_BACKUP_ON_POLICY) // game_utils.py:200-204
         for (size_t g = 0; g < ng; g++) {
-            const int p0 = e->game_starts ? e->h_start_ply[g] : e->p.start.ply; // the game's own start ply when a table is set
+            const int p0 = start_ply_of(e, (int64_t)g); // the game's own start ply when a table is set
             double reward = (double)h.game_ret0[g];
             if (p0 & 1) reward = -reward; // first recorded ply is player 1's
             for (int i = 0; i < h.game_len[g]; i++) {
@@ -2813,7 +2478,7 @@ extern "C" int az_engine_export_device(az_engine *e, void *dev_buf, int64_t byte
     if (e->cfg.backup == AZ_BACKUP_ON_POLICY) {
         long long threads = (long long)n * (long long)mp;
         hipLaunchKernelGGL(fill_on_policy_values_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, e->p.rec_len,
-                           e->p.rec_ret0, e->p.rec_value, (int)n, (int)mp, e->p.start.ply, e->game_starts ? e->d_start_ply : nullptr);
+                           e->p.rec_ret0, e->p.rec_value, (int)n, (int)mp, e->p.start.ply, start_plies_dev(e));
         HIPCHK(e, hipGetLastError());
     }
     size_t sizes[AZ_RECORD_ARRAYS];

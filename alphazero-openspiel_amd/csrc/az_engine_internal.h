@@ -1,4 +1,4 @@
-// az_engine_internal.h — definitions shared by az_engine.hip and az_replay.hip (NOT part of the C ABI).
+// az_engine_internal.h — definitions shared by az_engine.hip, az_starts.hip and az_replay.hip (NOT part of the C ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,6 +10,7 @@
 #include "az_games.h"
 #include "az_keychain.h"
 #include "az_records.h"
+#include "az_starts.h"
 
 #define NONE32 0xFFFFFFFFu
 
@@ -137,11 +138,32 @@ struct Params {
     // of az_advance_kernel only, which the host launches while forced_k > 0; the others never touch the two fields.
     double forced_k;
 };
+static_assert(sizeof(Params) == 952, "Params is passed by value to every kernel and baked into captured graphs: its layout does not move");
 
 // The engine's own record arrays as a view (az_records.h); the tick kernel keeps reading p.rec_* itself.
 static inline AzRecords records_of(const Params &p) {
     return AzRecords{p.rec_len, p.rec_ret0, p.rec_states, p.rec_move, p.rec_nchild, p.rec_child_action, p.rec_child_visits, p.rec_value};
 }
+
+// Where games start.  The table lives in device memory by game id and is read at reset, at take-next and at game end only.
+enum StartKind {
+    START_UNIFORM = 0,  // every game starts from Params::start (Params::starts is null); prefixed: a non-empty prefix gave it
+    START_PER_POSITION, // manual_moves engines (az_engine_set_start_positions / _start_states_device): Params::starts = states
+    START_PER_GAME,     // plain self-play engines (az_engine_set_game_starts / _device): the same, and plies, keys, h_plies count
+};
+struct StartTable {
+    StartKind kind = START_UNIFORM;
+    bool prefixed = false;
+    // START_PER_GAME: the key pairs were GIVEN (a prefix's chain, or the caller's keys_dev) and the games' key chains step by
+    // absolute ply; otherwise they are the start states' own seeds and the games are keyed as ordinary ones (az_keychain.h)
+    bool keyed = false;
+    int64_t n = 0, cap = 0;    // entries in force (0 = no table), entries allocated (kept across setter calls)
+    AzState *states = nullptr; // [cap]
+    int32_t *plies = nullptr;  // [cap] the states' plies as plain int32 (what the replay append indexes with)
+    uint64_t *keys = nullptr;  // [cap][2] history key pairs
+    unsigned long long *check = nullptr; // result word of the device forms' validity pass
+    std::vector<int32_t> h_plies;        // START_PER_GAME: host copy of plies[0..n)
+};
 
 struct az_engine {
     az_config cfg;
@@ -155,23 +177,12 @@ struct az_engine {
     int *d_actions = nullptr;
     int64_t ticks = 0;
     int64_t inj_games = 0;
-    AzState *d_starts = nullptr; // the table behind p.starts (kept across az_engine_set_start_positions calls)
-    int64_t starts_cap = 0, starts_n = 0;
-    unsigned long long *d_start_check = nullptr; // result record of az_engine_set_start_states_device's validity pass
-    // az_engine_set_game_starts / az_engine_set_game_starts_device (plain self-play engines): the table is a game-start table.
-    // Next to each AzState of d_starts: the game's start ply as a plain int32 (what the replay append indexes with) and its
-    // history key pair (az_keychain.h).  keyed: the pairs were GIVEN (a prefix's chain, or the caller's keys_dev) and the games'
-    // key chains step by absolute ply; otherwise they are the start states' own seeds and the games are keyed as ordinary ones.
-    bool game_starts = false, starts_keyed = false;
-    int32_t *d_start_ply = nullptr;
-    uint64_t *d_start_keys = nullptr; // u64 [starts_cap][2]
-    std::vector<int32_t> h_start_ply; // host copy for az_engine_export's on-policy fill
+    StartTable start; // where games start: read through the accessors below, written by csrc/az_starts.hip alone
     CapDev cap = {0, 0, 0.0, nullptr, nullptr, nullptr}; // host copy of the playout cap's record; d_cap: the device record (p.capdev when a cap is in force)
     CapDev *d_cap = nullptr;
     bool rows_mapped = false; // az_engine_compact_rows has been called since the last reset
     int rows_live = 0;
     bool streaming = false;   // az_engine_stream_begin since the last az_engine_reset
-    bool has_prefix = false;  // az_engine_set_start_prefix gave a non-empty prefix
     int64_t read_pos = 0;     // stream mode: the first game id not yet taken
     int64_t ready_known = 0;  // ... and how many consecutive finished games the last az_engine_stream_ready found from there
     std::vector<int32_t> h_ring; // ... host copy of the rec_len ring for that scan
@@ -180,6 +191,41 @@ struct az_engine {
     struct alignas(16) HostBlock { unsigned char b[16]; };
     std::vector<HostBlock> h_records;
 };
+
+// What the rest of the library asks about the start of games (nobody outside csrc/az_starts.hip reads StartTable's kind or keyed).
+// Entries of the table in force by game id; 0 = none, every game starts from Params::start.
+static inline int64_t start_table_n(const az_engine *e) { return e->start.kind == START_UNIFORM ? 0 : e->start.n; }
+// No table, and a non-empty prefix gave Params::start.
+static inline bool start_prefixed(const az_engine *e) { return e->start.kind == START_UNIFORM && e->start.prefixed; }
+// Device array of the games' own start plies [start_table_n]; null = Params::start.ply for every game.
+static inline const int32_t *start_plies_dev(const az_engine *e) { return e->start.kind == START_PER_GAME ? e->start.plies : nullptr; }
+// Device array of the games' GIVEN key pairs [start_table_n][2]; null = every game is keyed from its start state.
+static inline const uint64_t *start_keys_dev(const az_engine *e) {
+    return e->start.kind == START_PER_GAME && e->start.keyed ? e->start.keys : nullptr;
+}
+// Start ply of game g, on the host.
+static inline int start_ply_of(const az_engine *e, int64_t g) {
+    return e->start.kind == START_PER_GAME ? e->start.h_plies[(size_t)g] : e->p.start.ply;
+}
+// Releases the table's arrays (the caller has taken it out of force).
+static inline void start_table_free(StartTable &t) {
+    if (t.states) (void)hipFree(t.states);
+    if (t.plies) (void)hipFree(t.plies);
+    if (t.keys) (void)hipFree(t.keys);
+    t.states = nullptr;
+    t.plies = nullptr;
+    t.keys = nullptr;
+    t.cap = 0;
+}
+
+#define HIPCHK(e, call)                                                                      \
+    do {                                                                                     \
+        hipError_t _s = (call);                                                              \
+        if (_s != hipSuccess) {                                                              \
+            (e)->err = std::string(#call) + ": " + hipGetErrorString(_s);                    \
+            return AZ_E_HIP;                                                                 \
+        }                                                                                    \
+    } while (0)
 
 // The packed root export (layout: include/az_engine.h, az_engine_export_roots_device): written by az_engine.hip, read by the
 // replay store's az_replay_refresh_from_roots.

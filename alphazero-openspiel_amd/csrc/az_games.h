@@ -91,7 +91,9 @@ AZ_HD bool az_c4_has_four(uint64_t b) {
 AZ_HD uint32_t az_c4_legal_mask(const AzState &s) {
     uint64_t occ = s.bb0 | s.bb1;
     uint32_t m = 0;
+#if defined(__clang__) // (hipcc; the host tests' g++ -Wall -Werror builds know no such pragma)
 #pragma unroll
+#endif
     for (int c = 0; c < 7; c++) m |= (uint32_t)(((occ >> (c * 7 + 5)) & 1ull) ^ 1ull) << c;
     return m;
 }
@@ -128,6 +130,20 @@ AZ_HD uint32_t az_bt_cell_moves(const AzState &s, const AzGeom &g, int cell) {
 AZ_HD int az_bt_encode(int cell, int me, int d, int capture) { return ((cell * 6 + (me ? 3 : 0) + d) << 1) | capture; }
 
 // ---------------------------------------------------------------- common
+// Is `action` - any int, A = az_num_actions - a legal move of the side to move?  az_apply assumes it is.
+//   connect_four : a column that is not full
+//   breakthrough : the cell holds a piece of the side to move, the direction is one of that side's three, the move is on the
+//                  board and not blocked, and the capture bit says what the move does
+template <int GAME> AZ_HD bool az_action_legal(const AzState &s, const AzGeom &g, int A, int action) {
+    if (action < 0 || action >= A) return false;
+    if (GAME == AZG_CONNECT_FOUR) return ((az_c4_legal_mask(s) >> action) & 1u) != 0;
+    const int cell = (action >> 1) / 6, d = (action >> 1) % 6 - ((s.ply & 1) ? 3 : 0);
+    if (d < 0 || d > 2) return false;
+    const uint32_t mv = az_bt_cell_moves(s, g, cell);
+    return (mv & (1u << d)) && (int)((mv >> (4 + d)) & 1u) == (action & 1);
+}
+
+
 // Applies `action` for the side to move.  Returns 0 = game continues, 1 = terminal; *ret0 = returns()[0].
 template <int GAME> AZ_HD int az_apply(AzState &s, const AzGeom &g, int action, float *ret0) {
     int me = s.ply & 1;

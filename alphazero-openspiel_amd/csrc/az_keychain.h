@@ -8,7 +8,7 @@
 //   a game with a GIVEN pair         the pair, step index of the j-th move = start ply + j = the absolute ply after the move
 // so a game that was given the pair of the history P and then plays m_1..m_k carries, at m_1..m_j, exactly the pair of an
 // ordinary game from the initial position whose history is P + m_1..m_j (include/az_replay.h, "the key rule").
-// Used by replay_keys_kernel (csrc/az_replay.hip) and by the host replay of az_engine_set_game_starts (csrc/az_engine.hip).
+// Used by replay_keys_kernel (csrc/az_replay.hip) and by the host replay of az_engine_set_game_starts (csrc/az_starts.h).
 #pragma once
 #include <stdint.h>
 

@@ -404,10 +404,8 @@ extern "C" int az_replay_append_engine(az_replay *r, az_engine *e, void *stream)
     a.max_plies = e->p.max_plies;
     a.maxc = e->p.maxc;
     a.start_ply = e->p.start.ply;
-    if (e->game_starts) { // a start per game: its own start ply and, when the table carries given pairs, its own key pair
-        a.start_plies = e->d_start_ply;
-        a.start_keys = e->starts_keyed ? e->d_start_keys : nullptr;
-    }
+    a.start_plies = start_plies_dev(e); // a start per game: its own start ply and, when the table carries given pairs, its own key pair
+    a.start_keys = start_keys_dev(e);
     a.on_policy = e->cfg.backup == AZ_BACKUP_ON_POLICY;
     if (!e->p.capdev) return append_common(r, a, lens, st);
     // a playout cap is in force: the engine's own mask of full-search moves decides which plies become examples
@@ -416,8 +414,8 @@ extern "C" int az_replay_append_engine(az_replay *r, az_engine *e, void *stream)
     RCHK(r, hipMalloc((void **)&d_keep, ng * mp));
     int rc = az_engine_full_moves_device(e, d_keep, (int64_t)ng, st);
     if (rc < 0) r->err = std::string("az_engine_full_moves_device: ") + az_last_error(e);
-    std::vector<int32_t> plies(ng, e->p.start.ply), kept;
-    if (rc >= 0 && e->game_starts) plies.assign(e->h_start_ply.begin(), e->h_start_ply.begin() + (long)ng);
+    std::vector<int32_t> plies(ng), kept;
+    for (size_t g = 0; rc >= 0 && g < ng; g++) plies[g] = start_ply_of(e, (int64_t)g); // (rc >= 0: ng is within the table)
     if (rc >= 0) rc = kept_counts(r, d_keep, lens, plies, (int32_t)mp, st, kept);
     if (rc >= 0) {
         a.keep = d_keep;

@@ -88,9 +88,7 @@ class SelfPlayEngine:
         self.G, self.A = z.n_slots, z.num_actions
         self.obs_shape = (z.obs_planes, z.rows, z.cols)
         self.max_plies, self.max_children = z.max_plies, z.max_children
-        self.start_history = []
-        self.start_histories = None  # set_start_positions / set_game_starts: one history per game
-        self.game_starts = None      # set_game_starts / set_game_starts_device: int32 array [n] of the games' start plies
+        self._starts()
         self.playout_cap = None      # set_playout_cap: (n_fast, p_full) while a cap is in force
         self.forced_playouts = None  # set_forced_playouts: (k, prune) while the setting is in force
         self.n_games = 0
@@ -103,6 +101,24 @@ class SelfPlayEngine:
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _starts(self, history=(), histories=None, game_starts=None):
+        """Where the games start, as the Python side keeps it - always the three together: start_history, the one prefix of
+        every game (injected draws are indexed from its end unless set_injected_rng(absolute_ply=True)); start_histories, one
+        history per game (set_start_positions / set_game_starts; None when the states came as positions); game_starts, the
+        int32 array [n] of the games' start plies (set_game_starts / set_game_starts_device)."""
+        self.start_history = [int(a) for a in history]
+        self.start_histories = None if histories is None else [[int(a) for a in h] for h in histories]
+        self.game_starts = game_starts
+
+    def _int_ptr(self, t, dtype, shape):
+        """Pointer to a contiguous integer tensor of this dtype and shape on the engine's device (None stays None)."""
+        if t is None:
+            return None
+        if t.dtype != dtype or not t.is_contiguous() or t.device != self.device or tuple(t.shape) != shape:
+            raise EngineError("expected a contiguous %s %s tensor on %s, got %s %s on %s"
+                              % (dtype, shape, self.device, t.dtype, tuple(t.shape), t.device))
+        return C.c_void_p(t.data_ptr())
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -132,9 +148,7 @@ class SelfPlayEngine:
     def set_start_prefix(self, actions):
         arr = (C.c_int32 * max(1, len(actions)))(*[int(a) for a in actions])
         self._check(self.lib.az_engine_set_start_prefix(self._h, arr, len(actions)))
-        self.start_history = [int(a) for a in actions]
-        self.start_histories = None
-        self.game_starts = None
+        self._starts(history=actions)
 
     def set_start_positions(self, histories):
         """A start position per game (manual_moves engines): histories[i] is the action list that leads from the initial
@@ -144,8 +158,7 @@ class SelfPlayEngine:
         ip = C.POINTER(C.c_int32)
         self._check(self.lib.az_engine_set_start_positions(self._h, actions.ctypes.data_as(ip), lengths.ctypes.data_as(ip),
                                                            stride, len(lengths)))
-        self.start_history = []  # injected draws are indexed by absolute ply (set_injected_rng(absolute_ply=True))
-        self.start_histories = [[int(a) for a in h] for h in histories]
+        self._starts(histories=histories)
 
     def set_start_states_device(self, bb, ply):
         """The device form of set_start_positions: game i starts from the state (bb[i, 0], bb[i, 1], ply[i]) - bb an int64
@@ -153,14 +166,9 @@ class SelfPlayEngine:
         as DeviceReplay.gather_states returns them.  Every state is checked on the device; a bad one raises EngineError
         naming the lowest offending game and the rule it breaks, and the previous table stays.  reset(n) afterwards."""
         n = int(ply.numel())
-        for t, dt, shape in ((bb, torch.int64, (n, 2)), (ply, torch.int32, (n,))):
-            if t.dtype != dt or not t.is_contiguous() or t.device != self.device or tuple(t.shape) != shape:
-                raise EngineError("expected a contiguous %s %s tensor on %s, got %s %s on %s"
-                                  % (dt, shape, self.device, t.dtype, tuple(t.shape), t.device))
-        self._check(self.lib.az_engine_set_start_states_device(self._h, C.c_void_p(bb.data_ptr()), C.c_void_p(ply.data_ptr()), n,
-                                                               self._stream()))
-        self.start_history = []
-        self.start_histories = None  # the histories are not known: the states came as positions
+        self._check(self.lib.az_engine_set_start_states_device(self._h, self._int_ptr(bb, torch.int64, (n, 2)),
+                                                               self._int_ptr(ply, torch.int32, (n,)), n, self._stream()))
+        self._starts()
 
     def set_game_starts(self, histories):
         """A start position per game for SELF-PLAY (az_engine_set_game_starts): game i of the next generation starts after the
@@ -172,9 +180,7 @@ class SelfPlayEngine:
         ip = C.POINTER(C.c_int32)
         self._check(self.lib.az_engine_set_game_starts(self._h, actions.ctypes.data_as(ip), lengths.ctypes.data_as(ip),
                                                        stride, len(lengths)))
-        self.start_history = []
-        self.start_histories = [[int(a) for a in h] for h in histories]
-        self.game_starts = lengths.copy()
+        self._starts(histories=histories, game_starts=lengths.copy())
 
     def set_game_starts_device(self, bb, ply, keys=None):
         """The device form of set_game_starts: game i starts from the state (bb[i, 0], bb[i, 1], ply[i]) - tensors as
@@ -182,16 +188,10 @@ class SelfPlayEngine:
         words; None: the games are keyed from their start states, as ordinary games that start there).  Every state is
         checked on the device; a bad one raises EngineError naming the lowest offending game, and the previous table stays."""
         n = int(ply.numel())
-        for t, dt, shape in ((bb, torch.int64, (n, 2)), (ply, torch.int32, (n,)), (keys, torch.int64, (n, 2))):
-            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != self.device or tuple(t.shape) != shape):
-                raise EngineError("expected a contiguous %s %s tensor on %s, got %s %s on %s"
-                                  % (dt, shape, self.device, t.dtype, tuple(t.shape), t.device))
         self._check(self.lib.az_engine_set_game_starts_device(
-            self._h, C.c_void_p(bb.data_ptr()), C.c_void_p(ply.data_ptr()), C.c_void_p(keys.data_ptr()) if keys is not None else None,
-            n, self._stream()))
-        self.start_history = []
-        self.start_histories = None  # the histories are not known: the states came as positions
-        self.game_starts = ply.cpu().numpy().astype(np.int32)
+            self._h, self._int_ptr(bb, torch.int64, (n, 2)), self._int_ptr(ply, torch.int32, (n,)),
+            self._int_ptr(keys, torch.int64, (n, 2)), n, self._stream()))
+        self._starts(game_starts=ply.cpu().numpy().astype(np.int32))
 
     def game_starts_device(self, n_games=None):
         """-> (ply int32 [n], keys int64 [n, 2] or None) device tensors: every game id's start ply and history key pair, what

@@ -303,6 +303,49 @@ def test_refusals_name_their_reason_and_leave_the_table_alone():
     eng.close()
 
 
+def test_setters_of_every_kind_replace_and_clear_one_another():
+    """The transitions between the kinds of start (uniform, per position, per game; keyed or not; a table that grows; a refused
+    call).  Neither engine is ticked."""
+    from alphazero_openspiel_amd import engine as E
+    game = games.load_game(C4)
+    kw = dict(n_slots=8, n_playouts=4, max_games=8)
+    man = _engine(C4, manual_moves=True, **kw)
+    man.set_start_positions([[3], [3, 2], []])
+    man.set_start_states_device(*_tensors(*RA.states_of(game, [[3, 2, 4], [3, 3, 2, 4]])))
+    with pytest.raises(E.EngineError, match=r"\(%d\).*n_games exceeds" % AZ_E_INVALID):
+        man.reset(3)
+    man.reset(2)
+    assert [man.read_slot(g)["ply"] for g in range(2)] == [3, 4]                                # the device states
+    man.set_start_prefix([3])                                                                  # clears the table
+    man.reset(8)
+    assert [man.read_slot(g)["ply"] for g in range(8)] == [1] * 8
+    man.close()
+
+    def pairs(keys):
+        return [tuple(r) for r in keys.cpu().numpy().view(np.uint64).tolist()]
+
+    eng = _engine(C4, **kw)
+    eng.set_game_starts([[3], [3, 2]])                                                          # keyed, 2 entries
+    five = [[], [3], [3, 2], [3, 2, 4], [3, 3, 2, 4]]
+    eng.set_game_starts_device(*_tensors(*RA.states_of(game, five)), keys=None)                 # not keyed, and the table grows
+    ply, keys = eng.game_starts_device(5)
+    assert keys is None and ply.cpu().tolist() == [0, 1, 2, 3, 4]
+    three = [[3, 2, 4], [], [4, 2, 3]]
+    eng.set_game_starts(three)                                                                  # keyed again
+    ply, keys = eng.game_starts_device(3)
+    assert ply.cpu().tolist() == [3, 0, 3] and pairs(keys) == [_chain(game, [], h)[1] for h in three]
+    bad_bb, bad_ply = _tensors(*RA.states_of(game, five + [[0, 6]]))                            # more games than the table can hold
+    bad_ply[4] = 9
+    with pytest.raises(E.EngineError, match=r"az_engine_set_game_starts_device: game 4: "):
+        eng.set_game_starts_device(bad_bb, bad_ply)
+    ply, keys = eng.game_starts_device(3)                                                       # the keyed table of 3 is in force
+    assert ply.cpu().tolist() == [3, 0, 3] and pairs(keys) == [_chain(game, [], h)[1] for h in three]
+    assert eng.game_starts.tolist() == [3, 0, 3]
+    with pytest.raises(E.EngineError, match=r"\(%d\).*n_games exceeds" % AZ_E_INVALID):
+        eng.reset(4)
+    eng.close()
+
+
 def test_append_device_checks_the_start_plies_before_any_kernel():
     game = games.load_game(C4)
     ex = RC.fake_export(game, n_games=4, seed=1, start_history=[3, 2])

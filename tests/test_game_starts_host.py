@@ -1,10 +1,12 @@
 """CPU-only checks of self-play from per-game start positions: the C ABI surface of its five entries, the scalar / array forms
-of examples_from_export and unpack_device_export, and the HOST build of the shared key-chain header (csrc/az_keychain.h)
-against a Python restatement of the chain written here.
+of examples_from_export and unpack_device_export, the HOST build of the shared key-chain header (csrc/az_keychain.h)
+against a Python restatement of the chain written here, and the host replay of an action prefix (csrc/az_starts.h) against
+games.py and that chain.
 
-The header is checked through a small stand-alone C++ program compiled at test time (g++, where AZ_KEY_HD is plain `inline`):
-the library's entries need a device, the shared header does not."""
+The headers are checked through small stand-alone C++ programs compiled at test time (g++, where AZ_KEY_HD is plain `inline`):
+the library's entries need a device, the shared headers do not."""
 import ctypes as C
+import functools
 import os
 import re
 import subprocess
@@ -213,3 +215,115 @@ def test_header_chain_is_the_python_chain_and_obeys_the_key_rule(name, header_ch
         a, b = _chain(game, [], [3, 2, 4])[1], _chain(game, [], [4, 2, 3])[1]
         assert games.state_from_history(game, [3, 2, 4]).bb == games.state_from_history(game, [4, 2, 3]).bb
         assert a[0] != b[0] and a[1] != b[1]
+
+
+# ------------------------------------------------------------------------------------------------ the host replay of a prefix
+# csrc/az_starts.h: the position and key pair of an action prefix, and the game's legality check of every action id, against
+# games.py and the Python chain above.  Every comparison is exact.
+_STARTS_PROGRAM = r"""
+#include <cstdio>
+#include <vector>
+#include "az_starts.h"
+int main() { // per line: game rows cols n a_1 .. a_n  ->  code bb0 bb1 ply key key2
+    int game, rows, cols, n;
+    while (scanf("%d %d %d %d", &game, &rows, &cols, &n) == 4) {
+        std::vector<int32_t> a((size_t)n + 1);
+        for (int i = 0; i < n; i++)
+            if (scanf("%d", &a[(size_t)i]) != 1) return 1;
+        const AzGeom g = az_make_geom(game, rows, cols);
+        AzState s;
+        AzKeyPair k;
+        const int code = az_replay_prefix(game, g, az_num_actions(game, rows, cols), a.data(), n, s, k);
+        printf("%d %llu %llu %d %llu %llu\n", code, (unsigned long long)s.bb0, (unsigned long long)s.bb1, s.ply,
+               (unsigned long long)k.key, (unsigned long long)k.key2);
+    }
+    return 0;
+}
+"""
+STARTS_GAMES = ["connect_four", "breakthrough(rows=6,columns=6)", "breakthrough(rows=5,columns=4)"]
+
+
+@pytest.fixture(scope="module")
+def header_replay(tmp_path_factory):
+    d = tmp_path_factory.mktemp("starts")
+    src, exe = d / "starts.cpp", d / "starts"
+    src.write_text(_STARTS_PROGRAM)
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "alphazero-openspiel_amd", "csrc"),
+                           str(src), "-o", str(exe)])
+
+    def run(game, prefixes):
+        """[(code, bb0, bb1, ply, key, key2)] of the header's replay, one per prefix."""
+        head = "%d %d %d " % (game.game_id, game.rows, game.cols)
+        text = "".join(head + " ".join(map(str, [len(p)] + list(p))) + "\n" for p in prefixes)
+        out = subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
+        assert len(out) == len(prefixes)
+        return [tuple(int(w) for w in line.split()) for line in out]
+
+    return run
+
+
+@functools.lru_cache(maxsize=None)
+def _played_games(name):
+    game = games.load_game(name)
+    ex = RC.fake_export(game, n_games=3, seed=33)
+    return game, [ex["move"][g, :int(ex["game_len"][g])].tolist() for g in range(3)]
+
+
+def test_starts_header_compiles_without_warnings(header_replay):
+    """The fixture builds with -Wall -Werror; the empty prefix is the initial position with its seed pair."""
+    for name in STARTS_GAMES:
+        game = games.load_game(name)
+        s0 = games.state_from_history(game, [])
+        assert header_replay(game, [[]]) == [(0, int(s0.bb[0]), int(s0.bb[1]), 0) + _seed(0, int(s0.bb[0]), int(s0.bb[1]))]
+
+
+@pytest.mark.parametrize("name", STARTS_GAMES)
+def test_header_replay_gives_the_state_and_key_pair_of_every_prefix(name, header_replay):
+    game, played = _played_games(name)
+    prefixes = [moves[:n] for moves in played for n in range(len(moves))]
+    want = []
+    for p in prefixes:
+        s = games.state_from_history(game, p)
+        want.append((0, int(s.bb[0]), int(s.bb[1]), len(p)) + _chain(game, [], p)[1])
+    assert header_replay(game, prefixes) == want
+
+
+@pytest.mark.parametrize("name", STARTS_GAMES)
+def test_header_replay_judges_every_action_id_as_the_python_rules_do(name, header_replay):
+    """At every position along the games, every id in [-1, A]: code 1 exactly for the ids games.py does not list (-1 and A among
+    them, and a breakthrough move whose capture bit says the wrong thing), 2 exactly when the move ends the game, 0 otherwise."""
+    game, played = _played_games(name)
+    A = game.num_distinct_actions()
+    cases, want = [], []
+    seen = {"capture": 0, "plain": 0, "ends": 0}
+    for moves in played:
+        for n in range(len(moves)):
+            s = games.state_from_history(game, moves[:n])
+            legal = set(s.legal_actions())
+            assert moves[n] in legal
+            for a in range(-1, A + 1):
+                cases.append(moves[:n] + [a])
+                if a not in legal:
+                    want.append(1)
+                    continue
+                t = s.clone()
+                t.apply_action(a)
+                want.append(2 if t.is_terminal() else 0)
+                seen["ends"] += t.is_terminal()
+                if game.game_id == 1:                      # the twin with the other capture bit is no move
+                    assert a ^ 1 not in legal
+                    seen["capture" if a & 1 else "plain"] += 1
+        # the whole game ends with its last move, and moves after the end do not change that - legal-looking ones or not
+        cases += [moves, moves + [moves[0]], moves + [A]]
+        want += [2, 2, 2]
+    got = header_replay(game, cases)
+    assert [r[0] for r in got] == want
+    assert seen["ends"] >= len(played) and (game.game_id == 0 or (seen["capture"] > 0 and seen["plain"] > 0))
+    if game.game_id == 0:
+        column = [0, 1, 0, 1, 0, 1]                        # four in column 0 for the first player
+        assert [r[0] for r in header_replay(game, [column, column + [0], column + [0, 3], [3] * 6, [3] * 7])] == [0, 2, 2, 0, 1]
+    else:
+        # a move onto the last rank: one of the random games ends that way (not by capturing the last piece)
+        ends = [games.state_from_history(game, moves) for moves in played]
+        last_ranks = ((1 << game.cols) - 1) << ((game.rows - 1) * game.cols), (1 << game.cols) - 1
+        assert any(s.bb[0] & last_ranks[0] or s.bb[1] & last_ranks[1] for s in ends)
