@@ -311,6 +311,14 @@ static void call_policy(orc_mcts *m, const orc_state *s, double *value) {
     m->n_evals++;
 }
 
+/* test read-back: the deepest playout of any tree since the last reset (tests/test_deep_lines_*.py) */
+static int64_t g_max_depth = 0;
+int64_t orc_max_depth(int reset) {
+    int64_t d = g_max_depth;
+    if (reset) g_max_depth = 0;
+    return d;
+}
+
 /* mcts.py:126-153 — `state` is the caller's clone and is modified */
 void orc_mcts_playout(orc_mcts *m, orc_state *state) {
     orc_node *node = m->root;
@@ -337,6 +345,7 @@ void orc_mcts_playout(orc_mcts *m, orc_state *state) {
     node_update_recursive(node, -leaf_value);
     m->n_sims++;
     m->sum_depth += depth;
+    if (depth > g_max_depth) g_max_depth = depth;
 }
 
 /* mcts.py:182-190; eta = the Dirichlet(0.3) draw of length n_legal */

@@ -92,6 +92,8 @@ def lib():
     L.orc_opponent_action.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_int32]
     L.orc_nodes_alive.restype = C.c_int64
     L.orc_nodes_total.restype = C.c_int64
+    L.orc_max_depth.restype = C.c_int64
+    L.orc_max_depth.argtypes = [C.c_int]
     _lib = L
     return L
 
@@ -238,6 +240,11 @@ class MCTS:
         out = np.zeros(5, dtype=np.int64)
         lib().orc_mcts_counters(self._m, _lp(out))
         return dict(zip(("sims", "evals", "terminal_hits", "sum_depth", "sum_children"), out.tolist()))
+
+
+def max_depth(reset=True):
+    """The deepest playout of any oracle tree since the last reset."""
+    return int(lib().orc_max_depth(int(reset)))
 
 
 def np_sum(a):

@@ -24,6 +24,9 @@ oracle/fakepolicy.py as policy_fn):
                       alphazerobot.py:42-120)
   trainer_on_engine_export.npz  Trainer.remove_duplicates and one net_step on the engine-produced records of
                       engine_export_connect_four.npz (that fixture must exist first)
+  mcts_trace_deep.json  MCTS.playout and MCTS.update_root under the line policy of tests/deep_line_cases.py: searches whose
+                      playouts run 42 / 148 plies deep (a 26x2 breakthrough board and connect_four), root statistics after
+                      every 16th playout, then while descending the principal line with update_root (every 8th depth)
   rules_*.json        random playouts of oracle/pygames.py (NOT reference output:
                       OpenSpiel is absent; rules are "parity unpinned")
 
@@ -219,6 +222,52 @@ def gen_mcts_traces_uct(ref):
         cases.append({"game": game_name, "prefix": [int(a) for a in prefix], "n_playouts": S, "use_dirichlet": use_dir,
                       "c_puct": c_puct, "dirichlet_ratio": 0.25, "salt": salt, "leaf_update": leaf_update,
                       "searches": searches})
+    return cases
+
+
+def gen_mcts_traces_deep(ref):
+    """Searches that run DEEP (tests/deep_line_cases.py: the line policy), then MCTS.update_root (mcts.py:192-203) down the most
+    visited line to its leaf: pins the oracle at the depths tests/test_deep_lines_gpu.py compares the engine with it."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import deep_line_cases as DL
+    cases = []
+    for key in ("bt26x2", "c4"):
+        c = DL.CASES[key]
+        game = pygames.load_game(c["game"])
+        A = game.num_distinct_actions()
+        shape = game.information_state_normalized_vector_shape()
+        pol = DL.case_policy(key)
+
+        def pf(state, _pol=pol, _shape=shape):
+            pri, val = _pol(ref.network.state_to_board(state, _shape))
+            return pri.tolist(), float(val)
+
+        S = c["n_playouts"]
+        state = game.new_initial_state()
+        tree = ref.mcts.MCTS(pf, A, c_puct=2.5, n_playouts=S, use_dirichlet=c["eta"] is not None, dirichlet_ratio=0.25)
+        if c["eta"] is not None:  # the case's own noise vector instead of a draw
+            orig = np.random.dirichlet
+            np.random.dirichlet = lambda alpha, size=None, _e=c["eta"]: np.array(_e[:len(alpha)], dtype=np.float64)
+            try:
+                tree.expand_root_dirichlet(state)
+            finally:
+                np.random.dirichlet = orig
+        after_expand = root_stats(tree.root)
+        trace = {}
+        for k in range(1, S + 1):
+            tree.playout(state.clone())
+            if k % 16 == 0 or k == S:
+                trace[str(k)] = root_stats(tree.root)
+        descent, depth = [], 0
+        while not tree.root.is_leaf():
+            st = root_stats(tree.root)
+            a = st["actions"][int(np.argmax(st["cN"]))]
+            tree.update_root(a)
+            depth += 1
+            if depth % 8 == 0 or tree.root.is_leaf():
+                descent.append({"depth": depth, "action": int(a), "root": root_stats(tree.root)})
+        cases.append({"key": key, "game": c["game"], "n_playouts": S, "salt": c["salt"], "vs": c["vs"], "eta": c["eta"],
+                      "after_root_expand": after_expand, "trace": trace, "descent": descent})
     return cases
 
 
@@ -538,6 +587,7 @@ def main():
 
     dump("mcts_trace.json", gen_mcts_traces(ref))
     dump("mcts_trace_uct.json", gen_mcts_traces_uct(ref))
+    dump("mcts_trace_deep.json", gen_mcts_traces_deep(ref))
     dump("selfplay.json", gen_selfplay(ref))
     dump("selfplay_npa.json", gen_selfplay(ref, SELFPLAY_NPA_SPECS))
     dump("remove_illegal.json", gen_remove_illegal(ref))

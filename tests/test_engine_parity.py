@@ -170,7 +170,7 @@ def _run_games(E, game, n_games, n_slots, salt, etas, us, **kw):
     eng = E.SelfPlayEngine(game, n_slots, rng="injected", max_games=n_games, **kw)
     eng.reset(n_games)
     eng.set_injected_rng(etas, us)
-    ev = E.HostPolicyEvaluator(eng, _board_fn(eng.A, salt))
+    ev = E.HostPolicyEvaluator(eng, salt if callable(salt) else _board_fn(eng.A, salt))  # (a board function of the caller's)
     obs, pri, val = eng.alloc_io()
     for _ in range(200000):
         eng.advance(pri, val, obs)

@@ -154,3 +154,31 @@ def test_arena_games_between_reference_bots(idx):
     got = orc.play_duel_game(p1, p2, c["game"], c["bot1_side"], n_playouts1=c["n_playouts"][0], n_playouts2=c["n_playouts"][1],
                              c_puct1=c["c_puct"][0], c_puct2=c["c_puct"][1], agent1=c["agents"][0], agent2=c["agents"][1])
     assert got["actions"] == c["actions"] and got["ret0"] == c["ret0"]
+
+
+@pytest.mark.parametrize("idx", range(2))
+def test_mcts_trace_deep_matches_reference(idx):
+    """tests/golden/mcts_trace_deep.json: the line policy of deep_line_cases.py, playouts 148 (breakthrough 26x2) and 42
+    (connect_four) plies deep, then update_root down the most visited line to its leaf - the oracle at the depths
+    test_deep_lines_gpu.py compares the engine with it."""
+    import deep_line_cases as DL
+    case = load_golden("mcts_trace_deep.json")[idx]
+    c = DL.CASES[case["key"]]
+    assert (case["game"], case["n_playouts"], case["salt"], case["vs"], case["eta"]) == \
+        (c["game"], c["n_playouts"], c["salt"], c["vs"], c["eta"])
+    m = orc.MCTS(DL.case_policy(case["key"]), c["game"], n_playouts=c["n_playouts"], use_dirichlet=c["eta"] is not None)
+    s = orc.State(c["game"])
+    if c["eta"] is not None:
+        m.expand_root_dirichlet(s, c["eta"])
+    assert m.root_stats() == case["after_root_expand"]
+    for k in range(1, c["n_playouts"] + 1):
+        m.playout(s)
+        if str(k) in case["trace"]:
+            assert m.root_stats() == case["trace"][str(k)], "after playout %d" % k
+    assert str(c["n_playouts"]) in case["trace"]
+    want = {d["depth"]: d for d in case["descent"]}
+    descent = DL.oracle_descent(m)
+    assert len(descent) == max(want) >= (130 if idx == 0 else 42)
+    for depth, (a, root) in enumerate(descent, 1):
+        if depth in want:
+            assert a == want[depth]["action"] and root == want[depth]["root"], "depth %d" % depth
