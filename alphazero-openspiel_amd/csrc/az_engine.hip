@@ -2819,7 +2819,8 @@ extern "C" int64_t az_engine_read_tree(az_engine *e, int32_t slot, int64_t max_n
         uint32_t nd = order[i];
         if (C0[nd] == NONE32) continue;
         uint32_t nc = M[nd] >> 16;
-        if (C0[nd] + nc > alloc) {
+        // (a tree holds every pool node at most once: links that share or revisit a block would make this walk endless)
+        if (C0[nd] + nc > alloc || order.size() + nc > (size_t)alloc) {
             e->err = "corrupt tree";
             return AZ_E_DEVICE;
         }

@@ -414,6 +414,48 @@ int orc_mcts_root_stats(const orc_mcts *m, int64_t *rootN, double *rootQ, int32_
     return m->root->n_children;
 }
 
+/* whole-tree read-back for tests, read-only: breadth-first from the root, the children of a node consecutive and in
+ * insertion (ascending-action) order, unvisited ones included - the order and meaning of az_engine_read_tree.  parent = the
+ * row of the parent, -1 (and action -1) for the root.  Fills at most max_nodes rows (0: none, the arrays may be NULL) and
+ * returns the number of nodes of the tree; -1 if the queue cannot be allocated. */
+int64_t orc_mcts_dump_tree(const orc_mcts *m, int64_t max_nodes, int32_t *parent, int32_t *action, int64_t *N, double *Q,
+                           double *P) {
+    int64_t cap = 1024, cnt = 0;
+    const orc_node **queue = (const orc_node **)malloc(sizeof *queue * (size_t)cap);
+    if (!queue) return -1;
+    queue[cnt++] = m->root;
+    for (int64_t i = 0; i < cnt; i++) {
+        const orc_node *nd = queue[i];
+        if (cnt + nd->n_children > cap) {
+            while (cnt + nd->n_children > cap) cap *= 2;
+            const orc_node **q2 = (const orc_node **)realloc((void *)queue, sizeof *queue * (size_t)cap);
+            if (!q2) {
+                free((void *)queue);
+                return -1;
+            }
+            queue = q2;
+        }
+        for (int k = 0; k < nd->n_children; k++) {
+            if (cnt < max_nodes) {
+                parent[cnt] = (int32_t)i;
+                action[cnt] = nd->actions[k];
+            }
+            queue[cnt++] = nd->children[k];
+        }
+    }
+    if (max_nodes > 0) {
+        parent[0] = -1;
+        action[0] = -1;
+    }
+    for (int64_t i = 0; i < cnt && i < max_nodes; i++) {
+        N[i] = queue[i]->N;
+        Q[i] = queue[i]->Q;
+        P[i] = queue[i]->P;
+    }
+    free((void *)queue);
+    return cnt;
+}
+
 void orc_mcts_counters(const orc_mcts *m, int64_t *out5) {
     out5[0] = m->n_sims;
     out5[1] = m->n_evals;

@@ -82,6 +82,8 @@ def lib():
     L.orc_mcts_update_root.argtypes = [vp, C.c_int]
     L.orc_mcts_root_stats.argtypes = [vp, lp, dp, ip, lp, dp, dp]
     L.orc_mcts_counters.argtypes = [vp, lp]
+    L.orc_mcts_dump_tree.restype = C.c_int64
+    L.orc_mcts_dump_tree.argtypes = [vp, C.c_int64, ip, ip, lp, dp, dp]
     L.orc_np_sum.argtypes = [dp, C.c_int]
     L.orc_np_sum.restype = C.c_double
     L.orc_remove_illegal_actions.argtypes = [dp, C.c_int, ip, C.c_int]
@@ -235,6 +237,19 @@ class MCTS:
         n = lib().orc_mcts_root_stats(self._m, _lp(rn), _dp(rq), _ip(acts), _lp(cn), _dp(cq), _dp(cp))
         return {"N": int(rn[0]), "Q": float(rq[0]), "actions": acts[:n].tolist(), "cN": cn[:n].tolist(),
                 "cQ": cq[:n].tolist(), "cP": cp[:n].tolist()}
+
+    def dump_tree(self):
+        """Whole tree, breadth-first: the dict of numpy arrays parent/action/N/Q/P that SelfPlayEngine.read_tree returns."""
+        L = lib()
+        n = L.orc_mcts_dump_tree(self._m, 0, None, None, None, None, None)
+        if n < 0:
+            raise MemoryError("orc_mcts_dump_tree")
+        par, act = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        N, Q, P = np.zeros(n, np.int64), np.zeros(n, np.float64), np.zeros(n, np.float64)
+        got = L.orc_mcts_dump_tree(self._m, n, _ip(par), _ip(act), _lp(N), _dp(Q), _dp(P))
+        if got != n:
+            raise RuntimeError("orc_mcts_dump_tree returned %d nodes, then %d" % (n, got))
+        return {"parent": par, "action": act, "N": N, "Q": Q, "P": P}
 
     def counters(self):
         out = np.zeros(5, dtype=np.int64)
