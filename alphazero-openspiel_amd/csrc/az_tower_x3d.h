@@ -35,6 +35,7 @@
 // (tests/test_fused_net.py).  Own code here where the packed tiles differ: the scratch destinations come from the host's table, the
 // compact-plane address is derived (p6_of), the stream addressing is X3D's chunking (X3DS::a_off), and the stores need no mask.  The epilogue's plane
 // stores need no mask here: every lane of a tile is a real position, and a board past the batch computes on zero planes.
+// The tower output goes to an image of the workgroup's rows of xout / xout_lo in LDS (X3DG::OFF_OUT) and leaves in whole lines.
 #pragma once
 #include "az_net_common.h"
 #include "az_tower_x3b_parts.h"
@@ -100,6 +101,13 @@ template <int V> struct X3DG {
     static constexpr int PLANE_B = PC * OCT_B, LO_OFF = 6 * PLANE_B + PC * 4; // hi: 6 octet planes + the compact plane of channels 48, 49
     static constexpr int S_PLANE = NCOL * 8, OFF_ACT = X3D::OFF_S + 9 * S_PLANE, LDS = OFF_ACT + 2 * LO_OFF;
     static_assert(LDS <= 160 * 1024 && LO_OFF < 65536 && 9 * S_PLANE < 65536 && PC % 16 == 0, "x3d LDS budget / ds offset fields / plane stride a multiple of 256 B");
+    // The tower output leaves through LDS: behind the last conv's k-loop the scratch and the planes are dead, and the last epilogue
+    // writes the workgroup's rows of xout (hi) and xout_lo there as they lie in memory - position gp = board * HW + cell at gp *
+    // out_stride, channel c at + 2 c - so that the copy-out reads 16 bytes per lane and a wave store covers one contiguous KiB.
+    // A 64-channel row is a multiple of the 256 bytes of the banks: 16 bytes of padding per position spread the epilogue's stores.
+    static constexpr int OFF_OUT = X3D::OFF_S;
+    __device__ static constexpr int out_stride(int xout_c) { return xout_c * 2 % 128 ? xout_c * 2 : xout_c * 2 + 16; }
+    static_assert(OFF_OUT % 16 == 0 && 2 * NCOL * (AZ_NET_XOUT_C * 2 + 16) <= LDS - OFF_OUT, "the image of both planes fits the dead scratch + planes");
 };
 
 template <int V>
@@ -173,7 +181,6 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
         int tile[NTA];
         unsigned baseL[NTA]; // LDS address of the lane's cell in octet plane 0 (hi)
         int grow[NTA];       // (prologue only) global board * HW + position of the lane's column, -1 = a board past the batch
-        unsigned livem = 0;  // bit nt: the column of tile nt belongs to a board of the batch
 #pragma unroll
         for (int nt = 0; nt < NTA; nt++) {
             tile[nt] = nt < NTW ? VV::first(wave) + nt : VV::split_tile(wave);
@@ -183,7 +190,6 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
             baseL[nt] = lds_base + G::OFF_ACT + cell * OCT_B;
             const int gb = blockIdx.x * p.xd_nb + b;
             grow[nt] = gb < p.n_boards ? gb * p.HW + pos : -1;
-            livem |= (gb < p.n_boards ? 1u : 0u) << nt;
         }
         // the lane's cell in the compact plane of channels 48, 49 (4 bytes per cell), from its octet-plane address (16 bytes per cell);
         // opaque: derived where it is used, not carried in a register per tile
@@ -423,15 +429,13 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
                 constexpr int mt = decltype(mt_c)::value;
                 const int co0 = 16 * mt + 4 * q;
                 const f32x4 o = x3b_epilogue_value<KIND, TT, IS_FIRST>(a, xr, s, sc, sh, next_bias, q);
-                if constexpr (KIND == 2) { // o: the tower output
+                if constexpr (KIND == 2) { // o: the tower output -> the workgroup's image of its rows of xout / xout_lo (G::OFF_OUT; copied out
+                                           // whole lines at the end of the kernel); every board: the copy-out leaves out the boards past the batch
                     half4 hi, lo;
                     split4(o, hi, lo);
-                    if (((opaque((int)livem) >> nt) & 1) && co0 < p.xout_c) { // a board of the batch (the column's global row, looked up again: once per
-                                                                            // forward); channels past the stride (tile T, q > 0) are not stored
-                        const int e = p.xd_pos[tile[nt] * 16 + l15];
-                        const size_t gr = (size_t)(blockIdx.x * p.xd_nb + (e >> 8)) * p.HW + (e & 255);
-                        *(half4 *)(p.xout + gr * p.xout_c + co0) = hi;
-                        *(half4 *)(p.xout_lo + gr * p.xout_c + co0) = lo;
+                    if (!TT || co0 < p.xout_c) { // channels past the stride (tile T, q > 0 at the 52-channel stride) are not stored
+                        lds_write64_off<32 * mt>(sa_hi, __builtin_bit_cast(f32x2, hi));
+                        lds_write64_off<32 * mt>(sa_lo, __builtin_bit_cast(f32x2, lo));
                     }
                     return;
                 }
@@ -474,8 +478,15 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
                 const unsigned qoff = (unsigned)((q >> 1) * plane_b + (q & 1) * 8);
 #pragma unroll
                 for (int nt = 0; nt < NTA; nt++) {
-                    sa_hi[nt] = addr_add((unsigned)opaque((int)baseL[nt]), qoff);
-                    sa_lo[nt] = sa_hi[nt] + LO_OFF;
+                    if constexpr (decltype(kind)::value == 2) { // the image: the lane's quarter-octet of channels 0..15 of its position's row (the column's
+                                                                // position, looked up again: once per forward)
+                        const int e = p.xd_pos[tile[nt] * 16 + l15], gp = (e >> 8) * p.HW + (e & 255);
+                        sa_hi[nt] = lds_base + G::OFF_OUT + gp * G::out_stride(p.xout_c) + q * 8;
+                        sa_lo[nt] = sa_hi[nt] + G::NCOL * G::out_stride(p.xout_c);
+                    } else {
+                        sa_hi[nt] = addr_add((unsigned)opaque((int)baseL[nt]), qoff);
+                        sa_lo[nt] = sa_hi[nt] + LO_OFF;
+                    }
                 }
                 static_for<3>([&](auto mt_c) {
                     constexpr int mt = decltype(mt_c)::value;
@@ -517,4 +528,21 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
         else if (wave == 6) body(I2, I1, I2);
         else body(I2, I2, I0);
     } else body(I2, I0, I0);
+    // ---- copy-out (behind the barrier that ends the last conv): the image -> the workgroup's rows of xout and xout_lo, 16 bytes per
+    // lane, consecutive lanes on consecutive addresses; the rows of boards past the batch are not written
+    {
+        const int row_b = p.HW * p.xout_c * 2, pos_b = p.xout_c * 2, stride = G::out_stride(p.xout_c);
+        const int left = p.n_boards - blockIdx.x * p.xd_nb, n16 = (left < p.xd_nb ? left : p.xd_nb) * (row_b >> 4);
+        unsigned char *g_hi = (unsigned char *)p.xout + (size_t)blockIdx.x * p.xd_nb * row_b, *g_lo = (unsigned char *)p.xout_lo + (size_t)blockIdx.x * p.xd_nb * row_b;
+        for (int i = tid; i < n16; i += 512) {
+            int src = i * 16; // (stride == pos_b: the image is the rows themselves)
+            if (stride != pos_b) {
+                const int gp = pos_b == 128 ? i >> 3 : i * 16 / pos_b;
+                src += gp * (stride - pos_b);
+            }
+            const uint4 h = *(const uint4 *)(lds + G::OFF_OUT + src), l = *(const uint4 *)(lds + G::OFF_OUT + G::NCOL * stride + src);
+            *(uint4 *)(g_hi + (size_t)i * 16) = h;
+            *(uint4 *)(g_lo + (size_t)i * 16) = l;
+        }
+    }
 }
