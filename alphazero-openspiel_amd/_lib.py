@@ -113,6 +113,8 @@ PROTOTYPES = [
     ("az_engine_set_playout_cap", C.c_int, [_vp, C.c_int32, C.c_double]),
     ("az_engine_full_moves_device", C.c_int, [_vp, _vp, C.c_int64, _vp]),
     ("az_engine_set_forced_playouts", C.c_int, [_vp, C.c_double, C.c_int32]),
+    ("az_engine_set_eval_mirror", C.c_int, [_vp, C.c_double]),
+    ("az_engine_read_request_mirror", C.c_int, [_vp, C.c_int32]),
     ("az_engine_advance", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     ("az_engine_advance_slots", C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     ("az_engine_compact_rows", C.c_int, [_vp, C.POINTER(C.c_int32), _vp]),

@@ -76,10 +76,12 @@ class Analyzer:
             an.search()
 
     policy_fn: the network (an nn.Module or its bound .predict), or an evaluator object (FusedNet, DeviceEvaluator,
-    HostPolicyEvaluator); None = set `.evaluator` (any callable(obs, priors_out, values_out)) before the first search."""
+    HostPolicyEvaluator); None = set `.evaluator` (any callable(obs, priors_out, values_out)) before the first search.
+    eval_mirror=p: every request of every search is evaluated left-right mirrored with probability p and mapped back
+    (SelfPlayEngine.set_eval_mirror; the coin is keyed by seed, position index, ply and request)."""
 
     def __init__(self, policy_fn, game_name, n_slots, n_playouts=100, c_puct=2.5, use_dirichlet=False, device=None,
-                 eval_backend="fused", eval_precision="f32x", seed=None, check_every=16, pv_depth=0, **kwargs):
+                 eval_backend="fused", eval_precision="f32x", seed=None, check_every=16, pv_depth=0, eval_mirror=None, **kwargs):
         if int(n_slots) < 1:
             raise ValueError("n_slots must be positive")
         if int(check_every) < 1:
@@ -96,6 +98,8 @@ class Analyzer:
         self.evaluator, self._owns_evaluator = None, False
         self._eval_backend, self._eval_precision = eval_backend, eval_precision
         try:
+            if eval_mirror is not None:
+                self.engine.set_eval_mirror(eval_mirror)
             if policy_fn is not None:
                 self.evaluator, self._owns_evaluator = _make_evaluator(policy_fn, self.engine.device, eval_backend,
                                                                        eval_precision, int(n_slots))
@@ -263,7 +267,8 @@ def dense_roots(roots, n, num_actions):
 
 
 def analyze_positions(policy_fn, game_name, histories, n_playouts=100, c_puct=2.5, use_dirichlet=False, n_slots=None,
-                      device=None, eval_backend="fused", eval_precision="f32x", seed=None, check_every=16, pv_depth=0, **kwargs):
+                      device=None, eval_backend="fused", eval_precision="f32x", seed=None, check_every=16, pv_depth=0,
+                      eval_mirror=None, **kwargs):
     """Search every given position with n_playouts of PUCT search, all of them side by side on the device.
 
     policy_fn   the network (nn.Module or its bound .predict) or an evaluator object, as elsewhere in the package
@@ -272,6 +277,7 @@ def analyze_positions(policy_fn, game_name, histories, n_playouts=100, c_puct=2.
                 evaluator.  With the fused network at f32x the results do not depend on it.
     pv_depth    D > 0: also return every position's principal variation - pv_actions [n, D] (-1 padded), pv_n, pv_q [n, D],
                 pv_len [n] (the whole greedy line's length) and greedy_value [n] (the off-policy target A0GB at its end)
+    eval_mirror p: every request is evaluated left-right mirrored with probability p (SelfPlayEngine.set_eval_mirror)
     kwargs      further SelfPlayEngine keywords (dirichlet_ratio, use_puct, nodes_per_slot, max_sims_per_tick, ...)
 
     Returns a dict, rows in the order given: visits [n, A] int64, q [n, A], priors [n, A] float64 (zero where there is no
@@ -285,7 +291,8 @@ def analyze_positions(policy_fn, game_name, histories, n_playouts=100, c_puct=2.
     if n_slots < 1:
         raise ValueError("n_slots must be positive")
     an = Analyzer(policy_fn, game, n_slots, n_playouts=n_playouts, c_puct=c_puct, use_dirichlet=use_dirichlet, device=device,
-                  eval_backend=eval_backend, eval_precision=eval_precision, seed=seed, check_every=check_every, pv_depth=pv_depth, **kwargs)
+                  eval_backend=eval_backend, eval_precision=eval_precision, seed=seed, check_every=check_every, pv_depth=pv_depth,
+                  eval_mirror=eval_mirror, **kwargs)
     try:
         parts = []
         prog = {k: 0 for k in _PROGRESS_SUMS}

@@ -75,6 +75,7 @@ __device__ __forceinline__ uint64_t lanes_below(int lane) { return lane ? (~0ull
 
 // ------------------------------------------------------------------------------------------------
 // Philox4x32-10 counter RNG: stream = (seed, game id), counter = (ply, purpose, index, draw)
+// Purposes: 0 root noise, 1 move choice, 2 arena opponent, 3 playout cap schedule, 4 / 5 orientation of a leaf / root request
 struct Philox {
     uint32_t k0, k1, c0, c1, c2, c3;
     uint32_t out[4];
@@ -641,6 +642,18 @@ __device__ __forceinline__ bool cap_draw_full(uint64_t seed, int gid, int ply, d
     philox_init(r, seed, (uint32_t)gid, (uint32_t)ply, 3u, 0u);
     return philox_u01(r) < p_full;
 }
+// Evaluation in a random left-right orientation (include/az_engine.h: az_engine_set_eval_mirror) - the coin of one network request:
+// mirrored iff u < p_mirror, u the first uniform of the Philox stream (seed, gid, root ply, purpose, index), whatever rng_mode is.
+// purpose 4 = a leaf request, index = the playouts of the current search completed so far (az_slot_info.sims_done); purpose 5 = the
+// root-expansion request, index 0.  Wave-uniform arguments, the same result in every lane.  The bit of the outstanding request
+// travels in bit 30 of leaf_ply[g], a word step 0 of the tick loads anyway (a ply is below 2^8).
+#define MIRROR_BIT_SHIFT 30
+#define LEAF_PLY_MASK 0x3FFFFFFF
+__device__ __forceinline__ int mirror_coin(const Params &p, int gid, int root_ply, uint32_t purpose, uint32_t idx) {
+    Philox r;
+    philox_init(r, p.seed, (uint32_t)gid, (uint32_t)root_ply, purpose, idx);
+    return philox_u01(r) < p.p_mirror ? 1 : 0;
+}
 // A slot arms the search of game `gid` at absolute ply `ply` (cold paths only: the reset kernel, and move_step after a move or with
 // a new game): the playout counter starts at 0, or - a fast move under a playout cap - at S - n_fast, the value returned.  The
 // kind is read from the generation's schedule, which az_cap_schedule_kernel draws at reset (cap_draw_full for every game id and
@@ -755,7 +768,8 @@ __device__ __forceinline__ uint32_t prune_forced_visits(const Params &p, uint32_
 // overlap the playout loop's (it used to be a kernel of its own: one more launch gap and ~11 us of serial latency
 // per tick; now moving slots run beside the other slots' playouts).
 // FORCED (az_engine_set_forced_playouts with prune = 1 reaches here): the recorded child visits of a full search are the pruned ones.
-template <int GAME, bool FORCED>
+// MIRROR (az_engine_set_eval_mirror): the root request draws its coin here and, mirrored, shows the network az_mirror_state(root).
+template <int GAME, bool FORCED, bool MIRROR>
 __device__ __forceinline__ void move_step(const Params &p, const int g, const int lane, int ph, SlotRegs sr,
                                           float *__restrict__ obs_row, const int row) { // obs_row: row `row` of the request buffer, this slot's
     const AzGeom &geom = p.geom;
@@ -963,7 +977,13 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
             if (mine > 1) p.eta_buf[(size_t)g * p.maxc + k[1]] = e1 / sum;
             if (mine > 2) p.eta_buf[(size_t)g * p.maxc + k[2]] = e2 / sum;
         }
-        write_obs<GAME>(p, sr.rs, obs_row, lane);
+        if constexpr (MIRROR) { // the request's orientation: stream (seed, game id, root ply, purpose 5, index 0)
+            const int mir = rfl(mirror_coin(p, sr.gid, sr.rs.ply, 5u, 0u));
+            if (lane == 0) p.leaf_ply[g] = mir << MIRROR_BIT_SHIFT; // (the word carries no leaf while the slot waits for its root)
+            write_obs<GAME>(p, mir ? az_mirror_state<GAME>(sr.rs, geom) : sr.rs, obs_row, lane);
+        } else {
+            write_obs<GAME>(p, sr.rs, obs_row, lane);
+        }
         st_evals++;
         ph = PH_WAIT_ROOT;
     }
@@ -996,7 +1016,11 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
 // FORCED = true (picked at launch when az_engine_set_forced_playouts is in force; plain PUCT self-play engines only): a root child
 // with n > 0 visits and n * n < k * P * N is selected before any other in a full search (forced playouts), and move_step may
 // prune the recorded counts.  FORCED = false compiles to the kernel without the feature.
-template <int GAME, int NP, bool MAPPED, bool FORCED>
+// MIRROR = true (picked at launch when az_engine_set_eval_mirror is in force): every request draws a coin where it is written - the
+// path that ends the wave's tick - and a mirrored one writes the observation of az_mirror_state(leaf); its bit rides in bit 30 of
+// leaf_ply[g], so step 0 still loads everything in one round trip, and the answer's prior of action a is read at
+// az_mirror_action(a).  MIRROR = false compiles to the kernel without the feature.
+template <int GAME, int NP, bool MAPPED, bool FORCED, bool MIRROR>
 __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_first, const int g_end, const float *__restrict__ priors,
                                                   const float *__restrict__ values, float *__restrict__ obs_out) {
     const int lane = threadIdx.x & 63;
@@ -1023,7 +1047,7 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
         // the agent's move / the opponent's move / the next search's root request / a stream's stalled slot asking for a game id
         // again: ends this slot's tick
         if (MAPPED && lane == 0) p.req_row[g] = row;
-        move_step<GAME, FORCED>(p, g, lane, ph, sr, obs_row, row);
+        move_step<GAME, FORCED, MIRROR>(p, g, lane, ph, sr, obs_row, row);
         return;
     }
     if (ph != PH_RUN && ph != PH_WAIT_LEAF && ph != PH_WAIT_ROOT) return;
@@ -1056,10 +1080,12 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
         int depth = 0;
         bool fresh;
         uint32_t c0;
+        // the orientation the outstanding request (leaf or root) was shown in
+        [[maybe_unused]] const int mir_ans = MIRROR ? (rfl(lf_ply_raw) >> MIRROR_BIT_SHIFT) & 1 : 0;
         if (ph == PH_WAIT_LEAF) {
             ls.bb0 = rfl64(lf_bb0_raw);
             ls.bb1 = rfl64(lf_bb1_raw);
-            ls.ply = rfl(lf_ply_raw);
+            ls.ply = MIRROR ? (rfl(lf_ply_raw) & LEAF_PLY_MASK) : rfl(lf_ply_raw);
             node = rflu(lf_node_raw);
             const int dm = rfl(lf_depth_raw); // depth | action leading to the leaf << 16
             depth = dm & 0xFFFF;
@@ -1103,7 +1129,10 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
         float pf[3] = {0.f, 0.f, 0.f}; // all the lane's priors first: independent loads, one round trip
 #pragma unroll
         for (int j = 0; j < MAXM; j++)
-            if (j < mine) pf[j] = pri[act[j]];
+            if (j < mine) {
+                if constexpr (MIRROR) pf[j] = pri[mir_ans ? az_mirror_action<GAME>(act[j], geom) : act[j]];
+                else pf[j] = pri[act[j]];
+            }
 #pragma unroll
         for (int j = 0; j < MAXM; j++)
             if (j < mine) {
@@ -1261,13 +1290,20 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
             continue;
         }
         // non-terminal leaf: ask the network (mcts.py:146)
-        write_obs<GAME>(p, s, obs_row, lane);
+        [[maybe_unused]] int mir = 0;
+        if constexpr (MIRROR) { // the request's orientation: stream (seed, game id, ROOT ply, purpose 4, index = sims_done as read back)
+            const int base = p.capdev ? rfl(p.capdev->sims_base[g]) : 0; // (a fast search's counter starts above 0: arm_search)
+            mir = rfl(mirror_coin(p, sr.gid, sr.rs.ply, 4u, (uint32_t)(sr.sims - base)));
+            write_obs<GAME>(p, mir ? az_mirror_state<GAME>(s, geom) : s, obs_row, lane);
+        } else {
+            write_obs<GAME>(p, s, obs_row, lane);
+        }
         st_evals++;
         if (lane == 0) {
             if (MAPPED) p.req_row[g] = row;
             p.leaf_bb0[g] = s.bb0;
             p.leaf_bb1[g] = s.bb1;
-            p.leaf_ply[g] = s.ply;
+            p.leaf_ply[g] = MIRROR ? (s.ply | (mir << MIRROR_BIT_SHIFT)) : s.ply;
             p.leaf_node[g] = node;
             p.depth[g] = depth | (int)((meta & 0xFFFFu) << 16); // + the action leading to the leaf (its META low half)
         }
@@ -1292,7 +1328,7 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
     }
 }
 
-template <int GAME, int NP, bool MAPPED, bool FORCED>
+template <int GAME, int NP, bool MAPPED, bool FORCED, bool MIRROR>
 __global__ __launch_bounds__(256) void az_advance_kernel(Params p, const int g_first, const int g_end, const float *__restrict__ priors,
                                                          const float *__restrict__ values, float *__restrict__ obs_out) {
     const int n_slot_wgs = (g_end - g_first + 3) >> 2;
@@ -1301,7 +1337,7 @@ __global__ __launch_bounds__(256) void az_advance_kernel(Params p, const int g_f
         return;
     }
     const int epoch = p.defer_compact ? p.cjob_count[0] : 0; // (the same in every wave of the launch: compact_jobs)
-    advance_slot_wave<GAME, NP, MAPPED, FORCED>(p, g_first, g_end, priors, values, obs_out);
+    advance_slot_wave<GAME, NP, MAPPED, FORCED, MIRROR>(p, g_first, g_end, priors, values, obs_out);
     // every slot wave reports itself seen, whichever way it left: its extra workgroup stays until none of its rows can hand over a job
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (p.defer_compact && (threadIdx.x & 63) == 0 && g_first + row < g_end)
@@ -2110,6 +2146,42 @@ extern "C" int az_engine_set_forced_playouts(az_engine *e, double k, int32_t pru
     return AZ_OK;
 }
 
+// ---- evaluation in a random left-right orientation (include/az_engine.h: az_engine_set_eval_mirror) ----------------------------
+extern "C" int az_engine_set_eval_mirror(az_engine *e, double p_mirror) {
+    if (!e) return AZ_E_INVALID;
+    if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) {
+        e->err = "az_engine_set_eval_mirror is for self-play and manual_moves engines: refused for an arena engine (an evaluation game "
+                 "measures the network as it is, in the one orientation its opponent's games are played in)";
+        return AZ_E_INVALID;
+    }
+    if (!(p_mirror >= 0.0 && p_mirror <= 1.0)) { // (the negated form takes NaN too)
+        e->err = "az_engine_set_eval_mirror: p_mirror must be finite and in [0, 1] (0 clears the setting)";
+        return AZ_E_INVALID;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, hipDeviceSynchronize()); // a generation that still plays was launched under the old setting
+    e->p.p_mirror = p_mirror;
+    e->reset_done = false; // the caller starts a generation next (az_engine_reset / az_engine_stream_begin)
+    return AZ_OK;
+}
+
+// The tick kernel's instantiation for the settings in force (az_engine_set_forced_playouts, az_engine_set_eval_mirror: each its
+// own instantiations; with neither set the engine launches the kernel without either feature).
+template <int GAME, int NP, bool MAPPED>
+static void launch_tick(az_engine *e, dim3 grid, dim3 block, hipStream_t st, int g_first, int g_end, const float *priors,
+                        const float *values, float *obs_out) {
+    const bool forced = e->p.forced_k > 0.0, mirror = e->p.p_mirror > 0.0;
+#define AZ_TICK(F, M) hipLaunchKernelGGL((az_advance_kernel<GAME, NP, MAPPED, F, M>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out)
+    if (mirror) {
+        if (forced) AZ_TICK(true, true);
+        else AZ_TICK(false, true);
+    } else {
+        if (forced) AZ_TICK(true, false);
+        else AZ_TICK(false, false);
+    }
+#undef AZ_TICK
+}
+
 // `defer`: compactions of this launch are handed to its own extra workgroups (compact_jobs; whole-engine launches only: the job
 // list and its counters are one set per engine, and slot groups ticking on their own streams would share them).
 template <bool MAPPED>
@@ -2120,14 +2192,8 @@ static int advance_range(az_engine *e, int g_first, int g_end, const float *prio
     defer = defer && e->may_compact;
     dim3 grid((g_end - g_first + 3) / 4 + (defer ? AZ_COMPACT_WGS : 0)), block(256);
     e->p.defer_compact = defer ? 1 : 0;
-    const bool forced = e->p.forced_k > 0.0; // (az_engine_set_forced_playouts: its own instantiations, the others stay as they are)
-    if (e->cfg.game == AZ_GAME_CONNECT_FOUR) {
-        if (forced) hipLaunchKernelGGL((az_advance_kernel<AZG_CONNECT_FOUR, 1, MAPPED, true>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out);
-        else hipLaunchKernelGGL((az_advance_kernel<AZG_CONNECT_FOUR, 1, MAPPED, false>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out);
-    } else {
-        if (forced) hipLaunchKernelGGL((az_advance_kernel<AZG_BREAKTHROUGH, 3, MAPPED, true>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out);
-        else hipLaunchKernelGGL((az_advance_kernel<AZG_BREAKTHROUGH, 3, MAPPED, false>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out);
-    }
+    if (e->cfg.game == AZ_GAME_CONNECT_FOUR) launch_tick<AZG_CONNECT_FOUR, 1, MAPPED>(e, grid, block, st, g_first, g_end, priors, values, obs_out);
+    else launch_tick<AZG_BREAKTHROUGH, 3, MAPPED>(e, grid, block, st, g_first, g_end, priors, values, obs_out);
     e->p.defer_compact = 0;
     HIPCHK(e, hipGetLastError());
     return AZ_OK;
@@ -2717,6 +2783,7 @@ extern "C" int az_engine_read_slot(az_engine *e, int32_t slot, az_slot_info *o) 
     RD(o->leaf_bb[0], e->p.leaf_bb0); RD(o->leaf_bb[1], e->p.leaf_bb1); RD(o->leaf_ply, e->p.leaf_ply);
     RD(o->depth, e->p.depth);
     o->depth &= 0xFFFF; // (the high half carries the action that leads to the requested leaf)
+    o->leaf_ply &= LEAF_PLY_MASK; // (bit 30 carries the orientation of the outstanding request: az_engine_read_request_mirror)
     if (e->p.capdev) { // a fast move's counter starts above 0 under a playout cap: sims_done counts the current search from 0
         int32_t base = 0;
         RD(base, e->cap.sims_base);
@@ -2724,6 +2791,29 @@ extern "C" int az_engine_read_slot(az_engine *e, int32_t slot, az_slot_info *o) 
     }
 #undef RD
     return AZ_OK;
+}
+
+extern "C" int az_engine_read_request_mirror(az_engine *e, int32_t slot) {
+    if (!e) return AZ_E_INVALID;
+    if (slot < 0 || slot >= e->p.G) {
+        e->err = "az_engine_read_request_mirror: slot " + std::to_string(slot) + " is outside [0, n_slots = " + std::to_string(e->p.G) + ")";
+        return AZ_E_INVALID;
+    }
+    if (!e->reset_done) {
+        e->err = "az_engine_read_request_mirror before az_engine_reset";
+        return AZ_E_STATE;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, hipDeviceSynchronize());
+    int ph = PH_IDLE, word = 0;
+    HIPCHK(e, hipMemcpy(&ph, e->p.phase + slot, sizeof ph, hipMemcpyDeviceToHost));
+    if (ph != PH_WAIT_ROOT && ph != PH_WAIT_LEAF) {
+        e->err = "az_engine_read_request_mirror: the slot has no request outstanding (phase " + std::to_string(ph) + ", not 3 or 4)";
+        return AZ_E_STATE;
+    }
+    if (!(e->p.p_mirror > 0.0)) return 0; // no setting in force: every request is shown as it is
+    HIPCHK(e, hipMemcpy(&word, e->p.leaf_ply + slot, sizeof word, hipMemcpyDeviceToHost));
+    return (word >> MIRROR_BIT_SHIFT) & 1;
 }
 
 extern "C" int az_engine_read_root_noise(az_engine *e, int32_t slot, double *eta_out) {

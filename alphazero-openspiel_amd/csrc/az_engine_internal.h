@@ -137,8 +137,11 @@ struct Params {
     // forced playouts and policy target pruning (az_engine_set_forced_playouts): k = 0 = none.  Read by the FORCED instantiations
     // of az_advance_kernel only, which the host launches while forced_k > 0; the others never touch the two fields.
     double forced_k;
+    // evaluation in a random left-right orientation (az_engine_set_eval_mirror): 0 = none.  Read by the MIRROR instantiations of
+    // az_advance_kernel only, which the host launches while p_mirror > 0; appended, so no other field moves.
+    double p_mirror;
 };
-static_assert(sizeof(Params) == 952, "Params is passed by value to every kernel and baked into captured graphs: its layout does not move");
+static_assert(sizeof(Params) == 960, "Params is passed by value to every kernel and baked into captured graphs: its layout does not move");
 
 // The engine's own record arrays as a view (az_records.h); the tick kernel keeps reading p.rec_* itself.
 static inline AzRecords records_of(const Params &p) {

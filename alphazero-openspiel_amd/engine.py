@@ -91,6 +91,7 @@ class SelfPlayEngine:
         self._starts()
         self.playout_cap = None      # set_playout_cap: (n_fast, p_full) while a cap is in force
         self.forced_playouts = None  # set_forced_playouts: (k, prune) while the setting is in force
+        self.eval_mirror = None      # set_eval_mirror: p_mirror while the setting is in force
         self.n_games = 0
 
     # ------------------------------------------------------------------ plumbing
@@ -221,6 +222,20 @@ class SelfPlayEngine:
         the reason otherwise).  k = 0 clears the setting.  reset() or stream_begin() afterwards."""
         self._check(self.lib.az_engine_set_forced_playouts(self._h, float(k), int(prune)))
         self.forced_playouts = (float(k), bool(prune)) if float(k) > 0.0 else None
+
+    def set_eval_mirror(self, p):
+        """Evaluation in a random left-right orientation (az_engine_set_eval_mirror): from the next reset() / stream_begin() on,
+        every network request of a search is shown to the network mirrored with probability p and its priors are mapped back
+        (the value is used as it is).  The coin is a Philox draw keyed by (seed, game id, root ply, request), so a game still
+        depends on (seed, game id, network) alone; the records do not change shape.  Self-play and manual_moves engines
+        (EngineError names the reason for an arena engine).  p = 0 clears the setting.  reset() or stream_begin() afterwards."""
+        self._check(self.lib.az_engine_set_eval_mirror(self._h, float(p)))
+        self.eval_mirror = float(p) if float(p) > 0.0 else None
+
+    def read_request_mirror(self, slot):
+        """The orientation bit of the slot's outstanding request (az_engine_read_request_mirror): 1 = the observation in the
+        request buffer is the mirrored position's; 0 with no setting in force.  EngineError unless the slot is in phase 3 or 4."""
+        return int(self._check(self.lib.az_engine_read_request_mirror(self._h, int(slot))))
 
     def full_moves_device(self, n_games=None):
         """-> uint8 device tensor [n, max_plies] by absolute ply: 1 where a recorded ply was searched in full, 0 elsewhere (a
@@ -814,14 +829,19 @@ class SelfPlayStream:
     would have played).
 
     forced_playouts=k or (k, prune): SelfPlayEngine.set_forced_playouts before the stream begins (an engine that already carries
-    the setting streams with it as well: the pruned counts travel in the records themselves)."""
+    the setting streams with it as well: the pruned counts travel in the records themselves).
+    eval_mirror=p: SelfPlayEngine.set_eval_mirror before the stream begins (an engine that already carries the setting streams
+    with it as well)."""
 
-    def __init__(self, engine, evaluator, seed=None, use_graph=True, ticks_per_graph=16, check_every=32, forced_playouts=None):
+    def __init__(self, engine, evaluator, seed=None, use_graph=True, ticks_per_graph=16, check_every=32, forced_playouts=None,
+                 eval_mirror=None):
         self.engine, self.evaluator = engine, evaluator
         self.use_graph, self.check_every = bool(use_graph), max(1, int(check_every))
         self.ticks_per_graph = min(max(1, int(ticks_per_graph)), self.check_every)
         if forced_playouts is not None:
             engine.set_forced_playouts(*(forced_playouts if isinstance(forced_playouts, (tuple, list)) else (forced_playouts,)))
+        if eval_mirror is not None:
+            engine.set_eval_mirror(eval_mirror)
         engine.stream_begin(seed)
         self.obs, self.pri, self.val = engine.alloc_io()
         self.taken = 0          # games handed over so far = the id of the next one

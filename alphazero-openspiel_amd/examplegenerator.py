@@ -123,18 +123,37 @@ class ExampleGenerator:
                 raise ValueError("forced_playouts is not supported with use_puct=False: the rules are stated for the PUCT value")
             self.forced_playouts = (k, bool(prune)) if k > 0.0 else None
 
+        # eval_mirror=p: every network request of a search is evaluated left-right mirrored with probability p and its answer
+        # mapped back (SelfPlayEngine.set_eval_mirror).  An engine setting keyed by (seed, game id) that leaves the records as
+        # they are: it goes to EVERY engine this generator builds (pools, ranks, overlap, the stream of continuous=True).
+        self.eval_mirror = kwargs.get("eval_mirror")
+        if self.eval_mirror is not None:
+            try:
+                p = float(self.eval_mirror)
+            except (TypeError, ValueError):
+                raise ValueError("eval_mirror must be a probability in [0, 1], got %r" % (self.eval_mirror,))
+            if not 0.0 <= p <= 1.0:  # (NaN fails both comparisons)
+                raise ValueError("eval_mirror must be a probability in [0, 1], got %r" % (self.eval_mirror,))
+            if self.is_test:
+                raise ValueError("eval_mirror is a self-play setting: it is not supported with is_test=True (evaluation games show "
+                                 "the network every position as it is)")
+            self.eval_mirror = p if p > 0.0 else None
+
     def _engine_kwargs(self):
         return {k: self.kwargs[k] for k in _ENGINE_KW if k in self.kwargs}
 
     def _new_engine(self, n_slots, **kw):
-        """A self-play engine with this generator's search settings (forced_playouts among them; reset() comes after)."""
+        """A self-play engine with this generator's search settings (forced_playouts and eval_mirror among them; reset() comes
+        after)."""
         engine = SelfPlayEngine(self.game, n_slots, **kw, **self._engine_kwargs())
-        if self.forced_playouts is not None:
-            try:
+        try:
+            if self.forced_playouts is not None:
                 engine.set_forced_playouts(*self.forced_playouts)
-            except Exception:
-                close_all(engine)
-                raise
+            if self.eval_mirror is not None:
+                engine.set_eval_mirror(self.eval_mirror)
+        except Exception:
+            close_all(engine)
+            raise
         return engine
 
     def _pool_device_list(self):

@@ -56,9 +56,15 @@ def main():
     ap.add_argument("--forced-playouts", type=float, default=0.0, metavar="K",
                     help="forced playouts at the root and policy target pruning (KataGo, section 3.2) in every full search: a tried "
                          "root child gets at least sqrt(K P N) visits, and the visits it did not earn leave the recorded pi (e.g. 2)")
+    ap.add_argument("--eval-mirror", type=float, default=0.0, metavar="P",
+                    help="evaluate every network request of a search (self-play, and the searches of --reanalyse) left-right mirrored "
+                         "with probability P and map the answer back, as AlphaGo Zero and KataGo do: a left/right bias of the net "
+                         "averages out of the visit counts instead of being trained back in (e.g. 0.5)")
     a = ap.parse_args()
     if not 0.0 <= a.forced_playouts < float("inf"):
         ap.error("--forced-playouts takes a finite K >= 0")
+    if not 0.0 <= a.eval_mirror <= 1.0:
+        ap.error("--eval-mirror takes a probability in [0, 1]")
     cap = None
     if a.playout_cap:
         if a.continuous:
@@ -79,7 +85,7 @@ def main():
     if a.continuous:
         generator = ExampleGenerator(net, a.game, dev, continuous=True, n_slots=min(a.games, 4096), n_playouts=a.playouts,
                                      backup=a.backup, eval_precision=a.precision, seed=1,
-                                     forced_playouts=a.forced_playouts or None)
+                                     forced_playouts=a.forced_playouts or None, eval_mirror=a.eval_mirror or None)
     for gen in range(1, a.generations + 1):
         t0 = time.perf_counter()
         net.eval()
@@ -94,6 +100,8 @@ def main():
                                    device=dev, seed=gen)
             if a.forced_playouts:
                 eng.set_forced_playouts(a.forced_playouts)                 # the records then hold the pruned counts
+            if a.eval_mirror:
+                eng.set_eval_mirror(a.eval_mirror)
             if cap is not None:
                 eng.set_playout_cap(*cap)                                  # append_engine below keeps the full-search moves only
             prog = E.run_selfplay(eng, FusedNet(net, dev, max_boards=eng.G, precision=a.precision), a.games, use_graph=True)
@@ -121,7 +129,7 @@ def main():
             if reanalyser is None:
                 reanalyser = replay.Reanalyser(store, net, min(a.reanalyse, 4096), a.playouts,
                                                value_target=a.backup if a.backup in ("soft-Z", "A0C", "off-policy") else None,
-                                               eval_precision=a.precision)
+                                               eval_precision=a.precision, eval_mirror=a.eval_mirror or None)
             else:
                 reanalyser.set_evaluator(net)
             n_re = reanalyser.reanalyse(n=a.reanalyse, seed=gen)

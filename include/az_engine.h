@@ -328,6 +328,40 @@ int az_engine_full_moves_device(az_engine *e, uint8_t *full_out_dev, int64_t n_g
 int az_engine_set_forced_playouts(az_engine *e, double k, int32_t prune);
 
 /*
+ * Evaluation in a random left-right orientation (AlphaGo Zero: Silver et al. 2017, "Methods"; KataGo): both games are symmetric
+ * under the mirror column c <-> cols-1-c, so every network request may be shown to the network mirrored and its answer mapped back.
+ * A left/right bias of the net then averages out over a search instead of being written into every visit count.  It costs no
+ * extra evaluation, launch or memory.  The reference has no counterpart; with nothing set every kernel computes what it computed
+ * before, bit for bit.
+ *
+ * az_engine_set_eval_mirror: self-play engines (closed generations and stream mode) and manual_moves engines (analysis, reanalyse);
+ *   an arena engine (arena_agent != AZ_ARENA_SELF_PLAY) returns AZ_E_INVALID and az_last_error names the reason.  p_mirror finite
+ *   and in [0, 1]; p_mirror == 0 clears the setting.  Call it before az_engine_reset or az_engine_stream_begin (the next call the
+ *   engine accepts): it holds for every later generation, and composes with a start prefix, both start tables, a playout cap,
+ *   forced playouts, both rng_modes, keep_search_tree, az_engine_advance_slots on several streams and the dense rows of
+ *   az_engine_advance_rows.  Nothing travels beside the packed export: records, pools, ranks and the replay store do not change.
+ * The coin: every request a slot issues is mirrored iff u < p_mirror, u the first philox_u01 of a Philox stream - from Philox
+ *   whatever rng_mode is, as the cap schedule, so a game still depends on (seed, game id, network) alone, whichever slot, slot
+ *   group, stream, pool or rank plays it:
+ *     leaf request (az_slot_info.phase == 4)            (seed, game id, absolute ply of the slot's ROOT, purpose 4, index = the
+ *                                                        sims_done az_slot_info reports for the waiting slot)
+ *     root-expansion request (az_slot_info.phase == 3)  (seed, game id, root ply, purpose 5, index 0)
+ *   (Purposes 0, 1, 2, 3: root noise, move choice, arena opponent, playout cap.)  A search re-armed with AZ_ACTION_SEARCH_AGAIN
+ *   counts from 0 at the same root, so it draws the same coins again.
+ * A mirrored request: the observation written to obs_out is that of az_mirror_state(state) (csrc/az_games.h: the W-flip of the
+ *   plain observation); when the answer is consumed, action a takes priors[row][az_mirror_action(a)]; the value is used as it is.
+ *   az_slot_info.leaf_bb keeps the unmirrored state; the NaN check and AZ_FAULT_BAD_PRIOR behave as before.
+ *
+ * az_engine_read_request_mirror: the parity read-back - the bit (0 or 1) of the slot's outstanding request; 0 with no setting in
+ *   force.  AZ_E_STATE when the slot is not in phase 3 or 4 (or before az_engine_reset), AZ_E_INVALID for a bad slot.  Host code
+ *   only: no kernel runs.  Synchronises the device as az_engine_read_slot.
+ *
+ * Limits: one orientation per request, not the average of both (two evaluations per request: another feature); no arena engines.
+ */
+int az_engine_set_eval_mirror(az_engine *e, double p_mirror);
+int az_engine_read_request_mirror(az_engine *e, int32_t slot);
+
+/*
  * One tick = MCTS.playout's select + expand + backup (mcts.py:126-153) for all slots, fused with the
  * agent's move step when a slot has finished its S playouts (alphazerobot.py:71-93,
  * game_utils.py:156-197, mcts.py:155-162,192-203) and the root Dirichlet expansion (mcts.py:182-190):
