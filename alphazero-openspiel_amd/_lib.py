@@ -13,6 +13,7 @@ RNG_PHILOX, RNG_INJECTED = 0, 1
 FAULTS = {1: "POOL_EXHAUSTED", 2: "PLY_OVERFLOW", 4: "NO_VISITS", 8: "BAD_PRIOR", 16: "ILLEGAL_ACTION", 32: "VISIT_RANGE"}
 SELECT_PUCT, SELECT_UCT = 0, 1
 ACTION_NONE, ACTION_SEARCH_AGAIN = -1, -2
+PROOF_UNKNOWN, PROOF_WIN, PROOF_DRAW, PROOF_LOSS = 0, 1, 2, 3  # az_engine_set_solver: seen by the player who moved into the node
 ARENA_AGENTS = {None: 0, "zero": 1, "net": 2}
 OPPONENTS = {None: 0, "random": 1, "uct": 2, "external": 3}
 REPLAY_FAULTS = {1: "KEY_COLLISION", 2: "BAD_INDEX", 4: "ROOT_MISMATCH"}
@@ -115,6 +116,10 @@ PROTOTYPES = [
     ("az_engine_set_forced_playouts", C.c_int, [_vp, C.c_double, C.c_int32]),
     ("az_engine_set_eval_mirror", C.c_int, [_vp, C.c_double]),
     ("az_engine_read_request_mirror", C.c_int, [_vp, C.c_int32]),
+    ("az_engine_set_solver", C.c_int, [_vp, C.c_int32]),
+    ("az_engine_read_proofs", C.c_int64, [_vp, C.c_int32, C.POINTER(C.c_int8), C.c_int64]),
+    ("az_engine_proofs_device_bytes", C.c_int64, [_vp]),
+    ("az_engine_export_proofs_device", C.c_int, [_vp, _vp, C.c_int64, _vp]),
     ("az_engine_advance", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     ("az_engine_advance_slots", C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     ("az_engine_compact_rows", C.c_int, [_vp, C.POINTER(C.c_int32), _vp]),

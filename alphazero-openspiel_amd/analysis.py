@@ -78,10 +78,14 @@ class Analyzer:
     policy_fn: the network (an nn.Module or its bound .predict), or an evaluator object (FusedNet, DeviceEvaluator,
     HostPolicyEvaluator); None = set `.evaluator` (any callable(obs, priors_out, values_out)) before the first search.
     eval_mirror=p: every request of every search is evaluated left-right mirrored with probability p and mapped back
-    (SelfPlayEngine.set_eval_mirror; the coin is keyed by seed, position index, ply and request)."""
+    (SelfPlayEngine.set_eval_mirror; the coin is keyed by seed, position index, ply and request).
+    solver=True: MCTS-Solver (SelfPlayEngine.set_solver) - a search ends as soon as its root is proven, and results() gains
+    solved [n] (object array: +1 / 0 / -1 for the side to move, None while unknown) and solved_children [n, A] int8 (the same
+    for the side to move after each move; -128 where unknown or no child)."""
 
     def __init__(self, policy_fn, game_name, n_slots, n_playouts=100, c_puct=2.5, use_dirichlet=False, device=None,
-                 eval_backend="fused", eval_precision="f32x", seed=None, check_every=16, pv_depth=0, eval_mirror=None, **kwargs):
+                 eval_backend="fused", eval_precision="f32x", seed=None, check_every=16, pv_depth=0, eval_mirror=None, solver=False,
+                 **kwargs):
         if int(n_slots) < 1:
             raise ValueError("n_slots must be positive")
         if int(check_every) < 1:
@@ -100,6 +104,9 @@ class Analyzer:
         try:
             if eval_mirror is not None:
                 self.engine.set_eval_mirror(eval_mirror)
+            self.solver = bool(solver)
+            if self.solver:
+                self.engine.set_solver(True)
             if policy_fn is not None:
                 self.evaluator, self._owns_evaluator = _make_evaluator(policy_fn, self.engine.device, eval_backend,
                                                                        eval_precision, int(n_slots))
@@ -238,7 +245,29 @@ class Analyzer:
             if self.lines is None:
                 self.lines = read_lines(self.engine.export_lines_device(self.pv_depth, self.lines_buf))
             res.update(dense_lines(self.lines, self.n))
+        if self.solver:
+            res.update(dense_proofs(self.engine.export_proofs_device().cpu().numpy(), self.roots, self.n, self.engine.A))
         return res
+
+
+SOLVED_UNKNOWN = -128  # solved_children: no child, or nothing proven
+
+
+def dense_proofs(proofs, roots, n, num_actions):
+    """export_proofs_device() rows [G, 1 + mc] + read_roots() dict -> solved [n] (object: +1 / 0 / -1 for the side to move at the
+    root, None = unknown) and solved_children [n, A] int8 (the value, for the root's side to move, of playing the action;
+    SOLVED_UNKNOWN where unknown).  A status is seen by the player who moved INTO a node: the root's changes sign."""
+    value = np.array([SOLVED_UNKNOWN, 1, 0, -1], dtype=np.int8)  # by status, for the player who moved into the node
+    solved = np.empty(n, dtype=object)
+    for i in range(n):
+        st = int(proofs[i, 0])
+        solved[i] = None if st == 0 else -int(value[st])
+    act = roots["child_action"][:n]
+    live = act >= 0
+    rows = np.broadcast_to(np.arange(n)[:, None], act.shape)[live]
+    ch = np.full((n, num_actions), SOLVED_UNKNOWN, dtype=np.int8)
+    ch[rows, act[live]] = value[proofs[:n, 1:][live]]
+    return {"solved": solved, "solved_children": ch}
 
 
 def dense_lines(lines, n):
@@ -268,7 +297,7 @@ def dense_roots(roots, n, num_actions):
 
 def analyze_positions(policy_fn, game_name, histories, n_playouts=100, c_puct=2.5, use_dirichlet=False, n_slots=None,
                       device=None, eval_backend="fused", eval_precision="f32x", seed=None, check_every=16, pv_depth=0,
-                      eval_mirror=None, **kwargs):
+                      eval_mirror=None, solver=False, **kwargs):
     """Search every given position with n_playouts of PUCT search, all of them side by side on the device.
 
     policy_fn   the network (nn.Module or its bound .predict) or an evaluator object, as elsewhere in the package
@@ -278,6 +307,7 @@ def analyze_positions(policy_fn, game_name, histories, n_playouts=100, c_puct=2.
     pv_depth    D > 0: also return every position's principal variation - pv_actions [n, D] (-1 padded), pv_n, pv_q [n, D],
                 pv_len [n] (the whole greedy line's length) and greedy_value [n] (the off-policy target A0GB at its end)
     eval_mirror p: every request is evaluated left-right mirrored with probability p (SelfPlayEngine.set_eval_mirror)
+    solver      True: MCTS-Solver (SelfPlayEngine.set_solver); the result gains solved [n] and solved_children [n, A] (Analyzer)
     kwargs      further SelfPlayEngine keywords (dirichlet_ratio, use_puct, nodes_per_slot, max_sims_per_tick, ...)
 
     Returns a dict, rows in the order given: visits [n, A] int64, q [n, A], priors [n, A] float64 (zero where there is no
@@ -292,7 +322,7 @@ def analyze_positions(policy_fn, game_name, histories, n_playouts=100, c_puct=2.
         raise ValueError("n_slots must be positive")
     an = Analyzer(policy_fn, game, n_slots, n_playouts=n_playouts, c_puct=c_puct, use_dirichlet=use_dirichlet, device=device,
                   eval_backend=eval_backend, eval_precision=eval_precision, seed=seed, check_every=check_every, pv_depth=pv_depth,
-                  eval_mirror=eval_mirror, **kwargs)
+                  eval_mirror=eval_mirror, solver=solver, **kwargs)
     try:
         parts = []
         prog = {k: 0 for k in _PROGRESS_SUMS}

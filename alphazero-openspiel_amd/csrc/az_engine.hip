@@ -769,7 +769,9 @@ __device__ __forceinline__ uint32_t prune_forced_visits(const Params &p, uint32_
 // per tick; now moving slots run beside the other slots' playouts).
 // FORCED (az_engine_set_forced_playouts with prune = 1 reaches here): the recorded child visits of a full search are the pruned ones.
 // MIRROR (az_engine_set_eval_mirror): the root request draws its coin here and, mirrored, shows the network az_mirror_state(root).
-template <int GAME, bool FORCED, bool MIRROR>
+// SOLVER (az_engine_set_solver): at a proven root the counts are adjusted (rule 6 of include/az_engine.h) BEFORE the move is drawn,
+// and the search-derived value targets are the proven value.
+template <int GAME, bool FORCED, bool MIRROR, bool SOLVER>
 __device__ __forceinline__ void move_step(const Params &p, const int g, const int lane, int ph, SlotRegs sr,
                                           float *__restrict__ obs_row, const int row) { // obs_row: row `row` of the request buffer, this slot's
     const AzGeom &geom = p.geom;
@@ -862,6 +864,13 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
             cq = t.nd[c0 + lane].Q;
             cact = (int)(t.nd[c0 + lane].META & 0xFFFFu);
         }
+        [[maybe_unused]] uint32_t root_st = AZ_PROOF_UNKNOWN;
+        if constexpr (SOLVER) { // a proven root: the player to move has won iff the root is LOSS for the player who moved into it
+            root_st = rflu(t.nd[sr.root].status);
+            const uint32_t cst = lane < nc ? t.nd[c0 + lane].status : AZ_PROOF_UNKNOWN;
+            if (root_st == AZ_PROOF_LOSS && cst != AZ_PROOF_WIN) cn = 0;  // only the winning moves keep their visits
+            if (root_st == AZ_PROOF_DRAW && cst == AZ_PROOF_LOSS) cn = 0; // the losing moves give theirs up
+        }
         long long tot = wave_sum_ll((long long)cn);
         if (nc == 0 || (tot <= 0 && p.arena_agent != AZ_ARENA_NET)) fault |= AZ_FAULT_NO_VISITS;
         if (sr.rs.ply >= p.max_plies || (!p.stream_mode && sr.gid >= p.max_games) || sr.gid < 0) fault |= AZ_FAULT_PLY_OVERFLOW;
@@ -881,6 +890,10 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
             target = wave_max(lane < nc ? (cn > 0 ? cq : -99.0) : -INFINITY);
         } else if (p.backup == AZ_BACKUP_OFF_POLICY) { // A0GB: the value at the end of the most-visited line
             target = greedy_line(t.nd, p.cap, sr.root, lane, p.max_plies - sr.rs.ply + 1, LineValueOnly()).value;
+        }
+        if constexpr (SOLVER) { // the exact value for the player to move
+            if (root_st != AZ_PROOF_UNKNOWN && p.backup != AZ_BACKUP_ON_POLICY)
+                target = root_st == AZ_PROOF_LOSS ? 1.0 : (root_st == AZ_PROOF_WIN ? -1.0 : 0.0);
         }
         // action sampling: visit fractions -> remove_illegal_actions -> temperature -> np.random.choice
         double nv = (lane < nc && tot > 0) ? (double)cn / (double)tot : 0.0; // mcts.py:162
@@ -1020,7 +1033,10 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
 // path that ends the wave's tick - and a mirrored one writes the observation of az_mirror_state(leaf); its bit rides in bit 30 of
 // leaf_ply[g], so step 0 still loads everything in one round trip, and the answer's prior of action a is read at
 // az_mirror_action(a).  MIRROR = false compiles to the kernel without the feature.
-template <int GAME, int NP, bool MAPPED, bool FORCED, bool MIRROR>
+// SOLVER = true (picked at launch when az_engine_set_solver is in force; never together with FORCED): MCTS-Solver, rules 1-5 of
+// include/az_engine.h.  The status word rides in the 16 bytes every select loads anyway; a proof event (rare) walks the path
+// registers upward.  SOLVER = false compiles to the kernel without the feature.
+template <int GAME, int NP, bool MAPPED, bool FORCED, bool MIRROR, bool SOLVER>
 __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_first, const int g_end, const float *__restrict__ priors,
                                                   const float *__restrict__ values, float *__restrict__ obs_out) {
     const int lane = threadIdx.x & 63;
@@ -1047,7 +1063,7 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
         // the agent's move / the opponent's move / the next search's root request / a stream's stalled slot asking for a game id
         // again: ends this slot's tick
         if (MAPPED && lane == 0) p.req_row[g] = row;
-        move_step<GAME, FORCED, MIRROR>(p, g, lane, ph, sr, obs_row, row);
+        move_step<GAME, FORCED, MIRROR, SOLVER>(p, g, lane, ph, sr, obs_row, row);
         return;
     }
     if (ph != PH_RUN && ph != PH_WAIT_LEAF && ph != PH_WAIT_ROOT) return;
@@ -1067,6 +1083,7 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
     // ---- 1. second round trip: the root node, and (request outstanding) the nodes of the recorded path ----------
     const AzNode rootn = t.nd[sr.root]; // same address in every lane
     uint32_t root_n = rflu(rootn.N), root_c0 = rflu(rootn.C0), root_meta = rflu(rootn.META);
+    [[maybe_unused]] uint32_t root_st = SOLVER ? rflu(rootn.status) : 0u;
     if (lane == 0) { // depth 0 of every path
         path.r[0] = sr.root;
         path.pn[0] = rootn.N;
@@ -1188,12 +1205,13 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
     int rc_best = 0;
     uint32_t rc_n = 0, rc_c0 = NONE32, rc_meta = 0;
     double rc_q = 0.0, rc_p = 0.0;
+    [[maybe_unused]] uint32_t rc_st = 0;
     for (;;) {
         if (__ballot(fault != 0)) { // faults are raised per lane: make the exit wave-uniform
             next_phase = PH_IDLE;
             break;
         }
-        if (sr.sims >= p.S) { // the agent's move step (move_step) opens this slot's next tick
+        if (sr.sims >= p.S || (SOLVER && root_st != AZ_PROOF_UNKNOWN)) { // the agent's move step (move_step) opens this slot's next tick
             next_phase = p.manual_moves ? PH_SEARCH_DONE : PH_MOVE;
             break;
         }
@@ -1218,10 +1236,12 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
         int depth = 0, term = 0;
         float ret0 = 0.f;
         int mover = s.ply & 1;
-        while (nc > 0 && !term) {
+        [[maybe_unused]] uint32_t pst = AZ_PROOF_UNKNOWN; // SOLVER: the status of the node the descent stands on
+        while (nc > 0 && !term && !(SOLVER && pst != AZ_PROOF_UNKNOWN)) {
             mover = s.ply & 1;
             double val = -INFINITY, cq = 0.0;
             uint32_t cn = 0, cc0 = NONE32, cmeta = 0;
+            [[maybe_unused]] uint32_t cst = AZ_PROOF_UNKNOWN;
             if (lane < nc) {
                 AzNode c;
                 if (depth == 0 && rc_valid) { // (wave-uniform) a chained playout: the root's children are still in registers
@@ -1230,6 +1250,7 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
                     c.META = rc_meta;
                     c.Q = rc_q;
                     c.P = rc_p;
+                    if constexpr (SOLVER) c.status = rc_st;
                 } else {
                     c = t.nd[c0 + lane]; // the lane's child: two 16-byte loads
                     if (depth == 0) {
@@ -1238,6 +1259,7 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
                         rc_meta = c.META;
                         rc_q = c.Q;
                         rc_p = c.P;
+                        if constexpr (SOLVER) rc_st = c.status;
                     }
                 }
                 cn = c.N;
@@ -1250,6 +1272,12 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
                     val = cn == 0 ? INFINITY : c.Q + (p.c_puct * c.P) * sqrt(p.log_table[np_ < p.log_n ? np_ : 0u] / (double)cn);
                 if constexpr (FORCED) { // a forced playout: the first-maximum ballot below takes the lowest forced child
                     if (depth == 0 && cn > 0 && (double)cn * (double)cn < (forced_k * c.P) * (double)np_) val = INFINITY;
+                }
+                if constexpr (SOLVER) { // a move proven lost for the player choosing is never selected
+                    // (some child stays selectable: an expanded unproven node has an unproven child - rule 2's invariant, kept by
+                    // the propagation below - and the descent enters no proven node, nor the search a proven root)
+                    cst = c.status;
+                    if (cst == AZ_PROOF_LOSS) val = -INFINITY;
                 }
             }
             double mx = wave_max(val);
@@ -1264,14 +1292,49 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
             c0 = (uint32_t)__builtin_amdgcn_readlane((int)cc0, best);
             meta = (uint32_t)__builtin_amdgcn_readlane((int)cmeta, best);
             const double qsel = readlane_d(cq, best);
+            if constexpr (SOLVER) pst = (uint32_t)__builtin_amdgcn_readlane((int)cst, best);
             nc = c0 == NONE32 ? 0 : (int)(meta >> 16);
             term = az_apply<GAME>(s, geom, (int)(meta & 0xFFFFu), &ret0);
             depth++;
             path.set(lane, depth, node, np_, qsel);
         }
-        if (term) { // mcts.py:148-152: leaf_value = -player_return(mover); update_recursive(-leaf_value)
+        if (term || (SOLVER && pst != AZ_PROOF_UNKNOWN)) { // mcts.py:148-152: leaf_value = -player_return(mover); update_recursive(-leaf_value)
             double x = mover == 0 ? (double)ret0 : -(double)ret0;
+            if constexpr (SOLVER) { // a playout stopped at a proven node backs up the proven value (a terminal's is the same number)
+                if (pst != AZ_PROOF_UNKNOWN) x = pst == AZ_PROOF_WIN ? 1.0 : (pst == AZ_PROOF_LOSS ? -1.0 : 0.0);
+            }
             backup_path<NP>(t, path, depth, x, lane);
+            if constexpr (SOLVER) {
+                if (pst == AZ_PROOF_UNKNOWN) { // the terminal node has just become proven: mark it and walk the path upward
+                    uint32_t st = x > 0.0 ? AZ_PROOF_WIN : (x < 0.0 ? AZ_PROOF_LOSS : AZ_PROOF_DRAW);
+                    if (lane == 0) t.nd[node].status = st;
+                    if (depth == 1 && lane == rc_best) rc_st = st;
+                    uint32_t child = node;
+                    for (int d = depth - 1; d >= 0; d--) { // d: depth of the parent of `child` (wave-uniform, from the path registers)
+                        uint32_t par = 0;
+#pragma unroll
+                        for (int i = 0; i < NP; i++)
+                            if ((d >> 6) == i) par = (uint32_t)__builtin_amdgcn_readlane((int)path.r[i], d & 63);
+                        uint32_t pst_new = AZ_PROOF_LOSS; // a WIN child: the parent is lost for the player who moved into it
+                        if (st != AZ_PROOF_WIN) {
+                            const uint4 hd = *(const uint4 *)(t.nd + par); // N, C0, META, status: one 16-byte load
+                            const uint32_t pc0 = rflu(hd.y);
+                            const int pnc = (int)(rflu(hd.z) >> 16);
+                            uint32_t s_c = AZ_PROOF_LOSS; // (lanes beyond the children: neutral for the minimum below)
+                            if (lane < pnc) s_c = pc0 + (uint32_t)lane == child ? st : t.nd[pc0 + lane].status;
+                            if (__ballot(s_c == AZ_PROOF_UNKNOWN)) break; // an unproven child: the parent stays unknown
+                            // every child proven: minus the best child value (codes ascend from WIN to LOSS)
+                            const bool any_win = __ballot(s_c == AZ_PROOF_WIN) != 0, any_draw = __ballot(s_c == AZ_PROOF_DRAW) != 0;
+                            pst_new = any_win ? AZ_PROOF_LOSS : (any_draw ? AZ_PROOF_DRAW : AZ_PROOF_WIN);
+                        }
+                        if (lane == 0) t.nd[par].status = pst_new;
+                        if (d == 1 && lane == rc_best) rc_st = pst_new;
+                        if (d == 0) root_st = pst_new;
+                        child = par;
+                        st = pst_new;
+                    }
+                }
+            }
             { // the backed-up N and Q of the depth-1 node (lane 1 of the path registers) into the cached child record
                 const uint32_t n1 = (uint32_t)__builtin_amdgcn_readlane((int)path.pn[0], 1);
                 const double q1 = readlane_d(path.pq[0], 1);
@@ -1328,7 +1391,7 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
     }
 }
 
-template <int GAME, int NP, bool MAPPED, bool FORCED, bool MIRROR>
+template <int GAME, int NP, bool MAPPED, bool FORCED, bool MIRROR, bool SOLVER>
 __global__ __launch_bounds__(256) void az_advance_kernel(Params p, const int g_first, const int g_end, const float *__restrict__ priors,
                                                          const float *__restrict__ values, float *__restrict__ obs_out) {
     const int n_slot_wgs = (g_end - g_first + 3) >> 2;
@@ -1337,7 +1400,7 @@ __global__ __launch_bounds__(256) void az_advance_kernel(Params p, const int g_f
         return;
     }
     const int epoch = p.defer_compact ? p.cjob_count[0] : 0; // (the same in every wave of the launch: compact_jobs)
-    advance_slot_wave<GAME, NP, MAPPED, FORCED, MIRROR>(p, g_first, g_end, priors, values, obs_out);
+    advance_slot_wave<GAME, NP, MAPPED, FORCED, MIRROR, SOLVER>(p, g_first, g_end, priors, values, obs_out);
     // every slot wave reports itself seen, whichever way it left: its extra workgroup stays until none of its rows can hand over a job
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (p.defer_compact && (threadIdx.x & 63) == 0 && g_first + row < g_end)
@@ -2130,6 +2193,7 @@ extern "C" int az_engine_set_forced_playouts(az_engine *e, double k, int32_t pru
     if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) why = "an arena engine (an evaluation game records no policy target)";
     else if (e->cfg.manual_moves) why = "a manual_moves engine (analysis and reanalyse searches are read raw)";
     else if (e->cfg.select_rule != AZ_SELECT_PUCT) why = "select_rule = AZ_SELECT_UCT (the forcing and pruning rules are stated for the PUCT value)";
+    else if (e->p.solver && k > 0.0) why = "an engine with az_engine_set_solver in force (forced playouts together with the solver are not built)";
     if (why) {
         e->err = std::string("az_engine_set_forced_playouts is for plain PUCT self-play engines: refused for ") + why;
         return AZ_E_INVALID;
@@ -2142,6 +2206,24 @@ extern "C" int az_engine_set_forced_playouts(az_engine *e, double k, int32_t pru
     HIPCHK(e, hipDeviceSynchronize()); // a generation that still plays was launched under the old setting
     e->p.forced_k = k;
     e->p.forced_prune = k > 0.0 ? prune : 0;
+    e->reset_done = false; // the caller starts a generation next (az_engine_reset / az_engine_stream_begin)
+    return AZ_OK;
+}
+
+// ---- MCTS-Solver (include/az_engine.h: az_engine_set_solver) ---------------------------------------------------------------------
+extern "C" int az_engine_set_solver(az_engine *e, int32_t on) {
+    if (!e) return AZ_E_INVALID;
+    const char *why = nullptr;
+    if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) why = "an arena engine (an evaluation game measures the reference's search)";
+    else if (e->cfg.select_rule != AZ_SELECT_PUCT) why = "select_rule = AZ_SELECT_UCT (the solver's select rule is stated for the PUCT value)";
+    else if (on && e->p.forced_k > 0.0) why = "an engine with az_engine_set_forced_playouts in force (forced playouts together with the solver are not built)";
+    if (why) {
+        e->err = std::string("az_engine_set_solver is for PUCT self-play and manual_moves engines: refused for ") + why;
+        return AZ_E_INVALID;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, hipDeviceSynchronize()); // a generation that still plays was launched under the old setting
+    e->p.solver = on ? 1 : 0;
     e->reset_done = false; // the caller starts a generation next (az_engine_reset / az_engine_stream_begin)
     return AZ_OK;
 }
@@ -2165,14 +2247,18 @@ extern "C" int az_engine_set_eval_mirror(az_engine *e, double p_mirror) {
     return AZ_OK;
 }
 
-// The tick kernel's instantiation for the settings in force (az_engine_set_forced_playouts, az_engine_set_eval_mirror: each its
-// own instantiations; with neither set the engine launches the kernel without either feature).
+// The tick kernel's instantiation for the settings in force (az_engine_set_forced_playouts, az_engine_set_eval_mirror,
+// az_engine_set_solver: each its own instantiations; with none set the engine launches the kernel without any of the features).
 template <int GAME, int NP, bool MAPPED>
 static void launch_tick(az_engine *e, dim3 grid, dim3 block, hipStream_t st, int g_first, int g_end, const float *priors,
                         const float *values, float *obs_out) {
     const bool forced = e->p.forced_k > 0.0, mirror = e->p.p_mirror > 0.0;
-#define AZ_TICK(F, M) hipLaunchKernelGGL((az_advance_kernel<GAME, NP, MAPPED, F, M>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out)
-    if (mirror) {
+#define AZ_TICK(F, M) hipLaunchKernelGGL((az_advance_kernel<GAME, NP, MAPPED, F, M, false>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out)
+#define AZ_TICK_SOLVER(M) hipLaunchKernelGGL((az_advance_kernel<GAME, NP, MAPPED, false, M, true>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out)
+    if (e->p.solver) { // (never with forced playouts: the two setters refuse each other)
+        if (mirror) AZ_TICK_SOLVER(true);
+        else AZ_TICK_SOLVER(false);
+    } else if (mirror) {
         if (forced) AZ_TICK(true, true);
         else AZ_TICK(false, true);
     } else {
@@ -2180,6 +2266,7 @@ static void launch_tick(az_engine *e, dim3 grid, dim3 block, hipStream_t st, int
         else AZ_TICK(false, false);
     }
 #undef AZ_TICK
+#undef AZ_TICK_SOLVER
 }
 
 // `defer`: compactions of this launch are handed to its own extra workgroups (compact_jobs; whole-engine launches only: the job
@@ -2663,6 +2750,50 @@ extern "C" int az_engine_export_roots_device(az_engine *e, void *dev_buf, int64_
 }
 
 // ------------------------------------------------------------------------------------------------
+// The proof status of every slot's root and root children (include/az_engine.h: az_engine_export_proofs_device): a wave per slot,
+// 1 + max_children bytes per slot, zeros beyond n_children - the buffer's contents depend on the trees alone.
+__global__ __launch_bounds__(256) void az_export_proofs_kernel(Params p, uint8_t *out) {
+    const int lane = threadIdx.x & 63;
+    const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (g >= p.G) return;
+    const int pool = rfl(p.which[g]) & POOL_MASK;
+    const uint32_t root = rflu(p.root[g]);
+    const AzNode *nd = p.nodes + (size_t)pool * p.cap;
+    uint32_t rst = 0, c0 = NONE32;
+    int nc = 0;
+    if (pool < p.G + p.n_spare && root < p.cap) { // (a slot's own words: never out of the pools)
+        rst = rflu(nd[root].status);
+        c0 = rflu(nd[root].C0);
+        nc = c0 == NONE32 ? 0 : (int)(rflu(nd[root].META) >> 16);
+        if (nc > p.maxc || c0 >= p.cap || c0 + (uint32_t)nc > p.cap) nc = 0;
+    }
+    uint8_t *row = out + (size_t)g * (size_t)(p.maxc + 1);
+    if (lane == 0) row[0] = (uint8_t)rst;
+    for (int i = lane; i < p.maxc; i += 64) row[1 + i] = i < nc ? (uint8_t)nd[c0 + i].status : (uint8_t)0;
+}
+
+extern "C" int64_t az_engine_proofs_device_bytes(const az_engine *e) {
+    if (!e) return AZ_E_INVALID;
+    return (int64_t)e->p.G * (int64_t)(e->p.maxc + 1);
+}
+
+extern "C" int az_engine_export_proofs_device(az_engine *e, void *dev_buf, int64_t bytes, void *stream) {
+    if (!e || !dev_buf) return AZ_E_INVALID;
+    if (bytes < (int64_t)e->p.G * (int64_t)(e->p.maxc + 1)) {
+        e->err = "az_engine_export_proofs_device: buffer smaller than az_engine_proofs_device_bytes()";
+        return AZ_E_INVALID;
+    }
+    if (!e->reset_done) {
+        e->err = "az_engine_export_proofs_device before az_engine_reset";
+        return AZ_E_STATE;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    hipLaunchKernelGGL(az_export_proofs_kernel, dim3((e->p.G + 3) / 4), dim3(256), 0, (hipStream_t)stream, e->p, (uint8_t *)dev_buf);
+    HIPCHK(e, hipGetLastError());
+    return AZ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // The greedy line of every slot's finished search in one buffer (layout: include/az_engine.h, az_engine_export_lines_device).
 // A wave per slot walks its tree with greedy_line, lane 0 records the first D steps as they are met, then the wave clears the
 // rows the line did not reach, so the buffer's contents depend on the trees alone.  The header is written by workgroup 0 from
@@ -2874,8 +3005,9 @@ extern "C" int az_engine_read_root(az_engine *e, int32_t slot, int64_t *root_n, 
     return nc;
 }
 
-extern "C" int64_t az_engine_read_tree(az_engine *e, int32_t slot, int64_t max_nodes, int32_t *parent, int32_t *action,
-                                       int64_t *n, double *q, double *pp) {
+// The walk behind az_engine_read_tree and az_engine_read_proofs: one breadth-first order for both.
+static int64_t read_tree_walk(az_engine *e, int32_t slot, int64_t max_nodes, int32_t *parent, int32_t *action, int64_t *n, double *q,
+                              double *pp, int8_t *proofs) {
     if (!e || slot < 0 || slot >= e->p.G || max_nodes < 0) return AZ_E_INVALID;
     HIPCHK(e, hipSetDevice(e->cfg.device));
     HIPCHK(e, hipDeviceSynchronize());
@@ -2927,6 +3059,16 @@ extern "C" int64_t az_engine_read_tree(az_engine *e, int32_t slot, int64_t max_n
         if (n) n[i] = N[nd];
         if (q) q[i] = Q[nd];
         if (pp) pp[i] = P[nd];
+        if (proofs) proofs[i] = (int8_t)nd_all[nd].status;
     }
     return cnt;
+}
+
+extern "C" int64_t az_engine_read_tree(az_engine *e, int32_t slot, int64_t max_nodes, int32_t *parent, int32_t *action,
+                                       int64_t *n, double *q, double *pp) {
+    return read_tree_walk(e, slot, max_nodes, parent, action, n, q, pp, nullptr);
+}
+
+extern "C" int64_t az_engine_read_proofs(az_engine *e, int32_t slot, int8_t *out, int64_t n) {
+    return read_tree_walk(e, slot, n, nullptr, nullptr, nullptr, nullptr, nullptr, out);
 }

@@ -24,7 +24,8 @@ struct __attribute__((aligned(32))) AzNode {
     uint32_t N;    // visit count
     uint32_t C0;   // index of the first child in the slot's pool half (NONE32 = leaf)
     uint32_t META; // action leading here | n_children << 16
-    uint32_t pad;
+    uint32_t status; // MCTS-Solver proof (AZ_PROOF_*), seen by the player who moved INTO the node like Q; 0 = unknown, and all a
+                     // kernel without the solver ever writes
     double Q, P;
 };
 
@@ -140,8 +141,11 @@ struct Params {
     // evaluation in a random left-right orientation (az_engine_set_eval_mirror): 0 = none.  Read by the MIRROR instantiations of
     // az_advance_kernel only, which the host launches while p_mirror > 0; appended, so no other field moves.
     double p_mirror;
+    // MCTS-Solver (az_engine_set_solver): 0 = off.  Read by the host's launch alone, which picks the SOLVER instantiations of
+    // az_advance_kernel while it is set; appended, so no other field moves.
+    int solver, solver_pad;
 };
-static_assert(sizeof(Params) == 960, "Params is passed by value to every kernel and baked into captured graphs: its layout does not move");
+static_assert(sizeof(Params) == 968, "Params is passed by value to every kernel and baked into captured graphs: its layout does not move");
 
 // The engine's own record arrays as a view (az_records.h); the tick kernel keeps reading p.rec_* itself.
 static inline AzRecords records_of(const Params &p) {

@@ -92,6 +92,7 @@ class SelfPlayEngine:
         self.playout_cap = None      # set_playout_cap: (n_fast, p_full) while a cap is in force
         self.forced_playouts = None  # set_forced_playouts: (k, prune) while the setting is in force
         self.eval_mirror = None      # set_eval_mirror: p_mirror while the setting is in force
+        self.solver = False          # set_solver: True while the setting is in force
         self.n_games = 0
 
     # ------------------------------------------------------------------ plumbing
@@ -231,6 +232,33 @@ class SelfPlayEngine:
         (EngineError names the reason for an arena engine).  p = 0 clears the setting.  reset() or stream_begin() afterwards."""
         self._check(self.lib.az_engine_set_eval_mirror(self._h, float(p)))
         self.eval_mirror = float(p) if float(p) > 0.0 else None
+
+    def set_solver(self, on=True):
+        """MCTS-Solver (az_engine_set_solver): from the next reset() / stream_begin() on, the search proves wins, losses and
+        draws inside its tree - it never selects a move proven lost, stops a playout at a proven node, ends a search whose root
+        is proven, plays a proven win and records exact targets there.  PUCT self-play and manual_moves engines (EngineError
+        names the reason for an arena engine, use_puct=False and an engine with forced playouts).  on=False clears the setting.
+        reset() or stream_begin() afterwards."""
+        self._check(self.lib.az_engine_set_solver(self._h, int(bool(on))))
+        self.solver = bool(on)
+
+    def read_proofs(self, slot):
+        """The proof status of every node of a slot's tree in the order of read_tree() (az_engine_read_proofs) -> int8 array:
+        0 unknown, 1 win, 2 draw, 3 loss for the player who moved into the node.  All 0 without set_solver."""
+        n = self._check(self.lib.az_engine_read_proofs(self._h, int(slot), None, 0))
+        out = np.zeros(n, np.int8)
+        self._check(self.lib.az_engine_read_proofs(self._h, int(slot), out.ctypes.data_as(C.POINTER(C.c_int8)), n))
+        return out
+
+    def export_proofs_device(self, buf=None):
+        """Every slot's root status and root child statuses as a uint8 device tensor [n_slots, 1 + max_children] (column 0 the
+        root, 0 beyond n_children) on the current stream: one kernel, no host synchronisation, may be captured in a graph."""
+        if buf is None:
+            buf = torch.empty((self.G, 1 + self.max_children), dtype=torch.uint8, device=self.device)
+        elif buf.dtype != torch.uint8 or not buf.is_contiguous() or buf.device != self.device:
+            raise EngineError("expected a contiguous uint8 tensor on %s" % (self.device,))
+        self._check(self.lib.az_engine_export_proofs_device(self._h, C.c_void_p(buf.data_ptr()), int(buf.numel()), self._stream()))
+        return buf
 
     def read_request_mirror(self, slot):
         """The orientation bit of the slot's outstanding request (az_engine_read_request_mirror): 1 = the observation in the
@@ -831,10 +859,11 @@ class SelfPlayStream:
     forced_playouts=k or (k, prune): SelfPlayEngine.set_forced_playouts before the stream begins (an engine that already carries
     the setting streams with it as well: the pruned counts travel in the records themselves).
     eval_mirror=p: SelfPlayEngine.set_eval_mirror before the stream begins (an engine that already carries the setting streams
-    with it as well)."""
+    with it as well).
+    solver=True / False: SelfPlayEngine.set_solver before the stream begins (None leaves the engine's setting as it is)."""
 
     def __init__(self, engine, evaluator, seed=None, use_graph=True, ticks_per_graph=16, check_every=32, forced_playouts=None,
-                 eval_mirror=None):
+                 eval_mirror=None, solver=None):
         self.engine, self.evaluator = engine, evaluator
         self.use_graph, self.check_every = bool(use_graph), max(1, int(check_every))
         self.ticks_per_graph = min(max(1, int(ticks_per_graph)), self.check_every)
@@ -842,6 +871,8 @@ class SelfPlayStream:
             engine.set_forced_playouts(*(forced_playouts if isinstance(forced_playouts, (tuple, list)) else (forced_playouts,)))
         if eval_mirror is not None:
             engine.set_eval_mirror(eval_mirror)
+        if solver is not None:
+            engine.set_solver(solver)
         engine.stream_begin(seed)
         self.obs, self.pri, self.val = engine.alloc_io()
         self.taken = 0          # games handed over so far = the id of the next one

@@ -139,6 +139,18 @@ class ExampleGenerator:
                                  "the network every position as it is)")
             self.eval_mirror = p if p > 0.0 else None
 
+        # solver=True: MCTS-Solver (SelfPlayEngine.set_solver) in every search.  The adjusted counts and exact targets sit where
+        # the raw ones sat, so the setting goes to EVERY engine this generator builds, like the two above.
+        self.solver = bool(kwargs.get("solver", False))
+        if self.solver:
+            if self.is_test:
+                raise ValueError("solver is a self-play setting: it is not supported with is_test=True (evaluation games measure the "
+                                 "reference's search)")
+            if not kwargs.get("use_puct", True):
+                raise ValueError("solver is not supported with use_puct=False: its select rule is stated for the PUCT value")
+            if self.forced_playouts is not None:
+                raise ValueError("solver is not supported together with forced_playouts")
+
     def _engine_kwargs(self):
         return {k: self.kwargs[k] for k in _ENGINE_KW if k in self.kwargs}
 
@@ -151,6 +163,8 @@ class ExampleGenerator:
                 engine.set_forced_playouts(*self.forced_playouts)
             if self.eval_mirror is not None:
                 engine.set_eval_mirror(self.eval_mirror)
+            if self.solver:
+                engine.set_solver(True)
         except Exception:
             close_all(engine)
             raise

@@ -276,7 +276,9 @@ class Reanalyser:
     are functions of a search root - or "off-policy" (A0GB, the value at the end of the most-visited line): the chunk's
     greedy lines are then exported too (Analyzer.lines_device, one kernel, depth 1: the value does not depend on it) and the
     refresh goes through refresh_from_search.  Further keywords go to the Analyzer (c_puct, use_dirichlet, eval_precision,
-    eval_mirror=p for searches whose requests are evaluated left-right mirrored with probability p, ...).
+    eval_mirror=p for searches whose requests are evaluated left-right mirrored with probability p, solver=True for MCTS-Solver
+    searches, ...).  With solver=True a search ends as soon as its root is proven and the refresh reads that root as it stands: the
+    raw visit counts and Q of what may be a handful of playouts, not the adjusted counts and exact value self-play records there.
     The store must not change between the calls made here (it is the caller's between reanalyse() calls); the next dedupe()
     averages a refreshed first occurrence with its stale duplicates, as the reference's aliasing does."""
 

@@ -60,9 +60,15 @@ def main():
                     help="evaluate every network request of a search (self-play, and the searches of --reanalyse) left-right mirrored "
                          "with probability P and map the answer back, as AlphaGo Zero and KataGo do: a left/right bias of the net "
                          "averages out of the visit counts instead of being trained back in (e.g. 0.5)")
+    ap.add_argument("--solver", action="store_true",
+                    help="MCTS-Solver: prove wins, losses and draws inside the search tree (self-play, and the searches of "
+                         "--reanalyse): never select a move proven lost, end a search whose root is proven, play a proven win and "
+                         "record exact targets there; not together with --forced-playouts")
     a = ap.parse_args()
     if not 0.0 <= a.forced_playouts < float("inf"):
         ap.error("--forced-playouts takes a finite K >= 0")
+    if a.solver and a.forced_playouts:
+        ap.error("--solver is not available together with --forced-playouts")
     if not 0.0 <= a.eval_mirror <= 1.0:
         ap.error("--eval-mirror takes a probability in [0, 1]")
     cap = None
@@ -85,7 +91,7 @@ def main():
     if a.continuous:
         generator = ExampleGenerator(net, a.game, dev, continuous=True, n_slots=min(a.games, 4096), n_playouts=a.playouts,
                                      backup=a.backup, eval_precision=a.precision, seed=1,
-                                     forced_playouts=a.forced_playouts or None, eval_mirror=a.eval_mirror or None)
+                                     forced_playouts=a.forced_playouts or None, eval_mirror=a.eval_mirror or None, solver=a.solver)
     for gen in range(1, a.generations + 1):
         t0 = time.perf_counter()
         net.eval()
@@ -102,6 +108,8 @@ def main():
                 eng.set_forced_playouts(a.forced_playouts)                 # the records then hold the pruned counts
             if a.eval_mirror:
                 eng.set_eval_mirror(a.eval_mirror)
+            if a.solver:
+                eng.set_solver(True)
             if cap is not None:
                 eng.set_playout_cap(*cap)                                  # append_engine below keeps the full-search moves only
             prog = E.run_selfplay(eng, FusedNet(net, dev, max_boards=eng.G, precision=a.precision), a.games, use_graph=True)
@@ -129,7 +137,7 @@ def main():
             if reanalyser is None:
                 reanalyser = replay.Reanalyser(store, net, min(a.reanalyse, 4096), a.playouts,
                                                value_target=a.backup if a.backup in ("soft-Z", "A0C", "off-policy") else None,
-                                               eval_precision=a.precision, eval_mirror=a.eval_mirror or None)
+                                               eval_precision=a.precision, eval_mirror=a.eval_mirror or None, solver=a.solver)
             else:
                 reanalyser.set_evaluator(net)
             n_re = reanalyser.reanalyse(n=a.reanalyse, seed=gen)

@@ -362,6 +362,57 @@ int az_engine_set_eval_mirror(az_engine *e, double p_mirror);
 int az_engine_read_request_mirror(az_engine *e, int32_t slot);
 
 /*
+ * MCTS-Solver (Winands, Bjornsson, Saito 2008; "certainty propagation"): the search proves wins, losses and draws inside its tree
+ * and acts on them.  The reference scores a terminal node again on every visit (mcts.py:148-152) and knows no proof; with nothing
+ * set every kernel computes what it computed before, bit for bit.
+ *
+ * Status: every node carries a proof status in the word that was padding, seen by the player who moved INTO the node (as its Q):
+ *   AZ_PROOF_UNKNOWN 0, AZ_PROOF_WIN 1 (+1), AZ_PROOF_DRAW 2 (0), AZ_PROOF_LOSS 3 (-1).  A fresh node is 0.
+ * 1. Terminal: a playout whose move ends the game marks that node with player_return(mover) - the value it backs up.
+ * 2. Propagation: right after that backup, from the node that has just become proven upward.  A WIN node makes its parent LOSS;
+ *    otherwise, if every child of the parent is proven, the parent takes minus the best child value (best DRAW -> DRAW, all LOSS
+ *    -> WIN); otherwise the walk stops.  A newly proven parent repeats the step, as far as the root.  An expanded unproven node
+ *    therefore always has an unproven child.
+ * 3. Select, at every depth: a LOSS child's selection value is -infinity (after the PUCT value, before the first-maximum rule).
+ * 4. A playout that selects a proven child stops there: it backs up the proven value as a terminal would, asks for no evaluation,
+ *    counts in terminal_hits and sum_depth, and chains inside a tick under max_sims_per_tick / chain_window_us like a terminal
+ *    hit.  The N and Q arithmetic (mcts.py:82-89) does not change.
+ * 5. A search whose root is proven ends at once (phase 2, or 5 on a manual_moves engine) - also a kept subtree or a root searched
+ *    again that is proven when the search is armed.  az_progress.sims and az_slot_info.sims_done count the playouts that ran.  The
+ *    root request for Dirichlet noise that the start of a search makes is still made.
+ * 6. The move at a proven root (self-play): at a root WON for the player to move (status LOSS: some child is WIN) the counts of
+ *    the children that are not WIN become 0; at a DRAW root those of the LOSS children become 0; at a lost root (every child LOSS)
+ *    the counts stay.  The adjusted counts are written where the raw counts were, and - unlike pruning - the move is drawn from
+ *    them with the same temperature / sampling / argmax arithmetic.  The soft-Z, A0C and off-policy value targets of such a ply are
+ *    the proven value for the player to move, exactly (+1.0, 0.0, -1.0); on-policy targets stay the game's outcome.
+ * 7. Re-rooting, both compaction paths and az_engine_update_root copy whole node records, status included; a re-expansion that
+ *    only rewrites P leaves it alone.
+ *
+ * az_engine_set_solver: on != 0 sets, 0 clears.  Plain PUCT self-play engines (closed generations, stream mode, dense rows) and
+ *   manual_moves engines; both rng_modes (AZ_RNG_INJECTED is allowed: the solver draws nothing).  AZ_E_INVALID, with the reason
+ *   in az_last_error, for an arena engine, select_rule == AZ_SELECT_UCT, and an engine with forced playouts in force - and
+ *   az_engine_set_forced_playouts refuses an engine with the solver set: the combination is not built.  Composes with a playout
+ *   cap, the evaluation mirror, start prefixes and tables, keep_search_tree.  The caller starts a generation next
+ *   (az_engine_reset / az_engine_stream_begin).
+ * az_engine_read_proofs: the status of every node of a slot's tree in the order of az_engine_read_tree (node 0 = the root) ->
+ *   the number of nodes; at most n are written.  Host code only; synchronises the device.  Works with the solver off (all 0).
+ * az_engine_export_proofs_device: per slot 1 + max_children bytes - the root's status, then its children's in child order (0
+ *   beyond n_children) - az_engine_proofs_device_bytes() in all.  One kernel, a wave per slot, asynchronous on `stream` and
+ *   graph-capturable; it sits beside az_engine_export_roots_device, whose layout does not change.
+ *
+ * Limits: win / draw / loss only (no score bounds), no preference for the shortest win or the longest loss, no forced playouts, no
+ *   arena agents, no UCT rule.
+ */
+#define AZ_PROOF_UNKNOWN 0
+#define AZ_PROOF_WIN 1
+#define AZ_PROOF_DRAW 2
+#define AZ_PROOF_LOSS 3
+int az_engine_set_solver(az_engine *e, int32_t on);
+int64_t az_engine_read_proofs(az_engine *e, int32_t slot, int8_t *out, int64_t n);
+int64_t az_engine_proofs_device_bytes(const az_engine *e);
+int az_engine_export_proofs_device(az_engine *e, void *dev_buf, int64_t bytes, void *stream);
+
+/*
  * One tick = MCTS.playout's select + expand + backup (mcts.py:126-153) for all slots, fused with the
  * agent's move step when a slot has finished its S playouts (alphazerobot.py:71-93,
  * game_utils.py:156-197, mcts.py:155-162,192-203) and the root Dirichlet expansion (mcts.py:182-190):
