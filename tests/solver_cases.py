@@ -3,12 +3,16 @@ game_utils.py:148-206, in plain Python with IEEE doubles and the original's asso
 az_engine_set_solver (include/az_engine.h): proof status on the nodes, propagation after a terminal's backup, no selection of a
 child proven lost, a playout that stops at a proven node, a search that ends at a proven root, the move and the targets at a proven
 root, and a status that travels with a kept subtree.  With solver=False it is play_game itself, which tests/test_solver_host.py
-pins against the C oracle.  Also here: a brute-force negamax for small positions, and the shared cases.  No test lives here."""
+pins against the C oracle.  Also here: a brute-force negamax for small positions, the shared cases, and (at the end) the cases of
+tests/test_solver_scale_host.py and tests/test_solver_scale_gpu.py: sequences and games at 400-1600 playouts and deep lines.  No
+test lives here."""
 import math
 
 import numpy as np
 
+import deep_line_cases as DL
 import forced_playouts_cases as FC
+import product_scale_cases as PS
 from oracle import binding as orc
 from oracle import fakepolicy
 
@@ -77,7 +81,7 @@ def propagate(node, path_states, audit):
 
 def play_game(game, salt, etas, us, solver=True, schedule=None, n_playouts=100, c_puct=2.5, temperature=1.0, dirichlet_ratio=0.25,
               use_dirichlet=True, keep_search_tree=True, backup="on-policy", num_probabilistic_actions=1000, start=(), audit=None,
-              trees=None, mirror=None):
+              trees=None, mirror=None, policy=None, max_searches=None, dumps=False):
     """One game of self-play from the position after `start`.  etas[i][j]: the Dirichlet draw of the j-th legal action at the i-th
     ply played, us[i]: the uniform behind that move.  schedule: per ply played (playouts, is_full) - a playout cap.
     audit(state, status, mover): called with a clone of the position of every node that takes a status, the status, and the player
@@ -86,13 +90,21 @@ def play_game(game, salt, etas, us, solver=True, schedule=None, n_playouts=100, 
     mirror: (coin, table) - az_engine_set_eval_mirror: coin(absolute ply of the root, phase of the waiting slot (3: the root request,
     4: a leaf), playouts of this search already run) says whether the request is evaluated left-right mirrored; the net then sees
     the board with its columns reversed and the search reads the prior of action a at table[a].  The value is left alone.
-    -> dict(plies=[dict(raw, recorded, actions, move, pi, value, ran, status)], actions, ret0, counters, effects, mirrored)."""
+    policy: board -> (priors, value) in place of fakepolicy.fake_eval(board, A, salt).
+    max_searches: stop after that many searches (the last move is still chosen and recorded, but not played; ret0 is None then).
+    dumps: every ply also carries tree = tree_dump(root) after its search and kept = the dump of the subtree the re-rooting kept,
+    before it is searched (None at the first ply and where the search starts on a fresh root).
+    -> dict(plies=[dict(raw, recorded, actions, move, pi, value, ran, status, counters (so far), nodes (in the tree after the
+    search), kept_nodes, kept_proven (nodes / proven nodes in the tree the search started on))], actions, ret0, counters, effects,
+    mirrored, events=[(ply played, depth of the terminal node that became proven, levels its proof climbed)])."""
     state = orc.State(game)
     for a in start:
         state.apply_action(a)
     A = int(state.num_actions)
     cnt = dict.fromkeys(COUNTERS, 0)
     eff = dict.fromkeys(EFFECTS, 0)
+    events = []
+    net = policy if policy is not None else (lambda b: fakepolicy.fake_eval(b, A, salt))
 
     cur = {"ply": len(start), "ran": 0}                                # the search under way: its root's absolute ply, playouts run
     mirrored = [0, 0]                                                   # requests evaluated as they are / mirrored
@@ -100,7 +112,7 @@ def play_game(game, salt, etas, us, solver=True, schedule=None, n_playouts=100, 
     def evaluate(s, phase=PH_WAIT_LEAF):
         board = np.asarray(s.board())
         flip = mirror is not None and bool(mirror[0](cur["ply"], phase, cur["ran"] if phase == PH_WAIT_LEAF else 0))
-        pri, val = fakepolicy.fake_eval(board[..., ::-1] if flip else board, A, salt)
+        pri, val = net(board[..., ::-1] if flip else board)
         if flip:
             pri = pri[np.asarray(mirror[1])]
         mirrored[int(flip)] += 1
@@ -133,7 +145,9 @@ def play_game(game, salt, etas, us, solver=True, schedule=None, n_playouts=100, 
                     node.status = status_of(x)
                     if audit is not None:
                         audit(states[-1], node.status, mover)
-                    if propagate(node, states, audit) >= 2:
+                    levels = propagate(node, states, audit)
+                    events.append((len(plies), depth, levels))
+                    if levels >= 2:
                         eff["levels2"] += 1
             cnt["terminal_hits"] += 1
         else:
@@ -158,6 +172,8 @@ def play_game(game, salt, etas, us, solver=True, schedule=None, n_playouts=100, 
         else:
             root = Node(None, 0.0, True)
         legal = state.legal_actions()
+        kept_nodes, kept_proven = tree_size(root)
+        kept = tree_dump(root) if dumps and hist and keep_search_tree else None
         if solver and root.status != UNKNOWN:
             eff["kept_proven_root"] += 1
         cur["ply"], cur["ran"] = len(start) + ply, 0
@@ -185,7 +201,10 @@ def play_game(game, salt, etas, us, solver=True, schedule=None, n_playouts=100, 
                 counts = [0 if c.status == LOSS else n for n, c in zip(raw, root.children)]
             if counts != raw:
                 eff["counts_zeroed"] += 1
-        rec = dict(raw=raw, recorded=counts, actions=list(root.actions), ran=ran, status=root.status, full=bool(full))
+        rec = dict(raw=raw, recorded=counts, actions=list(root.actions), ran=ran, status=root.status, full=bool(full),
+                   counters=dict(cnt), nodes=tree_size(root)[0], kept_nodes=kept_nodes, kept_proven=kept_proven)
+        if dumps:
+            rec["tree"], rec["kept"] = tree_dump(root), kept
         if trees is not None:
             trees.append(root)
 
@@ -221,24 +240,61 @@ def play_game(game, salt, etas, us, solver=True, schedule=None, n_playouts=100, 
             rec["value"] = FC.a0gb_value(root)
         rec["move"] = move
         plies.append(rec)
+        if max_searches is not None and len(plies) >= max_searches:
+            break
         state.apply_action(move)
         hist.append(move)
-    ret0 = state.player_return(0)
-    if backup == "on-policy":                                           # game_utils.py:200-204
+    ret0 = state.player_return(0) if state.is_terminal() else None
+    if backup == "on-policy" and ret0 is not None:                                           # game_utils.py:200-204
         reward = ret0 if len(start) % 2 == 0 else -ret0                 # (seen by the player to move at the first recorded ply)
         for rec in plies:
             rec["value"] = reward
             reward *= -1
-    return {"plies": plies, "actions": hist, "ret0": ret0, "counters": cnt, "effects": eff, "mirrored": mirrored}
+    return {"plies": plies, "actions": hist, "ret0": ret0, "counters": cnt, "effects": eff, "mirrored": mirrored, "events": events}
 
 
-def tree_statuses(root):
-    """The statuses of a tree in the breadth-first order of SelfPlayEngine.read_tree / read_proofs, with the visit counts."""
-    order, i = [root], 0
+def tree_statuses(root, full=False):
+    """The statuses of a tree in the breadth-first order of SelfPlayEngine.read_tree / read_proofs, with the visit counts.
+    full: -> (statuses, counts, parent rows, actions, Q, P) - every column of az_engine_read_tree; the root's row has parent -1
+    and action -1."""
+    order, parent, action, i = [root], [-1], [-1], 0
     while i < len(order):
-        order.extend(order[i].children)
+        n = order[i]
+        order.extend(n.children)
+        parent.extend([i] * len(n.children))
+        action.extend(n.actions)
         i += 1
-    return [n.status for n in order], [n.N for n in order]
+    if not full:
+        return [n.status for n in order], [n.N for n in order]
+    return [n.status for n in order], [n.N for n in order], parent, action, [n.Q for n in order], [n.P for n in order]
+
+
+def tree_dump(root):
+    """tree_statuses(full=True) as the arrays of SelfPlayEngine.read_tree (parent, action, N, Q, P) plus status as read_proofs'."""
+    st, n, parent, action, q, p = tree_statuses(root, full=True)
+    return {"parent": np.asarray(parent, dtype=np.int32), "action": np.asarray(action, dtype=np.int32),
+            "N": np.asarray(n, dtype=np.int64), "Q": np.asarray(q, dtype=np.float64), "P": np.asarray(p, dtype=np.float64),
+            "status": np.asarray(st, dtype=np.int8)}
+
+
+def tree_size(root):
+    """-> (nodes, proven nodes) of a tree."""
+    stack, nodes, proven = [root], 0, 0
+    while stack:
+        n = stack.pop()
+        nodes += 1
+        proven += n.status != UNKNOWN
+        stack.extend(n.children)
+    return nodes, proven
+
+
+def event_stats(events):
+    """What the proof events of a game reach -> dict(events, max_levels, max_depth, cross64, cross128: events whose walk up the
+    path goes from depth 64 (128) to depth 63 (127), i.e. depth - levels <= 63 (127) < depth)."""
+    return dict(events=len(events), max_levels=max((lv for _, _, lv in events), default=0),
+                max_depth=max((d for _, d, _ in events), default=0),
+                cross64=sum(1 for _, d, lv in events if d - lv <= 63 < d),
+                cross128=sum(1 for _, d, lv in events if d - lv <= 127 < d))
 
 
 # ------------------------------------------------------------------------------------------------ brute force
@@ -346,3 +402,142 @@ def model_games(idx, solver=True, schedules=None, audit=None, trees=None, mirror
     if cached:
         _MODEL[key] = out
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the solver at product scale
+# Shared by tests/test_solver_scale_host.py and tests/test_solver_scale_gpu.py.  A sequence is play_game on ONE kept tree without
+# root noise and with num_probabilistic_actions=0 (the move is the first maximum of the recorded counts, no uniform is drawn): search,
+# re-root to the move, search again, to the end of the game.  Policies are the memoised ones of product_scale_cases.py (hashed
+# softmax) and deep_line_cases.py (the line policy), so the model, the C oracle and an engine's HostPolicyEvaluator share evaluations.
+# The positions were picked on the CPU so that the conditions of tests/test_solver_scale_host.py hold: an edit that moves one has
+# to keep them.
+SCALE_CASES = {
+    "c4_mid": dict(game=C4, n_playouts=400, start=PS._C4_GAME[:8]),
+    "c4_late": dict(game=C4, n_playouts=400, start=PS._C4_GAME[:15]),
+    "c4_5_16": dict(game=C4, n_playouts=400, start=c4_late_prefix(5, 16)),
+    "c4_3_14": dict(game=C4, n_playouts=400, start=c4_late_prefix(3, 14)),
+    "bt6_800": dict(game=PS.BT6, n_playouts=800, start=PS._BT6_GAME[:23]),
+    # (the model's sequence from _BT8_GAME[:40] runs seven full searches; this is its position after four moves: four full searches,
+    # one that ends after 716 playouts and three proven roots - the whole sequence took too long for one GPU test)
+    "bt8_1600": dict(game=PS.BT8, n_playouts=1600, start=PS._BT8_GAME[:40] + [48, 598, 421, 260]),
+}
+LATE_C4 = ("c4_5_16", "c4_3_14")
+
+# One search from the initial position under the line policy: key -> game, playouts, salt, value scale.  bt8x8: proofs at depths
+# 63..92, the walk up the path crosses lane 63 of register 0 / lane 0 of register 1.  bt26x2_128: the first terminal lies at depth
+# 129 (the salt search is in DESIGN_HISTORY.md), climbs of 3 and 5 levels from there cross register 2 / register 1.  bt26x2: a
+# 5-level climb from depth 149, all inside register 2.
+DEEP_CASES = {
+    "bt8x8": dict(game="breakthrough(rows=8,columns=8)", n_playouts=290, salt=15, vs=0.01),
+    "bt26x2_128": dict(game="breakthrough(rows=26,columns=2)", n_playouts=177, salt=90, vs=0.01),
+    "bt26x2": dict(game="breakthrough(rows=26,columns=2)", n_playouts=340, salt=13, vs=0.01),
+}
+DEEP_GAME = dict(game="breakthrough(rows=8,columns=8)", n_playouts=90, salt=15, vs=0.01)   # the self-play game along bt8x8's line
+
+# Whole self-play games with root noise and injected draws (FC.draws(seed, game, n_games)), kept trees, n_games = n_slots.
+GAME_CASES = {
+    "c4_5_16_soft_z": dict(game=C4, n_playouts=400, start=c4_late_prefix(5, 16), n_games=2, seed=21, backup="soft-Z"),
+    "c4_3_14_off_policy": dict(game=C4, n_playouts=400, start=c4_late_prefix(3, 14), n_games=2, seed=22, backup="off-policy"),
+    "bt6_soft_z": dict(game=PS.BT6, n_playouts=800, start=PS._BT6_GAME[:23], n_games=1, seed=23, backup="soft-Z"),
+}
+
+_SCALE = {}
+
+
+def scale_model(key, solver=True, audit=None):
+    """The model's sequence of SCALE_CASES[key] with tree dumps, computed once per (case, solver).  solver=False: as many searches
+    as the solver's sequence has."""
+    if audit is None and (key, solver) in _SCALE:
+        return _SCALE[key, solver]
+    c = SCALE_CASES[key]
+    out = play_game(c["game"], PS.SALT, None, None, solver=solver, n_playouts=c["n_playouts"], use_dirichlet=False,
+                    keep_search_tree=True, backup="soft-Z", num_probabilistic_actions=0, start=c["start"], policy=PS.policy(c["game"]),
+                    dumps=audit is None, audit=audit, max_searches=None if solver else len(scale_model(key, True)["plies"]))
+    if audit is None:
+        _SCALE[key, solver] = out
+    return out
+
+
+def oracle_sequence(key, n_searches):
+    """SCALE_CASES[key] with the C oracle as product_scale_cases.oracle_sequence runs a sequence: search, update_root(most visited
+    child), search again -> per search dict(tree, root, counters, move)."""
+    c = SCALE_CASES[key]
+    m = orc.MCTS(PS.policy(c["game"]), c["game"], n_playouts=c["n_playouts"], use_dirichlet=False)
+    s = orc.State(c["game"])
+    for a in c["start"]:
+        s.apply_action(a)
+    rows = []
+    while len(rows) < n_searches and not s.is_terminal():
+        if rows:
+            m.update_root(rows[-1]["move"])
+        m.search(s)
+        root = m.root_stats()
+        rows.append(dict(tree=m.dump_tree(), root=root, counters=m.counters(), move=PS.most_visited(root)))
+        s.apply_action(rows[-1]["move"])
+    return rows
+
+
+def deep_policy(c):
+    return DL.policy(c["game"], c["salt"], c["vs"])
+
+
+def deep_model(key, solver=True):
+    """The model's one search of DEEP_CASES[key] from the initial position, with its tree dump, computed once."""
+    if ("deep", key, solver) not in _SCALE:
+        c = DEEP_CASES[key]
+        _SCALE["deep", key, solver] = play_game(c["game"], c["salt"], None, None, solver=solver, n_playouts=c["n_playouts"],
+                                                use_dirichlet=False, keep_search_tree=True, backup="soft-Z",
+                                                num_probabilistic_actions=0, policy=deep_policy(c), dumps=True, max_searches=1)
+    return _SCALE["deep", key, solver]
+
+
+def oracle_deep(key):
+    """DEEP_CASES[key] with the C oracle as deep_line_cases.oracle_search runs a case -> (dump_tree(), counters)."""
+    c = DEEP_CASES[key]
+    m = orc.MCTS(deep_policy(c), c["game"], n_playouts=c["n_playouts"], use_dirichlet=False)
+    s = orc.State(c["game"])
+    for _ in range(c["n_playouts"]):
+        m.playout(s)
+    return m.dump_tree(), m.counters()
+
+
+def deep_game_model(solver=True):
+    """The self-play game along bt8x8's line: kept tree, soft-Z, no root noise, num_probabilistic_actions=0; computed once."""
+    if ("deep_game", solver) not in _SCALE:
+        c = DEEP_GAME
+        _SCALE["deep_game", solver] = play_game(c["game"], c["salt"], None, None, solver=solver, n_playouts=c["n_playouts"],
+                                                use_dirichlet=False, keep_search_tree=True, backup="soft-Z",
+                                                num_probabilistic_actions=0, policy=deep_policy(c))
+    return _SCALE["deep_game", solver]
+
+
+def game_models(key):
+    """The model's games of GAME_CASES[key], computed once."""
+    if ("game", key) not in _SCALE:
+        c = GAME_CASES[key]
+        etas, us = FC.draws(c["seed"], c["game"], c["n_games"])
+        _SCALE["game", key] = [play_game(c["game"], PS.SALT, etas[i], us[i], solver=True, n_playouts=c["n_playouts"],
+                                         keep_search_tree=True, backup=c["backup"], start=c["start"], policy=PS.policy(c["game"]))
+                               for i in range(c["n_games"])]
+    return _SCALE["game", key]
+
+
+def small_pool(key):
+    """A pool that makes the re-rootings of GAME_CASES[key] compact -> (nodes_per_slot, compactions expected): one search's room
+    plus the largest subtree a re-rooting keeps plus slack, and the engine's bookkeeping (reroot) replayed on the model's tree
+    sizes as product_scale_cases.small_pool replays it on the oracle's.  Asserts that the kept subtree plus a search's room fits
+    at every re-rooting: POOL_EXHAUSTED cannot be the outcome."""
+    c = GAME_CASES[key]
+    games = game_models(key)
+    need = (c["n_playouts"] + 1) * PS.max_children(c["game"])
+    cap = need + max(p["kept_nodes"] for w in games for p in w["plies"]) + 64
+    compactions = 0
+    for w in games:
+        alloc = 1
+        for p, nxt in zip(w["plies"][:-1], w["plies"][1:]):
+            alloc += p["nodes"] - p["kept_nodes"]
+            assert alloc <= cap
+            if alloc + need > cap:
+                alloc, compactions = nxt["kept_nodes"], compactions + 1
+            assert alloc + need <= cap
+    return cap, compactions
