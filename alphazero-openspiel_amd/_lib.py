@@ -117,6 +117,7 @@ PROTOTYPES = [
     ("az_engine_set_eval_mirror", C.c_int, [_vp, C.c_double]),
     ("az_engine_read_request_mirror", C.c_int, [_vp, C.c_int32]),
     ("az_engine_set_solver", C.c_int, [_vp, C.c_int32]),
+    ("az_engine_set_fpu", C.c_int, [_vp, C.c_int32, C.c_double, C.c_double]),
     ("az_engine_read_proofs", C.c_int64, [_vp, C.c_int32, C.POINTER(C.c_int8), C.c_int64]),
     ("az_engine_proofs_device_bytes", C.c_int64, [_vp]),
     ("az_engine_export_proofs_device", C.c_int, [_vp, _vp, C.c_int64, _vp]),

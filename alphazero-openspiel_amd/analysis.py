@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from .engine import (DeviceEvaluator, EngineError, HostPolicyEvaluator, SelfPlayEngine, TickDriver, close_all, default_device,
-                     make_evaluator, read_lines)
+                     fpu_pair, make_evaluator, read_lines)
 from .games import Game, State
 
 PHASE_IDLE, PHASE_SEARCH_DONE = 0, 5
@@ -81,11 +81,14 @@ class Analyzer:
     (SelfPlayEngine.set_eval_mirror; the coin is keyed by seed, position index, ply and request).
     solver=True: MCTS-Solver (SelfPlayEngine.set_solver) - a search ends as soon as its root is proven, and results() gains
     solved [n] (object array: +1 / 0 / -1 for the side to move, None while unknown) and solved_children [n, A] int8 (the same
-    for the side to move after each move; -128 where unknown or no child)."""
+    for the side to move after each move; -128 where unknown or no child).
+    fpu=r or (r, r_root): first-play urgency in every search (SelfPlayEngine.set_fpu): an unvisited child is valued at its parent's
+    value minus r * sqrt(explored prior mass) (r_root at the root, default 0) in place of the reference's 0."""
 
     def __init__(self, policy_fn, game_name, n_slots, n_playouts=100, c_puct=2.5, use_dirichlet=False, device=None,
                  eval_backend="fused", eval_precision="f32x", seed=None, check_every=16, pv_depth=0, eval_mirror=None, solver=False,
-                 **kwargs):
+                 fpu=None, **kwargs):
+        fpu = None if fpu is None else fpu_pair(fpu)
         if int(n_slots) < 1:
             raise ValueError("n_slots must be positive")
         if int(check_every) < 1:
@@ -107,6 +110,8 @@ class Analyzer:
             self.solver = bool(solver)
             if self.solver:
                 self.engine.set_solver(True)
+            if fpu is not None:
+                self.engine.set_fpu(*fpu)
             if policy_fn is not None:
                 self.evaluator, self._owns_evaluator = _make_evaluator(policy_fn, self.engine.device, eval_backend,
                                                                        eval_precision, int(n_slots))
@@ -297,7 +302,7 @@ def dense_roots(roots, n, num_actions):
 
 def analyze_positions(policy_fn, game_name, histories, n_playouts=100, c_puct=2.5, use_dirichlet=False, n_slots=None,
                       device=None, eval_backend="fused", eval_precision="f32x", seed=None, check_every=16, pv_depth=0,
-                      eval_mirror=None, solver=False, **kwargs):
+                      eval_mirror=None, solver=False, fpu=None, **kwargs):
     """Search every given position with n_playouts of PUCT search, all of them side by side on the device.
 
     policy_fn   the network (nn.Module or its bound .predict) or an evaluator object, as elsewhere in the package
@@ -308,6 +313,7 @@ def analyze_positions(policy_fn, game_name, histories, n_playouts=100, c_puct=2.
                 pv_len [n] (the whole greedy line's length) and greedy_value [n] (the off-policy target A0GB at its end)
     eval_mirror p: every request is evaluated left-right mirrored with probability p (SelfPlayEngine.set_eval_mirror)
     solver      True: MCTS-Solver (SelfPlayEngine.set_solver); the result gains solved [n] and solved_children [n, A] (Analyzer)
+    fpu         r or (r, r_root): first-play urgency in every search (SelfPlayEngine.set_fpu)
     kwargs      further SelfPlayEngine keywords (dirichlet_ratio, use_puct, nodes_per_slot, max_sims_per_tick, ...)
 
     Returns a dict, rows in the order given: visits [n, A] int64, q [n, A], priors [n, A] float64 (zero where there is no
@@ -322,7 +328,7 @@ def analyze_positions(policy_fn, game_name, histories, n_playouts=100, c_puct=2.
         raise ValueError("n_slots must be positive")
     an = Analyzer(policy_fn, game, n_slots, n_playouts=n_playouts, c_puct=c_puct, use_dirichlet=use_dirichlet, device=device,
                   eval_backend=eval_backend, eval_precision=eval_precision, seed=seed, check_every=check_every, pv_depth=pv_depth,
-                  eval_mirror=eval_mirror, solver=solver, **kwargs)
+                  eval_mirror=eval_mirror, solver=solver, fpu=fpu, **kwargs)
     try:
         parts = []
         prog = {k: 0 for k in _PROGRESS_SUMS}

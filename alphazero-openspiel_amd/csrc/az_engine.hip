@@ -1036,7 +1036,11 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
 // SOLVER = true (picked at launch when az_engine_set_solver is in force; never together with FORCED): MCTS-Solver, rules 1-5 of
 // include/az_engine.h.  The status word rides in the 16 bytes every select loads anyway; a proof event (rare) walks the path
 // registers upward.  SOLVER = false compiles to the kernel without the feature.
-template <int GAME, int NP, bool MAPPED, bool FORCED, bool MIRROR, bool SOLVER>
+// FPU = true (picked at launch when az_engine_set_fpu is in force; with any of the three above): first-play urgency, the rule of
+// include/az_engine.h.  A child with N = 0 enters the comparison with Q_eff = -X.Q - f * sqrt(m) in place of 0: X.Q is wave-uniform
+// (the path registers' root Q at depth 0, the selected child's Q below), m one wave_sum_d over the priors of the visited children -
+// registers only, no load.  FPU = false compiles to the kernel without the feature.
+template <int GAME, int NP, bool MAPPED, bool FORCED, bool MIRROR, bool SOLVER, bool FPU>
 __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_first, const int g_end, const float *__restrict__ priors,
                                                   const float *__restrict__ values, float *__restrict__ obs_out) {
     const int lane = threadIdx.x & 63;
@@ -1237,11 +1241,16 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
         float ret0 = 0.f;
         int mover = s.ply & 1;
         [[maybe_unused]] uint32_t pst = AZ_PROOF_UNKNOWN; // SOLVER: the status of the node the descent stands on
+        // FPU: the Q of the node the descent stands on, as its record holds it - the root's from lane 0 of the path registers, which
+        // the backups of this launch (the answered request's, a chained terminal hit's) have kept equal to the record
+        [[maybe_unused]] double xq = 0.0;
+        if constexpr (FPU) xq = readlane_d(path.pq[0], 0);
         while (nc > 0 && !term && !(SOLVER && pst != AZ_PROOF_UNKNOWN)) {
             mover = s.ply & 1;
             double val = -INFINITY, cq = 0.0;
             uint32_t cn = 0, cc0 = NONE32, cmeta = 0;
             [[maybe_unused]] uint32_t cst = AZ_PROOF_UNKNOWN;
+            [[maybe_unused]] double cp = 0.0;
             if (lane < nc) {
                 AzNode c;
                 if (depth == 0 && rc_valid) { // (wave-uniform) a chained playout: the root's children are still in registers
@@ -1266,6 +1275,7 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
                 cc0 = c.C0;
                 cmeta = c.META;
                 cq = c.Q;
+                if constexpr (FPU) cp = c.P;
                 if (sr.rule == AZ_SELECT_PUCT)
                     val = c.Q + ((p.c_puct * c.P) * sqrt((double)np_)) / (double)(cn + 1); // mcts.py:78
                 else // mcts.py:80; log(N_parent) from the host's table (N_parent >= 1 whenever a child has a visit)
@@ -1280,6 +1290,15 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
                     if (cst == AZ_PROOF_LOSS) val = -INFINITY;
                 }
             }
+            if constexpr (FPU) { // (az_engine_set_fpu refuses AZ_SELECT_UCT: every tree of the engine is a PUCT tree)
+                // m: the prior mass already explored, +0.0 in the lanes of unvisited children and beyond the children
+                const double m = wave_sum_d(cn > 0 ? cp : 0.0);
+                // v - f * sqrt(m), v = -X.Q: two roundings, never one fused operation, whatever the contraction flag says
+                const double q_eff = __dsub_rn(-xq, __dmul_rn(depth == 0 ? p.fpu_reduction_root : p.fpu_reduction, sqrt(m)));
+                // an unvisited child is never forced (n > 0 there) and never proven (a status is written after a backup: N >= 1),
+                // so the value set here is the one that reaches the ballot
+                if (lane < nc && cn == 0) val =q_eff + (p.c_puct * cp) * sqrt((double)np_); // / (0 + 1)
+            }
             double mx = wave_max(val);
             unsigned long long eq = __ballot(val == mx);
             int best = eq ? __ffsll(eq) - 1 : 0; // first maximum in child order (mcts.py:50)
@@ -1293,6 +1312,7 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
             meta = (uint32_t)__builtin_amdgcn_readlane((int)cmeta, best);
             const double qsel = readlane_d(cq, best);
             if constexpr (SOLVER) pst = (uint32_t)__builtin_amdgcn_readlane((int)cst, best);
+            if constexpr (FPU) xq = qsel;
             nc = c0 == NONE32 ? 0 : (int)(meta >> 16);
             term = az_apply<GAME>(s, geom, (int)(meta & 0xFFFFu), &ret0);
             depth++;
@@ -1391,7 +1411,7 @@ __device__ __forceinline__ void advance_slot_wave(const Params &p, const int g_f
     }
 }
 
-template <int GAME, int NP, bool MAPPED, bool FORCED, bool MIRROR, bool SOLVER>
+template <int GAME, int NP, bool MAPPED, bool FORCED, bool MIRROR, bool SOLVER, bool FPU>
 __global__ __launch_bounds__(256) void az_advance_kernel(Params p, const int g_first, const int g_end, const float *__restrict__ priors,
                                                          const float *__restrict__ values, float *__restrict__ obs_out) {
     const int n_slot_wgs = (g_end - g_first + 3) >> 2;
@@ -1400,7 +1420,7 @@ __global__ __launch_bounds__(256) void az_advance_kernel(Params p, const int g_f
         return;
     }
     const int epoch = p.defer_compact ? p.cjob_count[0] : 0; // (the same in every wave of the launch: compact_jobs)
-    advance_slot_wave<GAME, NP, MAPPED, FORCED, MIRROR, SOLVER>(p, g_first, g_end, priors, values, obs_out);
+    advance_slot_wave<GAME, NP, MAPPED, FORCED, MIRROR, SOLVER, FPU>(p, g_first, g_end, priors, values, obs_out);
     // every slot wave reports itself seen, whichever way it left: its extra workgroup stays until none of its rows can hand over a job
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (p.defer_compact && (threadIdx.x & 63) == 0 && g_first + row < g_end)
@@ -2228,6 +2248,30 @@ extern "C" int az_engine_set_solver(az_engine *e, int32_t on) {
     return AZ_OK;
 }
 
+// ---- first-play urgency (include/az_engine.h: az_engine_set_fpu) -------------------------------------------------------------------
+extern "C" int az_engine_set_fpu(az_engine *e, int32_t on, double reduction, double reduction_root) {
+    if (!e) return AZ_E_INVALID;
+    const char *why = nullptr;
+    if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) why = "an arena engine (an evaluation game measures the reference's search)";
+    else if (e->cfg.select_rule != AZ_SELECT_PUCT) why = "select_rule = AZ_SELECT_UCT (that rule already values an unvisited child at +infinity)";
+    if (why) {
+        e->err = std::string("az_engine_set_fpu is for PUCT self-play and manual_moves engines: refused for ") + why;
+        return AZ_E_INVALID;
+    }
+    const double dmax = 1.7976931348623157e308;
+    if (on && !(reduction >= 0.0 && reduction <= dmax && reduction_root >= 0.0 && reduction_root <= dmax)) { // (the negated form takes NaN too)
+        e->err = "az_engine_set_fpu: reduction and reduction_root must be finite and >= 0 (on = 0 clears the setting)";
+        return AZ_E_INVALID;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, hipDeviceSynchronize()); // a generation that still plays was launched under the old setting
+    e->p.fpu_on = on ? 1 : 0;
+    e->p.fpu_reduction = on ? reduction : 0.0;
+    e->p.fpu_reduction_root = on ? reduction_root : 0.0;
+    e->reset_done = false; // the caller starts a generation next (az_engine_reset / az_engine_stream_begin)
+    return AZ_OK;
+}
+
 // ---- evaluation in a random left-right orientation (include/az_engine.h: az_engine_set_eval_mirror) ----------------------------
 extern "C" int az_engine_set_eval_mirror(az_engine *e, double p_mirror) {
     if (!e) return AZ_E_INVALID;
@@ -2248,13 +2292,23 @@ extern "C" int az_engine_set_eval_mirror(az_engine *e, double p_mirror) {
 }
 
 // The tick kernel's instantiation for the settings in force (az_engine_set_forced_playouts, az_engine_set_eval_mirror,
-// az_engine_set_solver: each its own instantiations; with none set the engine launches the kernel without any of the features).
+// az_engine_set_solver, az_engine_set_fpu: each its own instantiations; with none set the engine launches the kernel without any of
+// the features).
 template <int GAME, int NP, bool MAPPED>
 static void launch_tick(az_engine *e, dim3 grid, dim3 block, hipStream_t st, int g_first, int g_end, const float *priors,
                         const float *values, float *obs_out) {
     const bool forced = e->p.forced_k > 0.0, mirror = e->p.p_mirror > 0.0;
-#define AZ_TICK(F, M) hipLaunchKernelGGL((az_advance_kernel<GAME, NP, MAPPED, F, M, false>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out)
-#define AZ_TICK_SOLVER(M) hipLaunchKernelGGL((az_advance_kernel<GAME, NP, MAPPED, false, M, true>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out)
+#define AZ_TICK_FPU(F, M, SV, U) hipLaunchKernelGGL((az_advance_kernel<GAME, NP, MAPPED, F, M, SV, U>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out)
+#define AZ_TICK(F, M)        \
+    do {                     \
+        if (e->p.fpu_on) AZ_TICK_FPU(F, M, false, true); \
+        else AZ_TICK_FPU(F, M, false, false);            \
+    } while (0)
+#define AZ_TICK_SOLVER(M)    \
+    do {                     \
+        if (e->p.fpu_on) AZ_TICK_FPU(false, M, true, true); \
+        else AZ_TICK_FPU(false, M, true, false);            \
+    } while (0)
     if (e->p.solver) { // (never with forced playouts: the two setters refuse each other)
         if (mirror) AZ_TICK_SOLVER(true);
         else AZ_TICK_SOLVER(false);
@@ -2267,6 +2321,7 @@ static void launch_tick(az_engine *e, dim3 grid, dim3 block, hipStream_t st, int
     }
 #undef AZ_TICK
 #undef AZ_TICK_SOLVER
+#undef AZ_TICK_FPU
 }
 
 // `defer`: compactions of this launch are handed to its own extra workgroups (compact_jobs; whole-engine launches only: the job

@@ -143,9 +143,14 @@ struct Params {
     double p_mirror;
     // MCTS-Solver (az_engine_set_solver): 0 = off.  Read by the host's launch alone, which picks the SOLVER instantiations of
     // az_advance_kernel while it is set; appended, so no other field moves.
-    int solver, solver_pad;
+    int solver;
+    // first-play urgency (az_engine_set_fpu): fpu_on = 0 = the reference's Q = 0 for an unvisited child.  fpu_on is read by the host's
+    // launch alone, which picks the FPU instantiations of az_advance_kernel while it is set (the word was padding); these read the
+    // two reductions, appended, so no other field moves.
+    int fpu_on;
+    double fpu_reduction, fpu_reduction_root;
 };
-static_assert(sizeof(Params) == 968, "Params is passed by value to every kernel and baked into captured graphs: its layout does not move");
+static_assert(sizeof(Params) == 984, "Params is passed by value to every kernel and baked into captured graphs: its layout does not move");
 
 // The engine's own record arrays as a view (az_records.h); the tick kernel keeps reading p.rec_* itself.
 static inline AzRecords records_of(const Params &p) {

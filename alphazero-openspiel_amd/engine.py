@@ -93,6 +93,7 @@ class SelfPlayEngine:
         self.forced_playouts = None  # set_forced_playouts: (k, prune) while the setting is in force
         self.eval_mirror = None      # set_eval_mirror: p_mirror while the setting is in force
         self.solver = False          # set_solver: True while the setting is in force
+        self.fpu = None              # set_fpu: (reduction, root reduction) while the setting is in force
         self.n_games = 0
 
     # ------------------------------------------------------------------ plumbing
@@ -241,6 +242,21 @@ class SelfPlayEngine:
         reset() or stream_begin() afterwards."""
         self._check(self.lib.az_engine_set_solver(self._h, int(bool(on))))
         self.solver = bool(on)
+
+    def set_fpu(self, reduction, root=0.0):
+        """First-play urgency (az_engine_set_fpu): from the next reset() / stream_begin() on, an unvisited child enters the PUCT
+        comparison with Q = -parent.Q - f * sqrt(prior mass of the visited children) in place of the reference's 0; f = `root` at
+        the root of a search and `reduction` below, both finite and >= 0.  reduction=0 is not the reference ("worth what the parent
+        is worth"): clear_fpu() clears.  PUCT self-play and manual_moves engines (EngineError names the reason for an arena engine
+        and use_puct=False).  reset() or stream_begin() afterwards."""
+        self._check(self.lib.az_engine_set_fpu(self._h, 1, float(reduction), float(root)))
+        self.fpu = (float(reduction), float(root))
+
+    def clear_fpu(self):
+        """Back to the reference's Q = 0 for an unvisited child (az_engine_set_fpu with on = 0).  reset() or stream_begin()
+        afterwards."""
+        self._check(self.lib.az_engine_set_fpu(self._h, 0, 0.0, 0.0))
+        self.fpu = None
 
     def read_proofs(self, slot):
         """The proof status of every node of a slot's tree in the order of read_tree() (az_engine_read_proofs) -> int8 array:
@@ -845,6 +861,18 @@ def stream_take_layout(n_games, max_plies, max_children):
     return device_export_layout(n_games, max_plies, max_children)
 
 
+def fpu_pair(fpu):
+    """fpu=r or (r, r_root) -> (reduction, root reduction) as floats: both finite and >= 0, the root's 0 when left out (ValueError
+    otherwise).  The one validation of every fpu= keyword of the package."""
+    pair = tuple(fpu) if isinstance(fpu, (tuple, list)) else (fpu, 0.0)
+    if len(pair) != 2 or any(isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) for x in pair):
+        raise ValueError("fpu must be a reduction r or a pair (r, r_root) of numbers, got %r" % (fpu,))
+    r, r_root = float(pair[0]), float(pair[1])
+    if not (0.0 <= r < float("inf") and 0.0 <= r_root < float("inf")):
+        raise ValueError("fpu reductions must be finite and >= 0, got %r" % (fpu,))
+    return r, r_root
+
+
 class SelfPlayStream:
     """Continuous self-play: an engine in stream mode (az_engine_stream_begin), its request buffers and ONE tick driver.
     Slots never wait for the end of a generation: a finished slot takes the next game id at once, and take(n) hands the next n
@@ -860,10 +888,11 @@ class SelfPlayStream:
     the setting streams with it as well: the pruned counts travel in the records themselves).
     eval_mirror=p: SelfPlayEngine.set_eval_mirror before the stream begins (an engine that already carries the setting streams
     with it as well).
-    solver=True / False: SelfPlayEngine.set_solver before the stream begins (None leaves the engine's setting as it is)."""
+    solver=True / False: SelfPlayEngine.set_solver before the stream begins (None leaves the engine's setting as it is).
+    fpu=r or (r, r_root): SelfPlayEngine.set_fpu before the stream begins (None leaves the engine's setting as it is)."""
 
     def __init__(self, engine, evaluator, seed=None, use_graph=True, ticks_per_graph=16, check_every=32, forced_playouts=None,
-                 eval_mirror=None, solver=None):
+                 eval_mirror=None, solver=None, fpu=None):
         self.engine, self.evaluator = engine, evaluator
         self.use_graph, self.check_every = bool(use_graph), max(1, int(check_every))
         self.ticks_per_graph = min(max(1, int(ticks_per_graph)), self.check_every)
@@ -873,6 +902,8 @@ class SelfPlayStream:
             engine.set_eval_mirror(eval_mirror)
         if solver is not None:
             engine.set_solver(solver)
+        if fpu is not None:
+            engine.set_fpu(*fpu_pair(fpu))
         engine.stream_begin(seed)
         self.obs, self.pri, self.val = engine.alloc_io()
         self.taken = 0          # games handed over so far = the id of the next one

@@ -12,7 +12,7 @@ import copy
 import numpy as np
 import torch
 
-from .engine import (EngineError, SelfPlayEngine, SelfPlayStream, check_stream_request, close_all, examples_from_export,
+from .engine import (EngineError, SelfPlayEngine, SelfPlayStream, check_stream_request, close_all, examples_from_export, fpu_pair,
                      make_evaluator, run_selfplay, run_selfplay_pools, slot_groups, stream_capacity, unpack_device_export)
 from .games import Game
 from . import distributed as azdist
@@ -151,6 +151,17 @@ class ExampleGenerator:
             if self.forced_playouts is not None:
                 raise ValueError("solver is not supported together with forced_playouts")
 
+        # fpu=r or (r, r_root): first-play urgency (SelfPlayEngine.set_fpu) in every search.  A select rule that leaves the records'
+        # layout alone: it goes to EVERY engine this generator builds (pools, ranks, overlap, the stream of continuous=True).
+        self.fpu = kwargs.get("fpu")
+        if self.fpu is not None:
+            self.fpu = fpu_pair(self.fpu)
+            if self.is_test:
+                raise ValueError("fpu is a self-play setting: it is not supported with is_test=True (evaluation games measure the "
+                                 "reference's search)")
+            if not kwargs.get("use_puct", True):
+                raise ValueError("fpu is not supported with use_puct=False: that rule already values an unvisited child at +infinity")
+
     def _engine_kwargs(self):
         return {k: self.kwargs[k] for k in _ENGINE_KW if k in self.kwargs}
 
@@ -165,6 +176,8 @@ class ExampleGenerator:
                 engine.set_eval_mirror(self.eval_mirror)
             if self.solver:
                 engine.set_solver(True)
+            if self.fpu is not None:
+                engine.set_fpu(*self.fpu)
         except Exception:
             close_all(engine)
             raise

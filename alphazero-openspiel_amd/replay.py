@@ -277,7 +277,7 @@ class Reanalyser:
     greedy lines are then exported too (Analyzer.lines_device, one kernel, depth 1: the value does not depend on it) and the
     refresh goes through refresh_from_search.  Further keywords go to the Analyzer (c_puct, use_dirichlet, eval_precision,
     eval_mirror=p for searches whose requests are evaluated left-right mirrored with probability p, solver=True for MCTS-Solver
-    searches, ...).  With solver=True a search ends as soon as its root is proven and the refresh reads that root as it stands: the
+    searches, fpu=r or (r, r_root) for first-play urgency (SelfPlayEngine.set_fpu) in the searches, ...).  With solver=True a search ends as soon as its root is proven and the refresh reads that root as it stands: the
     raw visit counts and Q of what may be a handful of playouts, not the adjusted counts and exact value self-play records there.
     The store must not change between the calls made here (it is the caller's between reanalyse() calls); the next dedupe()
     averages a refreshed first occurrence with its stale duplicates, as the reference's aliasing does."""
@@ -346,17 +346,21 @@ class Forker:
     earlier forks are; the games of an engine with ONE shared set_start_prefix of length > 0 are keyed from that prefix's
     position instead - a fork off such a game still merges with its parent, but when it repeats the parent's next move the next
     dedupe() meets one `key` with two `key2` and raises the KEY_COLLISION fault.  Do not fork out of such a store.  One engine lives across the calls; further keywords go to it (c_puct, temperature, backup, ...).  Positions are
-    drawn WITH replacement: two forks of one position are two different games (the random stream is keyed by game id)."""
+    drawn WITH replacement: two forks of one position are two different games (the random stream is keyed by game id).
+    fpu=r or (r, r_root): the forked games are searched with first-play urgency (SelfPlayEngine.set_fpu)."""
 
     def __init__(self, store, net, n_slots, n_playouts, eval_backend="fused", eval_precision="f32x", use_graph=False, seed=0,
-                 max_games=None, **kwargs):
-        from .engine import SelfPlayEngine, make_evaluator
+                 max_games=None, fpu=None, **kwargs):
+        from .engine import SelfPlayEngine, fpu_pair, make_evaluator
+        fpu = None if fpu is None else fpu_pair(fpu)
         self.store, self.seed, self.use_graph, self.calls = store, int(seed), bool(use_graph), 0
         self.eval_backend, self.eval_precision = eval_backend, eval_precision
         self.engine = SelfPlayEngine(store.game, int(n_slots), n_playouts=int(n_playouts), device=store.device, seed=self.seed,
                                      max_games=int(max_games if max_games is not None else n_slots), **kwargs)
         self.evaluator = None
         try:
+            if fpu is not None:
+                self.engine.set_fpu(*fpu)
             self.evaluator = make_evaluator(net, store.device, eval_backend, eval_precision, self.engine.G)
         except Exception:
             self.engine.close()

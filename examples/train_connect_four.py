@@ -64,6 +64,10 @@ def main():
                     help="MCTS-Solver: prove wins, losses and draws inside the search tree (self-play, and the searches of "
                          "--reanalyse): never select a move proven lost, end a search whose root is proven, play a proven win and "
                          "record exact targets there; not together with --forced-playouts")
+    ap.add_argument("--fpu", default="", metavar="R[:R_ROOT]",
+                    help="first-play urgency reduction, as Lc0 and KataGo select: an unvisited child is valued at its parent's value "
+                         "minus R * sqrt(explored prior mass) (R_ROOT at the root, default 0) in place of the reference's 0, in "
+                         "self-play and in the searches of --reanalyse and --fork (e.g. 0.3)")
     a = ap.parse_args()
     if not 0.0 <= a.forced_playouts < float("inf"):
         ap.error("--forced-playouts takes a finite K >= 0")
@@ -71,6 +75,12 @@ def main():
         ap.error("--solver is not available together with --forced-playouts")
     if not 0.0 <= a.eval_mirror <= 1.0:
         ap.error("--eval-mirror takes a probability in [0, 1]")
+    fpu = None
+    if a.fpu:
+        try:
+            fpu = E.fpu_pair(tuple(float(x) for x in a.fpu.split(":")) if ":" in a.fpu else float(a.fpu))
+        except ValueError:
+            ap.error("--fpu takes R or R:R_ROOT, both finite and >= 0, e.g. 0.3 or 0.3:0")
     cap = None
     if a.playout_cap:
         if a.continuous:
@@ -91,7 +101,8 @@ def main():
     if a.continuous:
         generator = ExampleGenerator(net, a.game, dev, continuous=True, n_slots=min(a.games, 4096), n_playouts=a.playouts,
                                      backup=a.backup, eval_precision=a.precision, seed=1,
-                                     forced_playouts=a.forced_playouts or None, eval_mirror=a.eval_mirror or None, solver=a.solver)
+                                     forced_playouts=a.forced_playouts or None, eval_mirror=a.eval_mirror or None, solver=a.solver,
+                                     fpu=fpu)
     for gen in range(1, a.generations + 1):
         t0 = time.perf_counter()
         net.eval()
@@ -110,6 +121,8 @@ def main():
                 eng.set_eval_mirror(a.eval_mirror)
             if a.solver:
                 eng.set_solver(True)
+            if fpu is not None:
+                eng.set_fpu(*fpu)
             if cap is not None:
                 eng.set_playout_cap(*cap)                                  # append_engine below keeps the full-search moves only
             prog = E.run_selfplay(eng, FusedNet(net, dev, max_boards=eng.G, precision=a.precision), a.games, use_graph=True)
@@ -125,7 +138,7 @@ def main():
             t_fk = time.perf_counter()
             if forker is None:
                 forker = replay.Forker(store, net, min(a.fork, 4096), a.playouts, eval_precision=a.precision, use_graph=True,
-                                       max_games=a.fork, backup=a.backup, seed=1000)
+                                       max_games=a.fork, backup=a.backup, seed=1000, fpu=fpu)
             else:
                 forker.set_net(net)
             forker.fork(n=a.fork, seed=gen)
@@ -137,7 +150,7 @@ def main():
             if reanalyser is None:
                 reanalyser = replay.Reanalyser(store, net, min(a.reanalyse, 4096), a.playouts,
                                                value_target=a.backup if a.backup in ("soft-Z", "A0C", "off-policy") else None,
-                                               eval_precision=a.precision, eval_mirror=a.eval_mirror or None, solver=a.solver)
+                                               eval_precision=a.precision, eval_mirror=a.eval_mirror or None, solver=a.solver, fpu=fpu)
             else:
                 reanalyser.set_evaluator(net)
             n_re = reanalyser.reanalyse(n=a.reanalyse, seed=gen)

@@ -413,6 +413,45 @@ int64_t az_engine_proofs_device_bytes(const az_engine *e);
 int az_engine_export_proofs_device(az_engine *e, void *dev_buf, int64_t bytes, void *stream);
 
 /*
+ * First-play urgency (FPU) reduction, as Lc0 and KataGo select: what an unvisited child is worth in the PUCT comparison.  The
+ * reference scores it with Q = 0 (Node.Q starts at 0, mcts.py:78) - the value of a draw, whatever the position is worth: in a won
+ * position every untried move looks worse than it should, in a lost one every untried move looks like salvation and the search
+ * sprays its playouts over all of them.  With the setting an unvisited child is valued at its parent's own value, minus a penalty
+ * that grows with the prior mass already explored.  It costs no evaluation, no launch and no memory; with nothing set every
+ * kernel computes what it computed before, bit for bit.
+ *
+ * The rule.  All arithmetic is IEEE double, one rounding per operation.  Consider a node X whose children are compared by the PUCT
+ *   rule (mcts.py:38-52,78).
+ *   v = -X.Q: X's value for the player who chooses there.  X.Q is the node record's own Q as it stands before this playout's
+ *     backup; for the root it is root.Q, the root_q of az_engine_read_root.
+ *   m = the sum of P_i over the children with N_i > 0.  P is the node's own prior (after the noise at the root, after the mirror
+ *     mapping).  The sum is a butterfly over 64 values: child i in position i, +0.0 for unvisited children and for positions
+ *     beyond the children; for off = 32, 16, 8, 4, 2, 1 every position l takes x[l] + x[l ^ off]; m is position 0.  The order is
+ *     part of the definition.
+ *   f = reduction_root at depth 0 (X is the search's root), reduction below.
+ *   A child with N == 0 enters the comparison with Q_eff = v - f * sqrt(m): two roundings, no fused multiply-add, no clamp.  Its
+ *     value is Q_eff + ((c_puct * P) * sqrt((double)N_X)) / (double)(0 + 1), the association of the existing line.
+ *   A child with N > 0 is valued as before.
+ *   Everything after the value is unchanged: forcing (n > 0 only, so the two never meet on one child), the solver's -infinity, the
+ *   first-maximum rule, AZ_FAULT_BAD_PRIOR (a NaN prior makes m NaN and ends there through the empty ballot), the backup, N and Q.
+ *   The rule acts in every search of the engine: fast and full under a cap, kept trees, roots searched again.
+ *
+ * az_engine_set_fpu: on == 0 clears the setting and the other two arguments are ignored (reduction == 0 is NOT the reference: it
+ *   means "an unvisited child is worth what its parent is worth", so clearing has its own flag).  With on != 0 both reductions
+ *   must be finite and >= 0, else AZ_E_INVALID.  Plain PUCT self-play engines (closed generations, az_engine_advance_slots on
+ *   several streams, the dense rows of az_engine_advance_rows, stream mode) and manual_moves engines (analysis, reanalyse); both
+ *   rng_modes (it draws nothing).  AZ_E_INVALID, with the reason in az_last_error, for an arena engine and for select_rule ==
+ *   AZ_SELECT_UCT (that rule already gives an unvisited child +infinity).  Call it before az_engine_reset or
+ *   az_engine_stream_begin (the next call the engine accepts): it holds for every later generation, and composes with a start
+ *   prefix, both start tables, a playout cap, forced playouts, the evaluation mirror, the solver and keep_search_tree.  Records,
+ *   exports, pools, ranks and the replay store do not change.
+ *
+ * Limits: no arena agents (so playing strength is not measured here), no UCT rule, no separate treatment of the fast moves of a
+ *   playout cap.  Lc0 and KataGo use values around 0.2 to 0.4 below the root and 0 at a noised root; unmeasured here.
+ */
+int az_engine_set_fpu(az_engine *e, int32_t on, double reduction, double reduction_root);
+
+/*
  * One tick = MCTS.playout's select + expand + backup (mcts.py:126-153) for all slots, fused with the
  * agent's move step when a slot has finished its S playouts (alphazerobot.py:71-93,
  * game_utils.py:156-197, mcts.py:155-162,192-203) and the root Dirichlet expansion (mcts.py:182-190):

@@ -1,0 +1,220 @@
+"""First-play urgency without a GPU: the Python model of tests/fpu_cases.py against the older models with the setting off (which
+the older host tests pin to the C oracle), the butterfly sum against a restatement of wave_sum_d and against the left-to-right sum,
+the effects the rule must show on the inputs of tests/test_fpu_gpu.py, the ABI surface and the facade's argument validation."""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import forced_playouts_cases as FC
+import fpu_cases as F
+import solver_cases as SC
+from alphazero_openspiel_amd import _lib
+from oracle import binding as orc
+from oracle import fakepolicy
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _same_plies(got, want, what, keys):
+    assert got["actions"] == want["actions"] and got["ret0"] == want["ret0"] and got["counters"] == want["counters"], what
+    assert not any(got["effects"].values()), what
+    for j, (a, b) in enumerate(zip(got["plies"], want["plies"])):
+        for key in keys:
+            assert a[key] == b[key], (what, j, key)
+
+
+# ------------------------------------------------------------------------------------------------ 1. off is the older models
+@pytest.mark.parametrize("idx", range(len(FC.CASES)))
+def test_without_the_setting_the_model_is_forced_playouts_cases_play_game(idx):
+    """k = 0 (play_game_self itself, pinned to the C oracle by tests/test_forced_playouts_host.py) and k = 2 with pruning."""
+    c = FC.CASES[idx]
+    etas, us = FC.draws(c["seed"], c["game"], c["n_games"])
+    for k in (0.0, FC.K):
+        for i, want in enumerate(FC.model_games(idx, k)):
+            got = F.play_game(c["game"], c["salt"], etas[i], us[i], fpu=None, k=k, prune_targets=True, n_playouts=FC.S, **c["kw"])
+            _same_plies(got, want, (idx, k, i), ("raw", "recorded", "actions", "move", "pi", "value", "full"))
+
+
+@pytest.mark.parametrize("idx", [i for i, c in enumerate(SC.CASES) if c["start"] is None])
+def test_without_the_setting_the_model_is_the_c_oracle(idx):
+    """Straight against play_game_self of the C oracle, on the cases tests/test_solver_host.py pins to it."""
+    c = SC.CASES[idx]
+    A = FC.geometry(c["game"])[0]
+    etas, us = FC.draws(c["seed"], c["game"], c["n_games"])
+    for i in range(c["n_games"]):
+        got = F.play_game(c["game"], c["salt"], etas[i], us[i], fpu=None, n_playouts=SC.S, **c["kw"])
+        want = orc.play_game_self(lambda b: fakepolicy.fake_eval(b, A, c["salt"]), c["game"], etas=etas[i], us=us[i],
+                                  n_playouts=SC.S, **c["kw"])
+        assert got["actions"] == want["actions"] and got["ret0"] == want["ret0"] and got["counters"] == want["counters"], (idx, i)
+        assert not any(got["effects"].values())
+        for j, ply in enumerate(got["plies"]):
+            assert ply["raw"] == ply["recorded"] == want["root_cN"][j], (idx, i, j)
+            assert ply["pi"] == want["examples"][j][2] and ply["value"] == want["examples"][j][3], (idx, i, j)
+
+
+@pytest.mark.parametrize("idx", range(len(SC.CASES)))
+def test_without_the_setting_the_model_is_solver_cases_play_game(idx):
+    """With the solver on and off, start prefixes included."""
+    c = SC.CASES[idx]
+    etas, us = FC.draws(c["seed"], c["game"], c["n_games"])
+    for solver in (False, True):
+        for i, want in enumerate(SC.model_games(idx, solver=solver)):
+            got = F.play_game(c["game"], c["salt"], etas[i], us[i], fpu=None, solver=solver, n_playouts=SC.S,
+                              start=SC.case_start(c), **c["kw"])
+            _same_plies(got, want, (idx, solver, i), ("raw", "recorded", "actions", "move", "pi", "value", "ran", "status", "full"))
+
+
+# ------------------------------------------------------------------------------------------------ 2. the butterfly sum
+def _wave_sum_d(v):
+    """csrc/az_engine.hip, wave_sum_d, lane by lane: for (off = 32; off; off >>= 1) v += __shfl_xor(v, off) -> lane 0."""
+    v = np.array(v, dtype=np.float64)
+    lanes = np.arange(64)
+    off = 32
+    while off:
+        v = v + v[lanes ^ off]
+        off >>= 1
+    return float(v[0])
+
+
+def _left_to_right(xs):
+    tot = 0.0
+    for x in xs:
+        tot = tot + x
+    return tot
+
+
+def test_the_butterfly_is_wave_sum_d():
+    r = np.random.RandomState(5)
+    for n in (64, 64, 64, 7, 16, 17, 33, 48):
+        xs = (r.random_sample(n) * (r.random_sample(n) < 0.6)).tolist()
+        assert F.butterfly(xs) == _wave_sum_d(xs + [0.0] * (64 - n))
+    assert F.butterfly([]) == 0.0 and math.copysign(1.0, F.butterfly([])) == 1.0
+    assert F.butterfly([0.1, 0.2, 0.3]) == (0.1 + 0.3) + 0.2               # positions 0 and 2 meet at off = 2, position 1 at off = 1
+
+
+def _nodes(dump):
+    """A tree dump as (children rows of node i) lists."""
+    kids = {}
+    for i, p in enumerate(dump["parent"].tolist()):
+        if p >= 0:
+            kids.setdefault(p, []).append(i)
+    return kids
+
+
+def test_the_order_of_the_sum_matters_on_the_table():
+    """The fake policy's priors are float32 numbers, whose sums are exact in doubles in any order; a noised root's are not.  So on
+    every whole-game case of the table there are selections at which the left-to-right sum of the visited children's priors is
+    another number than the butterfly's: an engine (or a model) that sums in child order computes another m there - and, the root's
+    reduction being non-zero, another value."""
+    assert F.FPU[1] > 0.0
+    for key in F.GAMES:
+        assert sum(w["order_sensitive"] for w in F.game_models(key)) > 0, key
+    xs = [0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7]
+    assert F.butterfly(xs) != _left_to_right(xs)
+
+
+# ------------------------------------------------------------------------------------------------ 3. the rule bites on the table
+def test_the_searches_of_the_table_are_what_they_are_chosen_for():
+    for key, c in F.SEARCHES.items():
+        w, dumps = F.search_model(key)
+        off, dumps_off = F.search_model(key, None)
+        assert len(dumps) == 1 + c["again"] and w["counters"]["sims"] == (1 + c["again"]) * c["n_playouts"]
+        assert all(w["effects"][k] > 0 for k in F.EFFECTS), (key, w["effects"])
+        assert w["plies"][0]["raw"] != off["plies"][0]["raw"] or w["plies"][0]["move"] != off["plies"][0]["move"], key
+        assert dumps[-1]["N"].tolist() != dumps_off[-1]["N"].tolist(), key
+        widest = max(len(k) for k in _nodes(dumps[-1]).values())
+        visited_beyond = max((j for kids in _nodes(dumps[-1]).values() for j, i in enumerate(kids) if dumps[-1]["N"][i] > 0), default=0)
+        if key == "c4":
+            assert widest == 7
+        if key == "bt6":
+            assert widest > 16 and visited_beyond >= 16                  # a visited child at position 16 or beyond: its P enters m
+        if key == "bt8":
+            assert widest > 32 and visited_beyond >= 32                  # ... beyond lane 32: the off = 32 step carries weight
+        if key == "c4_deep":
+            assert w["max_depth"] > 8
+        if key == "c4_again":                                            # the second search went on in the first one's tree
+            assert int(dumps[1]["N"][0]) == 2 * c["n_playouts"] and int(dumps[0]["N"][0]) == c["n_playouts"]
+    assert F.FPU[0] != F.FPU[1] and F.FPU[1] > 0.0
+    for key in ("c4", "bt6"):                                            # and a mix-up of the two reductions shows in the tree
+        c = F.SEARCHES[key]
+        swapped = F.play_game(c["game"], c["salt"], None, None, fpu=(F.FPU[1], F.FPU[0]), n_playouts=c["n_playouts"],
+                              use_dirichlet=False, backup="soft-Z", num_probabilistic_actions=0, start=c["start"], max_searches=1)
+        assert swapped["plies"][0]["raw"] != F.search_model(key)[0]["plies"][0]["raw"] or \
+            swapped["counters"] != F.search_model(key)[0]["counters"], key
+
+
+@pytest.mark.parametrize("key", list(F.GAMES))
+def test_the_games_of_the_table_differ_from_the_games_without_the_setting(key):
+    """Every effect counter non-zero, and every game's records differ from the fpu=None game's: the parity of
+    tests/test_fpu_gpu.py cannot pass on an engine that accepts the setting and ignores it."""
+    on, off = F.game_models(key), F.game_models(key, None)
+    c = F.GAMES[key]
+    for k in F.EFFECTS:
+        assert sum(w["effects"][k] for w in on) > 0, (key, k)
+        assert not any(w["effects"][k] for w in off), (key, k)
+    for i, (a, b) in enumerate(zip(on, off)):
+        assert a["actions"] != b["actions"] or [p["recorded"] for p in a["plies"]] != [p["recorded"] for p in b["plies"]], (key, i)
+    plies = [p for w in on for p in w["plies"]]
+    if "cap" in c:
+        assert {p["full"] for p in plies} == {True, False}
+    if "forced" in c:
+        assert any(p["raw"] != p["recorded"] for p in plies)            # pruning took visits out of a recorded row
+    if "mirror" in c:
+        assert min(sum(w["mirrored"][k] for w in on) for k in (0, 1)) >= 10
+    if c.get("solver"):
+        assert any(p["status"] != SC.UNKNOWN and p["ran"] < F.S for p in plies)   # a search ended early at a proven root
+    if key == "chained":
+        assert sum(w["counters"]["terminal_hits"] for w in on) > 0
+
+
+def test_a_zero_reduction_is_not_the_reference():
+    c = F.SEARCHES["c4_deep"]
+    kw = dict(n_playouts=c["n_playouts"], use_dirichlet=False, backup="soft-Z", num_probabilistic_actions=0, start=c["start"],
+              max_searches=1)
+    zero = F.play_game(c["game"], c["salt"], None, None, fpu=(0.0, 0.0), **kw)
+    none = F.play_game(c["game"], c["salt"], None, None, fpu=None, **kw)
+    assert zero["plies"][0]["raw"] != none["plies"][0]["raw"] and any(zero["effects"].values())
+
+
+# ------------------------------------------------------------------------------------------------ 4. ABI and facade
+def test_abi_surface():
+    protos = {name: (res, args) for name, res, args in _lib.PROTOTYPES}
+    assert protos["az_engine_set_fpu"] == (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double])
+    header = open(os.path.join(ROOT, "include", "az_engine.h")).read()
+    assert re.search(r"int az_engine_set_fpu\(az_engine \*e, int32_t on, double reduction, double reduction_root\);", header)
+    lib = _lib.load()                                                    # (raises if the library lacks a declared symbol)
+    assert lib.az_engine_set_fpu.argtypes == protos["az_engine_set_fpu"][1] and lib.az_engine_set_fpu.restype == C.c_int
+    assert C.sizeof(_lib.AzConfig) == 152                                # az_config does not change
+
+
+def test_fpu_pair_validates():
+    from alphazero_openspiel_amd.engine import fpu_pair
+    assert fpu_pair(0.3) == (0.3, 0.0) and fpu_pair((0.3, 0.1)) == (0.3, 0.1) and fpu_pair([0, 1]) == (0.0, 1.0)
+    assert fpu_pair(np.float64(0.25)) == (0.25, 0.0)
+    for bad in (-0.1, (0.3, -1.0), float("nan"), (0.3, float("inf")), (0.3,), (0.1, 0.2, 0.3), "0.3", (0.3, None), True):
+        with pytest.raises(ValueError, match="fpu"):
+            fpu_pair(bad)
+
+
+def test_example_generator_takes_and_refuses_the_setting():
+    from alphazero_openspiel_amd.examplegenerator import ExampleGenerator
+    net = torch.nn.Identity()
+    kw = dict(n_playouts=24)                                             # (no device is touched before a generation is asked for)
+    assert ExampleGenerator(net, "connect_four", "cuda:0", fpu=0.3, **kw).fpu == (0.3, 0.0)
+    assert ExampleGenerator(net, "connect_four", "cuda:0", fpu=(0.3, 0.1), **kw).fpu == (0.3, 0.1)
+    assert ExampleGenerator(net, "connect_four", "cuda:0", **kw).fpu is None
+    for ok in (dict(continuous=True), dict(n_pools=2), dict(playout_cap=(6, 0.5)), dict(eval_mirror=0.5), dict(solver=True),
+               dict(forced_playouts=2.0), dict(overlap=2)):
+        assert ExampleGenerator(net, "connect_four", "cuda:0", fpu=(0.3, 0.1), **kw, **ok).fpu == (0.3, 0.1)
+    for bad in (-1.0, (0.3, float("nan")), (0.1, 0.2, 0.3), "x"):
+        with pytest.raises(ValueError, match="fpu"):
+            ExampleGenerator(net, "connect_four", "cuda:0", fpu=bad, **kw)
+    with pytest.raises(ValueError, match="fpu.*is_test=True"):
+        ExampleGenerator(net, "connect_four", "cuda:0", fpu=0.3, is_test=True, **kw)
+    with pytest.raises(ValueError, match="fpu.*use_puct=False"):
+        ExampleGenerator(net, "connect_four", "cuda:0", fpu=0.3, use_puct=False, **kw)
