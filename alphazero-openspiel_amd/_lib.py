@@ -65,6 +65,11 @@ class AzSlotInfo(C.Structure):
                 ("leaf_ply", C.c_int32), ("depth", C.c_int32)]
 
 
+class AzArenaSearch(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("fpu_on", C.c_int32), ("fpu_reduction", C.c_double),
+                ("fpu_reduction_root", C.c_double), ("solver", C.c_int32), ("reserved", C.c_int32), ("p_mirror", C.c_double)]
+
+
 class AzNetDesc(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("in_planes", C.c_int32),
                 ("n_filters", C.c_int32), ("n_blocks", C.c_int32), ("num_actions", C.c_int32), ("device", C.c_int32),
@@ -118,6 +123,8 @@ PROTOTYPES = [
     ("az_engine_read_request_mirror", C.c_int, [_vp, C.c_int32]),
     ("az_engine_set_solver", C.c_int, [_vp, C.c_int32]),
     ("az_engine_set_fpu", C.c_int, [_vp, C.c_int32, C.c_double, C.c_double]),
+    ("az_engine_set_arena_search", C.c_int, [_vp, C.POINTER(AzArenaSearch)]),
+    ("az_engine_set_arena_openings", C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.c_int64]),
     ("az_engine_read_proofs", C.c_int64, [_vp, C.c_int32, C.POINTER(C.c_int8), C.c_int64]),
     ("az_engine_proofs_device_bytes", C.c_int64, [_vp]),
     ("az_engine_export_proofs_device", C.c_int, [_vp, _vp, C.c_int64, _vp]),

@@ -1650,11 +1650,12 @@ __global__ void az_reset_kernel(Params p) {
     int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= p.G) return;
     bool active = (long long)g < p.n_games;
+    const AzState s0 = (p.starts && active) ? p.starts[g] : p.start; // game id g: its own start when a table is set
+    // arena: who moves first follows from the game's OWN start ply (az_engine_set_arena_openings), as opponent_to_move does later
     p.phase[g] = !active ? PH_IDLE
-                 : ((p.arena_agent != AZ_ARENA_SELF_PLAY && ((p.start.ply ^ g ^ p.arena_flip) & 1)) ? PH_OPPONENT
-                                                                                       : (p.use_dirichlet ? PH_NEED_ROOT : PH_RUN));
+                 : ((p.arena_agent != AZ_ARENA_SELF_PLAY && ((s0.ply ^ g ^ p.arena_flip) & 1)) ? PH_OPPONENT
+                                                                                  : (p.use_dirichlet ? PH_NEED_ROOT : PH_RUN));
     p.gid[g] = active ? g : -1;
-    const AzState s0 = (p.starts && active) ? p.starts[g] : p.start; // game id g (a table is never set on an arena engine: the phase above)
     p.bb0[g] = s0.bb0;
     p.bb1[g] = s0.bb1;
     p.ply[g] = s0.ply;
@@ -2291,6 +2292,49 @@ extern "C" int az_engine_set_eval_mirror(az_engine *e, double p_mirror) {
     return AZ_OK;
 }
 
+// ---- search settings of an arena agent (include/az_engine.h: az_engine_set_arena_search) ------------------------------------------
+// The Params fields are the three setters' own, so launch_tick picks the instantiation as it does for them; the FPU, SOLVER and
+// MIRROR instantiations of az_advance_kernel carry the arena paths (PH_OPP_DONE, the agent's move, re-rooting across both
+// players' moves) like the plain one.
+extern "C" int az_engine_set_arena_search(az_engine *e, const az_arena_search *s) {
+    if (!e) return AZ_E_INVALID;
+    const char *why = nullptr;
+    if (e->cfg.manual_moves) why = "a manual_moves engine (az_engine_set_fpu / _set_solver / _set_eval_mirror are its entries)";
+    else if (e->p.arena_agent == AZ_ARENA_SELF_PLAY) why = "a self-play engine (az_engine_set_fpu / _set_solver / _set_eval_mirror are its entries)";
+    else if (e->p.arena_agent == AZ_ARENA_NET) why = "an AZ_ARENA_NET agent (it searches nothing: one evaluation, the argmax of the priors)";
+    else if (e->cfg.select_rule != AZ_SELECT_PUCT) why = "select_rule = AZ_SELECT_UCT (first-play urgency and the solver's select rule are stated for the PUCT value)";
+    if (why) {
+        e->err = std::string("az_engine_set_arena_search is for AZ_ARENA_ZERO agents under the PUCT rule: refused for ") + why;
+        return AZ_E_INVALID;
+    }
+    az_arena_search off = {(int32_t)sizeof(az_arena_search), 0, 0.0, 0.0, 0, 0, 0.0};
+    if (!s) s = &off; // NULL clears
+    if (s->struct_size != (int32_t)sizeof(az_arena_search)) {
+        e->err = "az_engine_set_arena_search: az_arena_search.struct_size mismatch (header/library skew): got " +
+                 std::to_string(s->struct_size) + ", expected " + std::to_string(sizeof(az_arena_search));
+        return AZ_E_INVALID;
+    }
+    const double dmax = 1.7976931348623157e308;
+    if (s->fpu_on && !(s->fpu_reduction >= 0.0 && s->fpu_reduction <= dmax && s->fpu_reduction_root >= 0.0 &&
+                       s->fpu_reduction_root <= dmax)) { // (the negated form takes NaN too)
+        e->err = "az_engine_set_arena_search: fpu_reduction and fpu_reduction_root must be finite and >= 0 (fpu_on = 0 clears the setting)";
+        return AZ_E_INVALID;
+    }
+    if (!(s->p_mirror >= 0.0 && s->p_mirror <= 1.0)) { // (the negated form takes NaN too)
+        e->err = "az_engine_set_arena_search: p_mirror must be finite and in [0, 1] (0 clears the setting)";
+        return AZ_E_INVALID;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, hipDeviceSynchronize()); // games that still play were launched under the old settings
+    e->p.fpu_on = s->fpu_on ? 1 : 0;
+    e->p.fpu_reduction = s->fpu_on ? s->fpu_reduction : 0.0;
+    e->p.fpu_reduction_root = s->fpu_on ? s->fpu_reduction_root : 0.0;
+    e->p.solver = s->solver ? 1 : 0;
+    e->p.p_mirror = s->p_mirror;
+    e->reset_done = false; // the caller starts the games next (az_engine_reset)
+    return AZ_OK;
+}
+
 // The tick kernel's instantiation for the settings in force (az_engine_set_forced_playouts, az_engine_set_eval_mirror,
 // az_engine_set_solver, az_engine_set_fpu: each its own instantiations; with none set the engine launches the kernel without any of
 // the features).
@@ -2513,6 +2557,18 @@ extern "C" int az_engine_exchange_moves(az_engine *a, az_engine *b, void *stream
         a->err = "az_engine_exchange_moves before az_engine_reset";
         return AZ_E_STATE;
     }
+    // openings per game (az_engine_set_arena_openings): slot g of both engines plays ONE game, so both start it at the same ply
+    if (start_table_n(a) != start_table_n(b)) {
+        a->err = "az_engine_exchange_moves: the engines' opening tables differ in length (" + std::to_string(start_table_n(a)) + " and " +
+                 std::to_string(start_table_n(b)) + " games): give both the same az_engine_set_arena_openings table";
+        return AZ_E_STATE;
+    }
+    for (int64_t g = 0; start_table_n(a) && g < a->n_games; g++) // (host words only; without a table nothing is compared, as before)
+        if (start_ply_of(a, g) != start_ply_of(b, g)) {
+            a->err = "az_engine_exchange_moves: the engines' openings differ: game " + std::to_string(g) + " starts at ply " +
+                     std::to_string(start_ply_of(a, g)) + " and at ply " + std::to_string(start_ply_of(b, g));
+            return AZ_E_STATE;
+        }
     HIPCHK(a, hipSetDevice(a->cfg.device));
     hipLaunchKernelGGL(az_exchange_kernel, dim3((a->p.G + 255) / 256), dim3(256), 0, (hipStream_t)stream, a->p, b->p);
     HIPCHK(a, hipGetLastError());

@@ -130,7 +130,8 @@ struct Params {
     double *rec_value;
     // start position per GAME ID: null = every game starts from `start`.  Set for manual_moves engines by
     // az_engine_set_start_positions / az_engine_set_start_states_device, for plain self-play engines by az_engine_set_game_starts /
-    // az_engine_set_game_starts_device.  Read by game id at reset, at take-next and at game end only - never per tick.
+    // az_engine_set_game_starts_device, for arena engines by az_engine_set_arena_openings.  Read by game id at reset, at take-next
+    // and at game end only - never per tick.
     const AzState *starts;
     // playout cap randomisation (az_engine_set_playout_cap): null = none.  One pointer (Params grows by 8 bytes); only the cold
     // paths (reset, move_step, the read-backs) follow it.  Register figures of the tick kernel: DESIGN.md section 4.
@@ -161,7 +162,8 @@ static inline AzRecords records_of(const Params &p) {
 enum StartKind {
     START_UNIFORM = 0,  // every game starts from Params::start (Params::starts is null); prefixed: a non-empty prefix gave it
     START_PER_POSITION, // manual_moves engines (az_engine_set_start_positions / _start_states_device): Params::starts = states
-    START_PER_GAME,     // plain self-play engines (az_engine_set_game_starts / _device): the same, and plies, keys, h_plies count
+    START_PER_GAME,     // plain self-play engines (az_engine_set_game_starts / _device) and arena engines
+                        // (az_engine_set_arena_openings): the same, and plies, keys, h_plies count
 };
 struct StartTable {
     StartKind kind = START_UNIFORM;

@@ -3,7 +3,8 @@
 //
 // One prefix for every game (az_engine_set_start_prefix), or a table by game id in device memory: for manual_moves engines
 // (az_engine_set_start_positions / az_engine_set_start_states_device) and, with each game's start ply and history key pair beside
-// its state, for plain self-play engines (az_engine_set_game_starts / az_engine_set_game_starts_device).  A table comes in a host
+// its state, for plain self-play engines (az_engine_set_game_starts / az_engine_set_game_starts_device) and for arena engines
+// (az_engine_set_arena_openings).  A table comes in a host
 // form (an action prefix per game, replayed by az_starts.h) or a device form (states, checked on the device); each form has one
 // install routine, and starts_in_force is the one place that says which kind of start holds.  A refused call changes nothing.
 #include "az_engine_internal.h"
@@ -219,6 +220,21 @@ extern "C" int az_engine_set_game_starts_device(az_engine *e, const uint64_t *bb
     if (!e) return AZ_E_INVALID;
     if (game_starts_refusal(e, "az_engine_set_game_starts_device")) return AZ_E_INVALID;
     return install_starts_device(e, "az_engine_set_game_starts_device", START_PER_GAME, bb_dev, ply_dev, keys_dev, n_games, stream);
+}
+
+// An opening per evaluation game: the same START_PER_GAME table on an arena engine (both agent kinds, every opponent kind).  The
+// kernels read a game's start where they read a self-play table's - at reset, at take-next and at game end - and who moves first
+// follows from the game's own ply (az_reset_kernel, opponent_to_move).
+extern "C" int az_engine_set_arena_openings(az_engine *e, const int32_t *actions, const int32_t *lengths, int64_t stride, int64_t n_games) {
+    if (!e) return AZ_E_INVALID;
+    const char *why = nullptr;
+    if (e->cfg.manual_moves) why = "a manual_moves engine (az_engine_set_start_positions / az_engine_set_start_states_device are its entries)";
+    else if (e->p.arena_agent == AZ_ARENA_SELF_PLAY) why = "a self-play engine (az_engine_set_game_starts / az_engine_set_game_starts_device are its entries)";
+    if (why) {
+        e->err = std::string("az_engine_set_arena_openings is for arena engines: refused for ") + why;
+        return AZ_E_INVALID;
+    }
+    return install_starts_host(e, "az_engine_set_arena_openings", START_PER_GAME, actions, lengths, stride, n_games);
 }
 
 // ---- read-back: every game id's start ply and key pair ---------------------------------------------------------------------------

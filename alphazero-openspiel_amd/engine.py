@@ -94,6 +94,7 @@ class SelfPlayEngine:
         self.eval_mirror = None      # set_eval_mirror: p_mirror while the setting is in force
         self.solver = False          # set_solver: True while the setting is in force
         self.fpu = None              # set_fpu: (reduction, root reduction) while the setting is in force
+        self.arena_search = None     # set_arena_search: dict(fpu=, solver=, eval_mirror=) while an arena agent carries a setting
         self.n_games = 0
 
     # ------------------------------------------------------------------ plumbing
@@ -257,6 +258,36 @@ class SelfPlayEngine:
         afterwards."""
         self._check(self.lib.az_engine_set_fpu(self._h, 0, 0.0, 0.0))
         self.fpu = None
+
+    def set_arena_search(self, fpu=None, solver=False, eval_mirror=0.0):
+        """Search settings of an arena AGENT (az_engine_set_arena_search): from the next reset() on the "zero" agent of an
+        evaluation engine searches with first-play urgency (fpu=r or (r, r_root), as set_fpu), the MCTS-Solver (solver=True, as
+        set_solver; a won root plays a proven win, a drawn root never a proven loss) and / or the evaluation mirror (eval_mirror=p,
+        as set_eval_mirror) - what a match between two settings needs (arena.play_match).  Arena engines with agent "zero" under
+        use_puct only (EngineError names the reason otherwise); set_arena_search() with nothing on clears all three.  reset()
+        afterwards."""
+        rec = _lib.AzArenaSearch()
+        rec.struct_size = C.sizeof(_lib.AzArenaSearch)
+        pair = None if fpu is None else fpu_pair(fpu)
+        rec.fpu_on = int(pair is not None)
+        rec.fpu_reduction, rec.fpu_reduction_root = pair if pair is not None else (0.0, 0.0)
+        rec.solver = int(bool(solver))
+        rec.p_mirror = float(eval_mirror or 0.0)
+        self._check(self.lib.az_engine_set_arena_search(self._h, C.byref(rec)))
+        on = pair is not None or bool(solver) or rec.p_mirror > 0.0
+        self.arena_search = dict(fpu=pair, solver=bool(solver), eval_mirror=rec.p_mirror) if on else None
+
+    def set_arena_openings(self, prefixes):
+        """An opening per evaluation game (az_engine_set_arena_openings): game i of the next reset() starts after the action list
+        prefixes[i]; the agent still plays player (i & 1) ^ arena_flip, whatever the opening's length.  Arena engines only.  An
+        illegal action or a prefix that ends the game raises EngineError naming "game <i>" and an earlier table stays in force;
+        reset(n <= len(prefixes)) afterwards; set_start_prefix returns to one start.  Both engines of a duel take the same list.
+        export() then returns "start_ply" as an int32 array (game_starts)."""
+        actions, lengths, stride = pack_histories(prefixes)
+        ip = C.POINTER(C.c_int32)
+        self._check(self.lib.az_engine_set_arena_openings(self._h, actions.ctypes.data_as(ip), lengths.ctypes.data_as(ip),
+                                                          stride, len(lengths)))
+        self._starts(histories=prefixes, game_starts=lengths.copy())
 
     def read_proofs(self, slot):
         """The proof status of every node of a slot's tree in the order of read_tree() (az_engine_read_proofs) -> int8 array:

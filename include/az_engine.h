@@ -261,7 +261,8 @@ int az_engine_set_start_states_device(az_engine *e, const uint64_t *bb_dev, cons
  * The companion of az_engine_export_device (whose layout does not change) for az_replay_append_device_starts.  Returns 1 when
  * the table carries GIVEN pairs (pass them on as keys_dev there), 0 when it does not (pass NULL), < 0 on error.
  *
- * Limits: no opening per game on arena engines, no table in stream mode, and the multi-rank gather carries one start ply.
+ * Limits: no table in stream mode, and the multi-rank gather carries one start ply.  Arena engines take their openings per game
+ * through az_engine_set_arena_openings (below).
  */
 int az_engine_set_game_starts(az_engine *e, const int32_t *actions, const int32_t *lengths, int64_t stride, int64_t n_games);
 int az_engine_set_game_starts_device(az_engine *e, const uint64_t *bb_dev, const int32_t *ply_dev, const uint64_t *keys_dev,
@@ -356,7 +357,8 @@ int az_engine_set_forced_playouts(az_engine *e, double k, int32_t prune);
  *   force.  AZ_E_STATE when the slot is not in phase 3 or 4 (or before az_engine_reset), AZ_E_INVALID for a bad slot.  Host code
  *   only: no kernel runs.  Synchronises the device as az_engine_read_slot.
  *
- * Limits: one orientation per request, not the average of both (two evaluations per request: another feature); no arena engines.
+ * Limits: one orientation per request, not the average of both (two evaluations per request: another feature).  An arena agent takes
+ *   the setting through az_engine_set_arena_search (below), which is how its effect on playing strength is measured.
  */
 int az_engine_set_eval_mirror(az_engine *e, double p_mirror);
 int az_engine_read_request_mirror(az_engine *e, int32_t slot);
@@ -401,7 +403,8 @@ int az_engine_read_request_mirror(az_engine *e, int32_t slot);
  *   graph-capturable; it sits beside az_engine_export_roots_device, whose layout does not change.
  *
  * Limits: win / draw / loss only (no score bounds), no preference for the shortest win or the longest loss, no forced playouts, no
- *   arena agents, no UCT rule.
+ *   UCT rule.  An arena agent takes the setting through az_engine_set_arena_search (below), which is how its effect on playing
+ *   strength is measured.
  */
 #define AZ_PROOF_UNKNOWN 0
 #define AZ_PROOF_WIN 1
@@ -446,10 +449,58 @@ int az_engine_export_proofs_device(az_engine *e, void *dev_buf, int64_t bytes, v
  *   prefix, both start tables, a playout cap, forced playouts, the evaluation mirror, the solver and keep_search_tree.  Records,
  *   exports, pools, ranks and the replay store do not change.
  *
- * Limits: no arena agents (so playing strength is not measured here), no UCT rule, no separate treatment of the fast moves of a
- *   playout cap.  Lc0 and KataGo use values around 0.2 to 0.4 below the root and 0 at a noised root; unmeasured here.
+ * Limits: no UCT rule, no separate treatment of the fast moves of a playout cap.  An arena agent takes the setting through
+ *   az_engine_set_arena_search (below), which is how its effect on playing strength is measured (Lc0 and KataGo use values around
+ *   0.2 to 0.4 below the root and 0 at a noised root; the matches played here are in DESIGN_HISTORY.md).
  */
 int az_engine_set_fpu(az_engine *e, int32_t on, double reduction, double reduction_root);
+
+/*
+ * Arena matches between search settings: an evaluation game whose AGENT searches with first-play urgency, the MCTS-Solver or the
+ * evaluation mirror, and evaluation games that start from a position per game.  Engine A plays setting X, engine B setting Y
+ * (az_engine_exchange_moves), over N openings each played twice with the colours swapped: what measures whether a setting plays
+ * better.  az_engine_set_fpu / _set_solver / _set_eval_mirror / _set_game_starts keep refusing arena engines (an arena engine with
+ * none of the calls below measures the reference's search); these two entries accept arena engines ONLY.
+ *
+ * az_engine_set_arena_search: AZ_ARENA_ZERO agents, every opponent kind (AZ_OPPONENT_EXTERNAL included).  AZ_E_INVALID, with the
+ *   reason in az_last_error, for a self-play engine or a manual_moves engine (they have their own setters), for AZ_ARENA_NET (it
+ *   searches nothing) and for select_rule == AZ_SELECT_UCT.  s == NULL, or a record with fpu_on == 0, solver == 0 and
+ *   p_mirror == 0, clears all three.  struct_size must be sizeof(az_arena_search); `reserved` is not looked at.  The value checks
+ *   are those of the three setters and apply to a setting that is on: fpu_reduction and fpu_reduction_root finite and >= 0 with
+ *   fpu_on != 0; p_mirror in [0, 1], NaN refused.  On a refusal nothing changes.  Synchronises the device; the caller resets next.
+ *   The rules are the ones stated above, word for word: FPU acts at every select level of the agent's tree; the mirror's coins are
+ *   purposes 4 and 5 keyed by (seed, game id, root ply, ...) - the two engines of a duel have their own seeds and so their own
+ *   coins; solver rules 1-5 and 7 apply unchanged, and a kept subtree that is already proven when the opponent's move re-roots
+ *   onto it ends its search at once.  Rule 6 applies to the AGENT's move: the counts are adjusted before the move is drawn, and
+ *   the argmax (or, under arena_probabilistic, the sample) runs on the adjusted counts - a won root plays a proven win, the first
+ *   of the most visited among them; a drawn root never plays a proven loss; a lost root plays as before.  (The argmax is the first
+ *   maximum of the tempered fractions of the ADJUSTED counts: when every remaining count is tied it is the lowest such action; a
+ *   child whose count became 0 has fraction 0 and cannot be the maximum while another count is positive - and one is: a WIN child
+ *   was visited when it was proven, and a drawn root has a child that is not LOSS, visited likewise.)  az_engine_read_proofs and
+ *   az_engine_export_proofs_device work on arena engines.  Playout cap and forced playouts stay refused there.  With the entry
+ *   never called, or cleared, every arena launch is the kernel instantiation it was before, bit for bit.
+ *
+ * az_engine_set_arena_openings: the arguments, the host replay and the legality checks of az_engine_set_game_starts (an illegal
+ *   action or a prefix that ends the game -> AZ_E_INVALID naming "game <i>", the earlier table stays in force; az_engine_reset with
+ *   more games than the table holds is refused), for arena engines of both agent kinds and every opponent kind; self-play and
+ *   manual_moves engines are refused.  It supersedes a prefix, and az_engine_set_start_prefix clears it.  The agent of game i plays
+ *   player (i & 1) ^ arena_flip whatever the opening's length is (the rule (ply ^ i ^ arena_flip) & 1 on the ABSOLUTE ply): who
+ *   moves first in game i follows from its own start ply, at reset and when a slot takes a later id.  A kept tree's first rule is
+ *   decided from the game's own ply (an arena bot calls update_root with >= 2 moves played).  Records stay indexed by absolute
+ *   ply, game_len counts from the game's own start, and az_engine_game_starts_device answers for arena engines too.  Both engines
+ *   of a duel take the same table: az_engine_exchange_moves refuses (AZ_E_STATE) a pair whose tables differ in length or in any
+ *   start ply.
+ */
+typedef struct az_arena_search {
+    int32_t struct_size;            /* = sizeof(az_arena_search); ABI guard, as az_config */
+    int32_t fpu_on;                 /* the arguments of az_engine_set_fpu */
+    double  fpu_reduction, fpu_reduction_root;
+    int32_t solver;                 /* az_engine_set_solver */
+    int32_t reserved;
+    double  p_mirror;               /* az_engine_set_eval_mirror; 0 = off */
+} az_arena_search;
+int az_engine_set_arena_search(az_engine *e, const az_arena_search *s);
+int az_engine_set_arena_openings(az_engine *e, const int32_t *actions, const int32_t *lengths, int64_t stride, int64_t n_games);
 
 /*
  * One tick = MCTS.playout's select + expand + backup (mcts.py:126-153) for all slots, fused with the
