@@ -16,8 +16,8 @@ field of every root with `==`), and with the fused network at f32x the result do
 import numpy as np
 import torch
 
-from .engine import (DeviceEvaluator, EngineError, HostPolicyEvaluator, SelfPlayEngine, TickDriver, close_all, default_device,
-                     fpu_pair, make_evaluator, read_lines)
+from .engine import (DeviceEvaluator, EngineError, HostPolicyEvaluator, SearchSettings, SelfPlayEngine, TickDriver, close_all, default_device,
+                     make_evaluator, read_lines)
 from .games import Game, State
 
 PHASE_IDLE, PHASE_SEARCH_DONE = 0, 5
@@ -88,7 +88,8 @@ class Analyzer:
     def __init__(self, policy_fn, game_name, n_slots, n_playouts=100, c_puct=2.5, use_dirichlet=False, device=None,
                  eval_backend="fused", eval_precision="f32x", seed=None, check_every=16, pv_depth=0, eval_mirror=None, solver=False,
                  fpu=None, **kwargs):
-        fpu = None if fpu is None else fpu_pair(fpu)
+        # (solver=False is this signature's "not named"; eval_mirror=0 is named and clears)
+        settings = SearchSettings.from_kwargs(dict(eval_mirror=eval_mirror, solver=solver or None, fpu=fpu), off="clear")
         if int(n_slots) < 1:
             raise ValueError("n_slots must be positive")
         if int(check_every) < 1:
@@ -105,13 +106,8 @@ class Analyzer:
         self.evaluator, self._owns_evaluator = None, False
         self._eval_backend, self._eval_precision = eval_backend, eval_precision
         try:
-            if eval_mirror is not None:
-                self.engine.set_eval_mirror(eval_mirror)
-            self.solver = bool(solver)
-            if self.solver:
-                self.engine.set_solver(True)
-            if fpu is not None:
-                self.engine.set_fpu(*fpu)
+            self.solver = bool(settings.solver)
+            settings.apply(self.engine)
             if policy_fn is not None:
                 self.evaluator, self._owns_evaluator = _make_evaluator(policy_fn, self.engine.device, eval_backend,
                                                                        eval_precision, int(n_slots))

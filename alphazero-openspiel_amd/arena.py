@@ -23,19 +23,18 @@ import math
 import numpy as np
 import torch
 
-from .engine import EngineError, SelfPlayEngine, TickDriver, close_all, default_device, make_evaluator, tick_until
+from .engine import EngineError, SearchSettings, SelfPlayEngine, TickDriver, close_all, default_device, make_evaluator, tick_until
 from .games import load_game
+from .search_settings import ARENA_KEYS
 
 ENGINE_KW = ("n_playouts", "c_puct", "temperature", "keep_search_tree", "use_puct", "use_probabilistic_actions",
               "num_probabilistic_actions")
-SEARCH_KW = ("fpu", "solver", "eval_mirror")  # SelfPlayEngine.set_arena_search: the settings an arena agent may carry
+SEARCH_KW = ARENA_KEYS  # SelfPlayEngine.set_arena_search: the settings an arena agent may carry
 
 
 def _apply_search(engine, settings, openings):
     """set_arena_search / set_arena_openings for what `settings` (a dict) and `openings` name; nothing named, nothing called."""
-    kw = {k: settings[k] for k in SEARCH_KW if settings.get(k) is not None}
-    if kw.get("fpu") is not None or kw.get("solver") or kw.get("eval_mirror"):
-        engine.set_arena_search(**kw)
+    SearchSettings.from_kwargs({k: settings.get(k) for k in SEARCH_KW}).apply_arena(engine)
     if openings is not None:
         engine.set_arena_openings(openings)
 

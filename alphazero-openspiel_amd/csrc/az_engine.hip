@@ -25,6 +25,7 @@
 #include <string.h>
 
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/az_engine.h"
@@ -2129,57 +2130,6 @@ extern "C" int az_engine_set_injected_rng(az_engine *e, const double *etas, cons
     return AZ_OK;
 }
 
-// ---- playout cap randomisation (include/az_engine.h: az_engine_set_playout_cap) ------------------------------------------------
-extern "C" int az_engine_set_playout_cap(az_engine *e, int32_t n_fast, double p_full) {
-    if (!e) return AZ_E_INVALID;
-    const char *why = nullptr;
-    if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) why = "an arena engine (every agent move of an evaluation game is a full search)";
-    else if (e->cfg.manual_moves) why = "a manual_moves engine (its caller arms every search)";
-    else if (e->streaming) why = "an engine in stream mode (az_engine_stream_begin: the mask does not travel with a take)";
-    if (why) {
-        e->err = std::string("az_engine_set_playout_cap is for plain self-play engines in a closed generation: refused for ") + why;
-        return AZ_E_INVALID;
-    }
-    if (n_fast != 0) {
-        if (n_fast < 1 || n_fast > e->cfg.n_playouts || (!e->cfg.use_dirichlet && n_fast < 2)) {
-            e->err = "az_engine_set_playout_cap: n_fast must be in [1, n_playouts = " + std::to_string(e->cfg.n_playouts) +
-                     "], and >= 2 without root Dirichlet expansion (mcts.py:162 divides by zero); 0 clears the cap";
-            return AZ_E_INVALID;
-        }
-        if (!(p_full >= 0.0 && p_full <= 1.0)) {
-            e->err = "az_engine_set_playout_cap: p_full must be in [0, 1]";
-            return AZ_E_INVALID;
-        }
-    }
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    HIPCHK(e, hipDeviceSynchronize()); // a generation that still plays may be reading the record
-    if (n_fast && !e->d_cap) { // the first cap: the device record, the slots' word, the schedule and the mask beside the records
-        const size_t G = (size_t)e->p.G, plies = (size_t)e->cfg.max_games * e->p.max_plies;
-        const size_t off_sched = (G * sizeof(int) + 15) & ~(size_t)15, off_full = (off_sched + plies + 15) & ~(size_t)15,
-                     off_rec = (off_full + plies + 15) & ~(size_t)15; // ONE block: nothing is held if it cannot be had or cleared
-        void *blk = nullptr;
-        hipError_t hs = hipMalloc(&blk, off_rec + sizeof(CapDev));
-        if (hs == hipSuccess) hs = hipMemset(blk, 0, off_rec + sizeof(CapDev));
-        if (hs != hipSuccess) {
-            if (blk) (void)hipFree(blk);
-            e->err = std::string("az_engine_set_playout_cap: ") + hipGetErrorString(hs);
-            return hs == hipErrorOutOfMemory ? AZ_E_NOMEM : AZ_E_HIP;
-        }
-        e->dev_allocs.push_back(blk);
-        e->sizes.device_bytes += (int64_t)(off_rec + sizeof(CapDev));
-        e->cap.sims_base = (int *)blk;
-        e->cap.sched = (uint8_t *)blk + off_sched;
-        e->cap.rec_full = (uint8_t *)blk + off_full;
-        e->d_cap = (CapDev *)((char *)blk + off_rec);
-    }
-    e->cap.n_fast = n_fast;
-    e->cap.p_full = n_fast ? p_full : 0.0;
-    if (e->d_cap) HIPCHK(e, hipMemcpy(e->d_cap, &e->cap, sizeof(CapDev), hipMemcpyHostToDevice));
-    e->p.capdev = n_fast ? e->d_cap : nullptr;
-    e->reset_done = false; // the slots' counters were armed under the old setting: the caller resets (az_engine_reset)
-    return AZ_OK;
-}
-
 // one thread per (game, absolute ply): 1 for a recorded ply whose search was a full one, 0 elsewhere
 __global__ void az_full_moves_kernel(const int *len, const uint8_t *rec_full, int start_ply, const int32_t *start_plies, long long n_games,
                                      int max_plies, uint8_t *out) {
@@ -2207,165 +2157,208 @@ extern "C" int az_engine_full_moves_device(az_engine *e, uint8_t *full_out_dev, 
     return e->p.capdev ? 1 : 0;
 }
 
-// ---- forced playouts and policy target pruning (include/az_engine.h: az_engine_set_forced_playouts) ----------------------------
+// ---- search settings: one record, one table of who may carry what, one install path ("Search settings") -------------
+// What the six public setters of include/az_engine.h put in force, as they take it: install_search normalises when it stores.
+// Params and the cap's CapDev ARE the storage (Params is the kernel argument and does not move); this is what a setter reads out
+// of them, edits and hands back.
+struct SearchState {
+    int32_t n_fast; // az_engine_set_playout_cap: 0 = no cap
+    double p_full;
+    double forced_k; // az_engine_set_forced_playouts: 0 = none
+    int32_t forced_prune;
+    int32_t solver; // az_engine_set_solver
+    int32_t fpu_on; // az_engine_set_fpu
+    double fpu_reduction, fpu_reduction_root;
+    double p_mirror; // az_engine_set_eval_mirror: 0 = none
+};
+
+// An engine is of exactly one of the first five kinds; KIND_UCT (select_rule = AZ_SELECT_UCT) is asked after that one.
+enum { KIND_SELF_CLOSED, KIND_SELF_STREAM, KIND_MANUAL, KIND_ARENA_ZERO, KIND_ARENA_NET, KIND_UCT, N_KINDS };
+enum { SET_CAP, SET_FORCED, SET_SOLVER, SET_FPU, SET_MIRROR, SET_ARENA, N_SETTERS };
+
+#define ARENA_REF "an arena engine (an evaluation game measures the reference's search)"
+#define ARENA_CAP "an arena engine (every agent move of an evaluation game is a full search)"
+#define ARENA_FORCED "an arena engine (an evaluation game records no policy target)"
+#define ARENA_MIRROR "an arena engine (an evaluation game measures the network as it is, in the one orientation its opponent's games are played in)"
+#define SELF_OWN "a self-play engine (az_engine_set_fpu / _set_solver / _set_eval_mirror are its entries)"
+// Settings against engine kinds: null = the kind may carry the setting, else why not (az_last_error: "<name> is for <who>: refused
+// for <why>").  fpu_: how the entry's own record spells the three FPU fields in its messages.
+static const struct SearchEntry {
+    const char *name, *who, *fpu_;
+    const char *refuse[N_KINDS];
+} SEARCH_ENTRIES[N_SETTERS] = {
+    {"az_engine_set_playout_cap", "plain self-play engines in a closed generation", "",
+     {nullptr, "an engine in stream mode (az_engine_stream_begin: the mask does not travel with a take)",
+      "a manual_moves engine (its caller arms every search)", ARENA_CAP, ARENA_CAP, nullptr}},
+    {"az_engine_set_forced_playouts", "plain PUCT self-play engines", "",
+     {nullptr, nullptr, "a manual_moves engine (analysis and reanalyse searches are read raw)", ARENA_FORCED, ARENA_FORCED,
+      "select_rule = AZ_SELECT_UCT (the forcing and pruning rules are stated for the PUCT value)"}},
+    {"az_engine_set_solver", "PUCT self-play and manual_moves engines", "",
+     {nullptr, nullptr, nullptr, ARENA_REF, ARENA_REF, "select_rule = AZ_SELECT_UCT (the solver's select rule is stated for the PUCT value)"}},
+    {"az_engine_set_fpu", "PUCT self-play and manual_moves engines", "",
+     {nullptr, nullptr, nullptr, ARENA_REF, ARENA_REF, "select_rule = AZ_SELECT_UCT (that rule already values an unvisited child at +infinity)"}},
+    {"az_engine_set_eval_mirror", "self-play and manual_moves engines", "", {nullptr, nullptr, nullptr, ARENA_MIRROR, ARENA_MIRROR, nullptr}},
+    {"az_engine_set_arena_search", "AZ_ARENA_ZERO agents under the PUCT rule", "fpu_",
+     {SELF_OWN, SELF_OWN, "a manual_moves engine (az_engine_set_fpu / _set_solver / _set_eval_mirror are its entries)", nullptr,
+      "an AZ_ARENA_NET agent (it searches nothing: one evaluation, the argmax of the priors)",
+      "select_rule = AZ_SELECT_UCT (first-play urgency and the solver's select rule are stated for the PUCT value)"}},
+};
+#undef ARENA_REF
+#undef ARENA_CAP
+#undef ARENA_FORCED
+#undef ARENA_MIRROR
+#undef SELF_OWN
+
+static int engine_kind(const az_engine *e) {
+    if (e->p.arena_agent == AZ_ARENA_NET) return KIND_ARENA_NET;
+    if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) return KIND_ARENA_ZERO;
+    if (e->cfg.manual_moves) return KIND_MANUAL;
+    return e->streaming ? KIND_SELF_STREAM : KIND_SELF_CLOSED;
+}
+
+// The body of every setter: `edit(SearchState &)` turns the state in force into the state the caller wants (and may refuse with a
+// message of its own, after the engine's kind has been passed).  In this order, and nowhere else: who may carry the setting, the
+// exclusions between settings, the values, the commit.  A refusal changes nothing.
+template <class Edit>
+static int install_search(az_engine *e, int which, Edit edit) {
+    if (!e) return AZ_E_INVALID;
+    const SearchEntry &t = SEARCH_ENTRIES[which];
+    const std::string name = t.name, refused = name + " is for " + t.who + ": refused for ";
+    const char *why = t.refuse[engine_kind(e)];
+    if (!why && e->cfg.select_rule != AZ_SELECT_PUCT) why = t.refuse[KIND_UCT];
+    if (why) {
+        e->err = refused + why;
+        return AZ_E_INVALID;
+    }
+    SearchState s = {e->cap.n_fast,   e->cap.p_full,         e->p.forced_k,           e->p.forced_prune, e->p.solver,
+                     e->p.fpu_on,     e->p.fpu_reduction,    e->p.fpu_reduction_root, e->p.p_mirror};
+    const int rc = edit(s);
+    if (rc != AZ_OK) return rc;
+    if (s.solver && s.forced_k > 0.0) { // the one exclusion: each entry names the other as the setting in force
+        e->err = refused + "an engine with " + SEARCH_ENTRIES[which == SET_SOLVER ? SET_FORCED : SET_SOLVER].name +
+                 " in force (forced playouts together with the solver are not built)";
+        return AZ_E_INVALID;
+    }
+    // the values (the negated comparisons take NaN too)
+    const double dmax = 1.7976931348623157e308;
+    if (s.n_fast != 0) {
+        if (s.n_fast < 1 || s.n_fast > e->cfg.n_playouts || (!e->cfg.use_dirichlet && s.n_fast < 2)) {
+            e->err = name + ": n_fast must be in [1, n_playouts = " + std::to_string(e->cfg.n_playouts) +
+                     "], and >= 2 without root Dirichlet expansion (mcts.py:162 divides by zero); 0 clears the cap";
+            return AZ_E_INVALID;
+        }
+        if (!(s.p_full >= 0.0 && s.p_full <= 1.0)) {
+            e->err = name + ": p_full must be in [0, 1]";
+            return AZ_E_INVALID;
+        }
+    }
+    if (!(s.forced_k >= 0.0 && s.forced_k <= dmax) || (s.forced_prune != 0 && s.forced_prune != 1)) {
+        e->err = name + ": k must be finite and >= 0 (0 clears the setting), prune 0 or 1";
+        return AZ_E_INVALID;
+    }
+    if (s.fpu_on && !(s.fpu_reduction >= 0.0 && s.fpu_reduction <= dmax && s.fpu_reduction_root >= 0.0 && s.fpu_reduction_root <= dmax)) {
+        e->err = name + ": " + t.fpu_ + "reduction and " + t.fpu_ + "reduction_root must be finite and >= 0 (" + t.fpu_ + "on = 0 clears the setting)";
+        return AZ_E_INVALID;
+    }
+    if (!(s.p_mirror >= 0.0 && s.p_mirror <= 1.0)) {
+        e->err = name + ": p_mirror must be finite and in [0, 1] (0 clears the setting)";
+        return AZ_E_INVALID;
+    }
+    // the commit
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    HIPCHK(e, hipDeviceSynchronize()); // a generation that still plays was launched under the old settings and may be reading the cap
+    if (s.n_fast && !e->d_cap) { // the first cap: the device record, the slots' word, the schedule and the mask beside the records
+        const size_t G = (size_t)e->p.G, plies = (size_t)e->cfg.max_games * e->p.max_plies;
+        const size_t off_sched = (G * sizeof(int) + 15) & ~(size_t)15, off_full = (off_sched + plies + 15) & ~(size_t)15,
+                     off_rec = (off_full + plies + 15) & ~(size_t)15; // ONE block: nothing is held if it cannot be had or cleared
+        void *blk = nullptr;
+        hipError_t hs = hipMalloc(&blk, off_rec + sizeof(CapDev));
+        if (hs == hipSuccess) hs = hipMemset(blk, 0, off_rec + sizeof(CapDev));
+        if (hs != hipSuccess) {
+            if (blk) (void)hipFree(blk);
+            e->err = name + ": " + hipGetErrorString(hs);
+            return hs == hipErrorOutOfMemory ? AZ_E_NOMEM : AZ_E_HIP;
+        }
+        e->dev_allocs.push_back(blk);
+        e->sizes.device_bytes += (int64_t)(off_rec + sizeof(CapDev));
+        e->cap.sims_base = (int *)blk;
+        e->cap.sched = (uint8_t *)blk + off_sched;
+        e->cap.rec_full = (uint8_t *)blk + off_full;
+        e->d_cap = (CapDev *)((char *)blk + off_rec);
+    }
+    e->cap.n_fast = s.n_fast;
+    e->cap.p_full = s.n_fast ? s.p_full : 0.0;
+    if (e->d_cap) HIPCHK(e, hipMemcpy(e->d_cap, &e->cap, sizeof(CapDev), hipMemcpyHostToDevice));
+    e->p.capdev = s.n_fast ? e->d_cap : nullptr;
+    e->p.forced_k = s.forced_k;
+    e->p.forced_prune = s.forced_k > 0.0 ? s.forced_prune : 0;
+    e->p.solver = s.solver ? 1 : 0;
+    e->p.fpu_on = s.fpu_on ? 1 : 0;
+    e->p.fpu_reduction = s.fpu_on ? s.fpu_reduction : 0.0;
+    e->p.fpu_reduction_root = s.fpu_on ? s.fpu_reduction_root : 0.0;
+    e->p.p_mirror = s.p_mirror;
+    e->reset_done = false; // the slots were armed under the old settings: the caller starts a generation next (az_engine_reset /
+                           // az_engine_stream_begin)
+    return AZ_OK;
+}
+
+extern "C" int az_engine_set_playout_cap(az_engine *e, int32_t n_fast, double p_full) {
+    return install_search(e, SET_CAP, [&](SearchState &s) { s.n_fast = n_fast; s.p_full = p_full; return AZ_OK; });
+}
+
 extern "C" int az_engine_set_forced_playouts(az_engine *e, double k, int32_t prune) {
-    if (!e) return AZ_E_INVALID;
-    const char *why = nullptr;
-    if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) why = "an arena engine (an evaluation game records no policy target)";
-    else if (e->cfg.manual_moves) why = "a manual_moves engine (analysis and reanalyse searches are read raw)";
-    else if (e->cfg.select_rule != AZ_SELECT_PUCT) why = "select_rule = AZ_SELECT_UCT (the forcing and pruning rules are stated for the PUCT value)";
-    else if (e->p.solver && k > 0.0) why = "an engine with az_engine_set_solver in force (forced playouts together with the solver are not built)";
-    if (why) {
-        e->err = std::string("az_engine_set_forced_playouts is for plain PUCT self-play engines: refused for ") + why;
-        return AZ_E_INVALID;
-    }
-    if (!(k >= 0.0 && k <= 1.7976931348623157e308) || (prune != 0 && prune != 1)) { // (the negated form takes NaN too)
-        e->err = "az_engine_set_forced_playouts: k must be finite and >= 0 (0 clears the setting), prune 0 or 1";
-        return AZ_E_INVALID;
-    }
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    HIPCHK(e, hipDeviceSynchronize()); // a generation that still plays was launched under the old setting
-    e->p.forced_k = k;
-    e->p.forced_prune = k > 0.0 ? prune : 0;
-    e->reset_done = false; // the caller starts a generation next (az_engine_reset / az_engine_stream_begin)
-    return AZ_OK;
+    return install_search(e, SET_FORCED, [&](SearchState &s) { s.forced_k = k; s.forced_prune = prune; return AZ_OK; });
 }
 
-// ---- MCTS-Solver (include/az_engine.h: az_engine_set_solver) ---------------------------------------------------------------------
 extern "C" int az_engine_set_solver(az_engine *e, int32_t on) {
-    if (!e) return AZ_E_INVALID;
-    const char *why = nullptr;
-    if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) why = "an arena engine (an evaluation game measures the reference's search)";
-    else if (e->cfg.select_rule != AZ_SELECT_PUCT) why = "select_rule = AZ_SELECT_UCT (the solver's select rule is stated for the PUCT value)";
-    else if (on && e->p.forced_k > 0.0) why = "an engine with az_engine_set_forced_playouts in force (forced playouts together with the solver are not built)";
-    if (why) {
-        e->err = std::string("az_engine_set_solver is for PUCT self-play and manual_moves engines: refused for ") + why;
-        return AZ_E_INVALID;
-    }
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    HIPCHK(e, hipDeviceSynchronize()); // a generation that still plays was launched under the old setting
-    e->p.solver = on ? 1 : 0;
-    e->reset_done = false; // the caller starts a generation next (az_engine_reset / az_engine_stream_begin)
-    return AZ_OK;
+    return install_search(e, SET_SOLVER, [&](SearchState &s) { s.solver = on; return AZ_OK; });
 }
 
-// ---- first-play urgency (include/az_engine.h: az_engine_set_fpu) -------------------------------------------------------------------
 extern "C" int az_engine_set_fpu(az_engine *e, int32_t on, double reduction, double reduction_root) {
-    if (!e) return AZ_E_INVALID;
-    const char *why = nullptr;
-    if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) why = "an arena engine (an evaluation game measures the reference's search)";
-    else if (e->cfg.select_rule != AZ_SELECT_PUCT) why = "select_rule = AZ_SELECT_UCT (that rule already values an unvisited child at +infinity)";
-    if (why) {
-        e->err = std::string("az_engine_set_fpu is for PUCT self-play and manual_moves engines: refused for ") + why;
-        return AZ_E_INVALID;
-    }
-    const double dmax = 1.7976931348623157e308;
-    if (on && !(reduction >= 0.0 && reduction <= dmax && reduction_root >= 0.0 && reduction_root <= dmax)) { // (the negated form takes NaN too)
-        e->err = "az_engine_set_fpu: reduction and reduction_root must be finite and >= 0 (on = 0 clears the setting)";
-        return AZ_E_INVALID;
-    }
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    HIPCHK(e, hipDeviceSynchronize()); // a generation that still plays was launched under the old setting
-    e->p.fpu_on = on ? 1 : 0;
-    e->p.fpu_reduction = on ? reduction : 0.0;
-    e->p.fpu_reduction_root = on ? reduction_root : 0.0;
-    e->reset_done = false; // the caller starts a generation next (az_engine_reset / az_engine_stream_begin)
-    return AZ_OK;
+    return install_search(e, SET_FPU, [&](SearchState &s) { s.fpu_on = on; s.fpu_reduction = reduction; s.fpu_reduction_root = reduction_root; return AZ_OK; });
 }
 
-// ---- evaluation in a random left-right orientation (include/az_engine.h: az_engine_set_eval_mirror) ----------------------------
 extern "C" int az_engine_set_eval_mirror(az_engine *e, double p_mirror) {
-    if (!e) return AZ_E_INVALID;
-    if (e->p.arena_agent != AZ_ARENA_SELF_PLAY) {
-        e->err = "az_engine_set_eval_mirror is for self-play and manual_moves engines: refused for an arena engine (an evaluation game "
-                 "measures the network as it is, in the one orientation its opponent's games are played in)";
-        return AZ_E_INVALID;
-    }
-    if (!(p_mirror >= 0.0 && p_mirror <= 1.0)) { // (the negated form takes NaN too)
-        e->err = "az_engine_set_eval_mirror: p_mirror must be finite and in [0, 1] (0 clears the setting)";
-        return AZ_E_INVALID;
-    }
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    HIPCHK(e, hipDeviceSynchronize()); // a generation that still plays was launched under the old setting
-    e->p.p_mirror = p_mirror;
-    e->reset_done = false; // the caller starts a generation next (az_engine_reset / az_engine_stream_begin)
-    return AZ_OK;
+    return install_search(e, SET_MIRROR, [&](SearchState &s) { s.p_mirror = p_mirror; return AZ_OK; });
 }
 
-// ---- search settings of an arena agent (include/az_engine.h: az_engine_set_arena_search) ------------------------------------------
-// The Params fields are the three setters' own, so launch_tick picks the instantiation as it does for them; the FPU, SOLVER and
-// MIRROR instantiations of az_advance_kernel carry the arena paths (PH_OPP_DONE, the agent's move, re-rooting across both
-// players' moves) like the plain one.
-extern "C" int az_engine_set_arena_search(az_engine *e, const az_arena_search *s) {
-    if (!e) return AZ_E_INVALID;
-    const char *why = nullptr;
-    if (e->cfg.manual_moves) why = "a manual_moves engine (az_engine_set_fpu / _set_solver / _set_eval_mirror are its entries)";
-    else if (e->p.arena_agent == AZ_ARENA_SELF_PLAY) why = "a self-play engine (az_engine_set_fpu / _set_solver / _set_eval_mirror are its entries)";
-    else if (e->p.arena_agent == AZ_ARENA_NET) why = "an AZ_ARENA_NET agent (it searches nothing: one evaluation, the argmax of the priors)";
-    else if (e->cfg.select_rule != AZ_SELECT_PUCT) why = "select_rule = AZ_SELECT_UCT (first-play urgency and the solver's select rule are stated for the PUCT value)";
-    if (why) {
-        e->err = std::string("az_engine_set_arena_search is for AZ_ARENA_ZERO agents under the PUCT rule: refused for ") + why;
-        return AZ_E_INVALID;
-    }
-    az_arena_search off = {(int32_t)sizeof(az_arena_search), 0, 0.0, 0.0, 0, 0, 0.0};
-    if (!s) s = &off; // NULL clears
-    if (s->struct_size != (int32_t)sizeof(az_arena_search)) {
-        e->err = "az_engine_set_arena_search: az_arena_search.struct_size mismatch (header/library skew): got " +
-                 std::to_string(s->struct_size) + ", expected " + std::to_string(sizeof(az_arena_search));
-        return AZ_E_INVALID;
-    }
-    const double dmax = 1.7976931348623157e308;
-    if (s->fpu_on && !(s->fpu_reduction >= 0.0 && s->fpu_reduction <= dmax && s->fpu_reduction_root >= 0.0 &&
-                       s->fpu_reduction_root <= dmax)) { // (the negated form takes NaN too)
-        e->err = "az_engine_set_arena_search: fpu_reduction and fpu_reduction_root must be finite and >= 0 (fpu_on = 0 clears the setting)";
-        return AZ_E_INVALID;
-    }
-    if (!(s->p_mirror >= 0.0 && s->p_mirror <= 1.0)) { // (the negated form takes NaN too)
-        e->err = "az_engine_set_arena_search: p_mirror must be finite and in [0, 1] (0 clears the setting)";
-        return AZ_E_INVALID;
-    }
-    HIPCHK(e, hipSetDevice(e->cfg.device));
-    HIPCHK(e, hipDeviceSynchronize()); // games that still play were launched under the old settings
-    e->p.fpu_on = s->fpu_on ? 1 : 0;
-    e->p.fpu_reduction = s->fpu_on ? s->fpu_reduction : 0.0;
-    e->p.fpu_reduction_root = s->fpu_on ? s->fpu_reduction_root : 0.0;
-    e->p.solver = s->solver ? 1 : 0;
-    e->p.p_mirror = s->p_mirror;
-    e->reset_done = false; // the caller starts the games next (az_engine_reset)
-    return AZ_OK;
+// The fields are the three setters' own, so tick_kernel picks the instantiation as it does for them; the FPU, SOLVER and MIRROR
+// instantiations of az_advance_kernel carry the arena paths (PH_OPP_DONE, the agent's move, re-rooting across both players' moves)
+// like the plain one.
+extern "C" int az_engine_set_arena_search(az_engine *e, const az_arena_search *a) {
+    return install_search(e, SET_ARENA, [&](SearchState &s) {
+        const az_arena_search off = {(int32_t)sizeof(az_arena_search), 0, 0.0, 0.0, 0, 0, 0.0};
+        if (!a) a = &off; // NULL clears
+        if (a->struct_size != (int32_t)sizeof(az_arena_search)) {
+            e->err = "az_engine_set_arena_search: az_arena_search.struct_size mismatch (header/library skew): got " +
+                     std::to_string(a->struct_size) + ", expected " + std::to_string(sizeof(az_arena_search));
+            return AZ_E_INVALID;
+        }
+        s.fpu_on = a->fpu_on;
+        s.fpu_reduction = a->fpu_reduction;
+        s.fpu_reduction_root = a->fpu_reduction_root;
+        s.solver = a->solver;
+        s.p_mirror = a->p_mirror;
+        return AZ_OK;
+    });
 }
 
-// The tick kernel's instantiation for the settings in force (az_engine_set_forced_playouts, az_engine_set_eval_mirror,
-// az_engine_set_solver, az_engine_set_fpu: each its own instantiations; with none set the engine launches the kernel without any of
-// the features).
-template <int GAME, int NP, bool MAPPED>
-static void launch_tick(az_engine *e, dim3 grid, dim3 block, hipStream_t st, int g_first, int g_end, const float *priors,
-                        const float *values, float *obs_out) {
-    const bool forced = e->p.forced_k > 0.0, mirror = e->p.p_mirror > 0.0;
-#define AZ_TICK_FPU(F, M, SV, U) hipLaunchKernelGGL((az_advance_kernel<GAME, NP, MAPPED, F, M, SV, U>), grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out)
-#define AZ_TICK(F, M)        \
-    do {                     \
-        if (e->p.fpu_on) AZ_TICK_FPU(F, M, false, true); \
-        else AZ_TICK_FPU(F, M, false, false);            \
-    } while (0)
-#define AZ_TICK_SOLVER(M)    \
-    do {                     \
-        if (e->p.fpu_on) AZ_TICK_FPU(false, M, true, true); \
-        else AZ_TICK_FPU(false, M, true, false);            \
-    } while (0)
-    if (e->p.solver) { // (never with forced playouts: the two setters refuse each other)
-        if (mirror) AZ_TICK_SOLVER(true);
-        else AZ_TICK_SOLVER(false);
-    } else if (mirror) {
-        if (forced) AZ_TICK(true, true);
-        else AZ_TICK(false, true);
-    } else {
-        if (forced) AZ_TICK(true, false);
-        else AZ_TICK(false, false);
-    }
-#undef AZ_TICK
-#undef AZ_TICK_SOLVER
-#undef AZ_TICK_FPU
+// ---- the tick kernel's instantiation for the settings in force -------------------------------------------------------------------
+// One column per setting that has instantiations of its own: bit i of the index is the i-th template flag after MAPPED.  A new
+// setting is one more flag on az_advance_kernel and one more column here.  The pairs the setters refuse are not built.
+typedef void (*tick_kernel_t)(Params, int, int, const float *, const float *, float *);
+enum { TICK_FORCED = 1, TICK_MIRROR = 2, TICK_SOLVER = 4, TICK_FPU = 8, TICK_N = 16 };
+
+template <int GAME, int NP, bool MAPPED, int I>
+static tick_kernel_t tick_entry() {
+    if constexpr ((I & TICK_FORCED) && (I & TICK_SOLVER)) return nullptr; // (install_search: the one exclusion)
+    else return az_advance_kernel<GAME, NP, MAPPED, (I & TICK_FORCED) != 0, (I & TICK_MIRROR) != 0, (I & TICK_SOLVER) != 0, (I & TICK_FPU) != 0>;
+}
+
+template <int GAME, int NP, bool MAPPED, int... I>
+static tick_kernel_t tick_kernel(const Params &p, std::integer_sequence<int, I...>) {
+    static const tick_kernel_t table[TICK_N] = {tick_entry<GAME, NP, MAPPED, I>()...};
+    return table[(p.forced_k > 0.0 ? TICK_FORCED : 0) | (p.p_mirror > 0.0 ? TICK_MIRROR : 0) | (p.solver ? TICK_SOLVER : 0) | (p.fpu_on ? TICK_FPU : 0)];
 }
 
 // `defer`: compactions of this launch are handed to its own extra workgroups (compact_jobs; whole-engine launches only: the job
@@ -2377,9 +2370,15 @@ static int advance_range(az_engine *e, int g_first, int g_end, const float *prio
     hipStream_t st = (hipStream_t)stream;
     defer = defer && e->may_compact;
     dim3 grid((g_end - g_first + 3) / 4 + (defer ? AZ_COMPACT_WGS : 0)), block(256);
+    const std::make_integer_sequence<int, TICK_N> all;
+    const tick_kernel_t kernel = e->cfg.game == AZ_GAME_CONNECT_FOUR ? tick_kernel<AZG_CONNECT_FOUR, 1, MAPPED>(e->p, all)
+                                                                     : tick_kernel<AZG_BREAKTHROUGH, 3, MAPPED>(e->p, all);
+    if (!kernel) { // (install_search lets no such state in)
+        e->err = "no tick kernel is built for the search settings in force";
+        return AZ_E_STATE;
+    }
     e->p.defer_compact = defer ? 1 : 0;
-    if (e->cfg.game == AZ_GAME_CONNECT_FOUR) launch_tick<AZG_CONNECT_FOUR, 1, MAPPED>(e, grid, block, st, g_first, g_end, priors, values, obs_out);
-    else launch_tick<AZG_BREAKTHROUGH, 3, MAPPED>(e, grid, block, st, g_first, g_end, priors, values, obs_out);
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, e->p, g_first, g_end, priors, values, obs_out);
     e->p.defer_compact = 0;
     HIPCHK(e, hipGetLastError());
     return AZ_OK;

@@ -11,6 +11,7 @@ import torch
 
 from . import _lib
 from .games import Game, boards_from_bitboards
+from .search_settings import SearchSettings, fpu_pair  # noqa: F401 (fpu_pair: importable from here as before)
 
 
 class EngineError(RuntimeError):
@@ -266,16 +267,16 @@ class SelfPlayEngine:
         as set_eval_mirror) - what a match between two settings needs (arena.play_match).  Arena engines with agent "zero" under
         use_puct only (EngineError names the reason otherwise); set_arena_search() with nothing on clears all three.  reset()
         afterwards."""
+        s = SearchSettings.from_kwargs(dict(fpu=fpu, solver=solver, eval_mirror=eval_mirror))
         rec = _lib.AzArenaSearch()
         rec.struct_size = C.sizeof(_lib.AzArenaSearch)
-        pair = None if fpu is None else fpu_pair(fpu)
-        rec.fpu_on = int(pair is not None)
-        rec.fpu_reduction, rec.fpu_reduction_root = pair if pair is not None else (0.0, 0.0)
-        rec.solver = int(bool(solver))
-        rec.p_mirror = float(eval_mirror or 0.0)
+        rec.fpu_on = int(s.fpu is not None)
+        rec.fpu_reduction, rec.fpu_reduction_root = s.fpu or (0.0, 0.0)
+        rec.solver = int(bool(s.solver))
+        rec.p_mirror = s.eval_mirror or 0.0
         self._check(self.lib.az_engine_set_arena_search(self._h, C.byref(rec)))
-        on = pair is not None or bool(solver) or rec.p_mirror > 0.0
-        self.arena_search = dict(fpu=pair, solver=bool(solver), eval_mirror=rec.p_mirror) if on else None
+        on = s.fpu is not None or bool(s.solver) or rec.p_mirror > 0.0
+        self.arena_search = dict(fpu=s.fpu, solver=bool(s.solver), eval_mirror=rec.p_mirror) if on else None
 
     def set_arena_openings(self, prefixes):
         """An opening per evaluation game (az_engine_set_arena_openings): game i of the next reset() starts after the action list
@@ -892,18 +893,6 @@ def stream_take_layout(n_games, max_plies, max_children):
     return device_export_layout(n_games, max_plies, max_children)
 
 
-def fpu_pair(fpu):
-    """fpu=r or (r, r_root) -> (reduction, root reduction) as floats: both finite and >= 0, the root's 0 when left out (ValueError
-    otherwise).  The one validation of every fpu= keyword of the package."""
-    pair = tuple(fpu) if isinstance(fpu, (tuple, list)) else (fpu, 0.0)
-    if len(pair) != 2 or any(isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) for x in pair):
-        raise ValueError("fpu must be a reduction r or a pair (r, r_root) of numbers, got %r" % (fpu,))
-    r, r_root = float(pair[0]), float(pair[1])
-    if not (0.0 <= r < float("inf") and 0.0 <= r_root < float("inf")):
-        raise ValueError("fpu reductions must be finite and >= 0, got %r" % (fpu,))
-    return r, r_root
-
-
 class SelfPlayStream:
     """Continuous self-play: an engine in stream mode (az_engine_stream_begin), its request buffers and ONE tick driver.
     Slots never wait for the end of a generation: a finished slot takes the next game id at once, and take(n) hands the next n
@@ -927,14 +916,8 @@ class SelfPlayStream:
         self.engine, self.evaluator = engine, evaluator
         self.use_graph, self.check_every = bool(use_graph), max(1, int(check_every))
         self.ticks_per_graph = min(max(1, int(ticks_per_graph)), self.check_every)
-        if forced_playouts is not None:
-            engine.set_forced_playouts(*(forced_playouts if isinstance(forced_playouts, (tuple, list)) else (forced_playouts,)))
-        if eval_mirror is not None:
-            engine.set_eval_mirror(eval_mirror)
-        if solver is not None:
-            engine.set_solver(solver)
-        if fpu is not None:
-            engine.set_fpu(*fpu_pair(fpu))
+        SearchSettings.from_kwargs(dict(forced_playouts=forced_playouts, eval_mirror=eval_mirror, solver=solver, fpu=fpu),
+                                   off="clear").apply(engine)  # (None leaves the engine's setting, an off value clears it)
         engine.stream_begin(seed)
         self.obs, self.pri, self.val = engine.alloc_io()
         self.taken = 0          # games handed over so far = the id of the next one

@@ -12,7 +12,7 @@ import copy
 import numpy as np
 import torch
 
-from .engine import (EngineError, SelfPlayEngine, SelfPlayStream, check_stream_request, close_all, examples_from_export, fpu_pair,
+from .engine import (EngineError, SearchSettings, SelfPlayEngine, SelfPlayStream, check_stream_request, close_all, examples_from_export,
                      make_evaluator, run_selfplay, run_selfplay_pools, slot_groups, stream_capacity, unpack_device_export)
 from .games import Game
 from . import distributed as azdist
@@ -84,83 +84,19 @@ class ExampleGenerator:
                 raise ValueError("continuous=True ticks the engine on one stream: overlap > 1 is not supported with it")
             if self.eval_backend != "fused":
                 raise ValueError("continuous=True needs eval_backend=\"fused\" (got %r)" % (self.eval_backend,))
-        # playout_cap=(n_fast, p_full): playout cap randomisation (SelfPlayEngine.set_playout_cap) - every move is searched in full
-        # (n_playouts) with probability p_full, else with n_fast playouts, and ONLY the full-search moves become examples.  The
-        # mask of full-search moves is a side table of one engine: it does not travel with a gather (as game starts do not).
-        self.playout_cap = kwargs.get("playout_cap")
-        if self.playout_cap is not None:
-            try:
-                n_fast, p_full = self.playout_cap
-                n_fast, p_full = int(n_fast), float(p_full)
-            except (TypeError, ValueError):
-                raise ValueError("playout_cap must be a pair (n_fast, p_full), got %r" % (self.playout_cap,))
-            n_playouts = int(kwargs.get("n_playouts", 100))  # (SelfPlayEngine's default)
-            if not 1 <= n_fast <= n_playouts or not 0.0 <= p_full <= 1.0:
-                raise ValueError("playout_cap=(n_fast, p_full) needs 1 <= n_fast <= n_playouts = %d and 0 <= p_full <= 1, got %r"
-                                 % (n_playouts, self.playout_cap))
-            self.playout_cap = (n_fast, p_full)
-            self._check_start_positions("playout_cap")
-            if self.overlap > 1:
-                raise ValueError("playout_cap is not supported with overlap > 1: the capped generation is ticked on one stream")
-
-        # forced_playouts=k or (k, prune): forced playouts at the root and policy target pruning (SelfPlayEngine.set_forced_playouts)
-        # in every full search.  The pruned counts sit where the raw ones sat, so every path carries them: the setting goes to
-        # EVERY engine this generator builds (pools, ranks, overlap, the stream of continuous=True).
-        self.forced_playouts = kwargs.get("forced_playouts")
-        if self.forced_playouts is not None:
-            fp = self.forced_playouts
-            try:
-                k, prune = (fp if isinstance(fp, (tuple, list)) else (fp, True))
-                k = float(k)
-            except (TypeError, ValueError):
-                raise ValueError("forced_playouts must be k or a pair (k, prune), got %r" % (fp,))
-            if not (0.0 <= k < float("inf")) or prune not in (0, 1, False, True):
-                raise ValueError("forced_playouts needs a finite k >= 0 and prune False / True, got %r" % (fp,))
-            if self.is_test:
-                raise ValueError("forced_playouts is a self-play setting: it is not supported with is_test=True (evaluation games "
-                                 "record no policy target)")
-            if not kwargs.get("use_puct", True):
-                raise ValueError("forced_playouts is not supported with use_puct=False: the rules are stated for the PUCT value")
-            self.forced_playouts = (k, bool(prune)) if k > 0.0 else None
-
-        # eval_mirror=p: every network request of a search is evaluated left-right mirrored with probability p and its answer
-        # mapped back (SelfPlayEngine.set_eval_mirror).  An engine setting keyed by (seed, game id) that leaves the records as
-        # they are: it goes to EVERY engine this generator builds (pools, ranks, overlap, the stream of continuous=True).
-        self.eval_mirror = kwargs.get("eval_mirror")
-        if self.eval_mirror is not None:
-            try:
-                p = float(self.eval_mirror)
-            except (TypeError, ValueError):
-                raise ValueError("eval_mirror must be a probability in [0, 1], got %r" % (self.eval_mirror,))
-            if not 0.0 <= p <= 1.0:  # (NaN fails both comparisons)
-                raise ValueError("eval_mirror must be a probability in [0, 1], got %r" % (self.eval_mirror,))
-            if self.is_test:
-                raise ValueError("eval_mirror is a self-play setting: it is not supported with is_test=True (evaluation games show "
-                                 "the network every position as it is)")
-            self.eval_mirror = p if p > 0.0 else None
-
-        # solver=True: MCTS-Solver (SelfPlayEngine.set_solver) in every search.  The adjusted counts and exact targets sit where
-        # the raw ones sat, so the setting goes to EVERY engine this generator builds, like the two above.
-        self.solver = bool(kwargs.get("solver", False))
-        if self.solver:
-            if self.is_test:
-                raise ValueError("solver is a self-play setting: it is not supported with is_test=True (evaluation games measure the "
-                                 "reference's search)")
-            if not kwargs.get("use_puct", True):
-                raise ValueError("solver is not supported with use_puct=False: its select rule is stated for the PUCT value")
-            if self.forced_playouts is not None:
-                raise ValueError("solver is not supported together with forced_playouts")
-
-        # fpu=r or (r, r_root): first-play urgency (SelfPlayEngine.set_fpu) in every search.  A select rule that leaves the records'
-        # layout alone: it goes to EVERY engine this generator builds (pools, ranks, overlap, the stream of continuous=True).
-        self.fpu = kwargs.get("fpu")
-        if self.fpu is not None:
-            self.fpu = fpu_pair(self.fpu)
-            if self.is_test:
-                raise ValueError("fpu is a self-play setting: it is not supported with is_test=True (evaluation games measure the "
-                                 "reference's search)")
-            if not kwargs.get("use_puct", True):
-                raise ValueError("fpu is not supported with use_puct=False: that rule already values an unvisited child at +infinity")
+        # The search settings (search_settings.SearchSettings; an off k or p is the same as none: these engines are built here).
+        # playout_cap=(n_fast, p_full): every move is searched in full (n_playouts) with probability p_full, else with n_fast
+        # playouts, and ONLY the full-search moves become examples.  The mask of full-search moves is a side table of one engine: it
+        # does not travel with a gather (as game starts do not).
+        # forced_playouts=k or (k, prune), eval_mirror=p, solver=True, fpu=r or (r, r_root): forced playouts with policy target
+        # pruning, evaluation in a random left-right orientation, the MCTS-Solver and first-play urgency in every search.  They
+        # leave the records' layout alone (pruned and adjusted counts sit where the raw ones sat), so they go to EVERY engine this
+        # generator builds (pools, ranks, overlap, the stream of continuous=True).
+        self.settings = SearchSettings.from_kwargs(kwargs).check(
+            self._check_start_positions, is_test=self.is_test, use_puct=bool(kwargs.get("use_puct", True)),
+            n_playouts=int(kwargs.get("n_playouts", 100)), overlap=self.overlap)  # (100: SelfPlayEngine's default)
+        self.playout_cap, self.forced_playouts = self.settings.playout_cap, self.settings.forced_playouts
+        self.eval_mirror, self.solver, self.fpu = self.settings.eval_mirror, bool(self.settings.solver), self.settings.fpu
 
     def _engine_kwargs(self):
         return {k: self.kwargs[k] for k in _ENGINE_KW if k in self.kwargs}
@@ -170,14 +106,7 @@ class ExampleGenerator:
         after)."""
         engine = SelfPlayEngine(self.game, n_slots, **kw, **self._engine_kwargs())
         try:
-            if self.forced_playouts is not None:
-                engine.set_forced_playouts(*self.forced_playouts)
-            if self.eval_mirror is not None:
-                engine.set_eval_mirror(self.eval_mirror)
-            if self.solver:
-                engine.set_solver(True)
-            if self.fpu is not None:
-                engine.set_fpu(*self.fpu)
+            self.settings.apply(engine)
         except Exception:
             close_all(engine)
             raise

@@ -351,16 +351,15 @@ class Forker:
 
     def __init__(self, store, net, n_slots, n_playouts, eval_backend="fused", eval_precision="f32x", use_graph=False, seed=0,
                  max_games=None, fpu=None, **kwargs):
-        from .engine import SelfPlayEngine, fpu_pair, make_evaluator
-        fpu = None if fpu is None else fpu_pair(fpu)
+        from .engine import SearchSettings, SelfPlayEngine, make_evaluator
+        settings = SearchSettings.from_kwargs(dict(fpu=fpu))
         self.store, self.seed, self.use_graph, self.calls = store, int(seed), bool(use_graph), 0
         self.eval_backend, self.eval_precision = eval_backend, eval_precision
         self.engine = SelfPlayEngine(store.game, int(n_slots), n_playouts=int(n_playouts), device=store.device, seed=self.seed,
                                      max_games=int(max_games if max_games is not None else n_slots), **kwargs)
         self.evaluator = None
         try:
-            if fpu is not None:
-                self.engine.set_fpu(*fpu)
+            settings.apply(self.engine)
             self.evaluator = make_evaluator(net, store.device, eval_backend, eval_precision, self.engine.G)
         except Exception:
             self.engine.close()

@@ -69,26 +69,16 @@ def main():
                          "minus R * sqrt(explored prior mass) (R_ROOT at the root, default 0) in place of the reference's 0, in "
                          "self-play and in the searches of --reanalyse and --fork (e.g. 0.3)")
     a = ap.parse_args()
-    if not 0.0 <= a.forced_playouts < float("inf"):
-        ap.error("--forced-playouts takes a finite K >= 0")
-    if a.solver and a.forced_playouts:
-        ap.error("--solver is not available together with --forced-playouts")
-    if not 0.0 <= a.eval_mirror <= 1.0:
-        ap.error("--eval-mirror takes a probability in [0, 1]")
-    fpu = None
-    if a.fpu:
-        try:
-            fpu = E.fpu_pair(tuple(float(x) for x in a.fpu.split(":")) if ":" in a.fpu else float(a.fpu))
-        except ValueError:
-            ap.error("--fpu takes R or R:R_ROOT, both finite and >= 0, e.g. 0.3 or 0.3:0")
-    cap = None
-    if a.playout_cap:
-        if a.continuous:
-            ap.error("--playout-cap is not available with --continuous (the mask of full-search moves does not travel with a take)")
-        try:
-            cap = (int(a.playout_cap.split(":")[0]), float(a.playout_cap.split(":")[1]))
-        except (IndexError, ValueError):
-            ap.error("--playout-cap takes N_FAST:P_FULL, e.g. 25:0.25")
+    if a.playout_cap and a.continuous:
+        ap.error("--playout-cap is not available with --continuous (the mask of full-search moves does not travel with a take)")
+    try:  # one parser and one set of rules for the five settings (alphazero_openspiel_amd/search_settings.py)
+        settings = E.SearchSettings.from_kwargs(dict(
+            forced_playouts=a.forced_playouts or None, eval_mirror=a.eval_mirror or None, solver=a.solver,
+            fpu=(tuple(float(x) for x in a.fpu.split(":")) if ":" in a.fpu else float(a.fpu)) if a.fpu else None,
+            playout_cap=tuple(a.playout_cap.split(":")) if a.playout_cap else None)).check(n_playouts=a.playouts)
+    except ValueError as err:
+        ap.error("%s (--fpu takes R or R:R_ROOT, --playout-cap N_FAST:P_FULL)" % err)
+    fpu, cap = settings.fpu, settings.playout_cap
 
     dev = torch.device("cuda:0")
     game = games.load_game(a.game)
@@ -115,14 +105,7 @@ def main():
         else:
             eng = E.SelfPlayEngine(game, min(a.games, 4096), n_playouts=a.playouts, backup=a.backup, max_games=a.games,
                                    device=dev, seed=gen)
-            if a.forced_playouts:
-                eng.set_forced_playouts(a.forced_playouts)                 # the records then hold the pruned counts
-            if a.eval_mirror:
-                eng.set_eval_mirror(a.eval_mirror)
-            if a.solver:
-                eng.set_solver(True)
-            if fpu is not None:
-                eng.set_fpu(*fpu)
+            settings.apply(eng)                                            # (under forced playouts the records hold the pruned counts)
             if cap is not None:
                 eng.set_playout_cap(*cap)                                  # append_engine below keeps the full-search moves only
             prog = E.run_selfplay(eng, FusedNet(net, dev, max_boards=eng.G, precision=a.precision), a.games, use_graph=True)

@@ -43,7 +43,7 @@ def main():
     ev = FusedNet(net, dev, max_boards=G, precision=a.precision)
     for leg, p in (("plain", 0.0), ("eval_mirror", a.p)):
         eng = E.SelfPlayEngine("connect_four", G, n_playouts=a.playouts, max_games=(a.warmup + a.steps + 2) * G, device=dev, seed=1)
-        eng.set_eval_mirror(p)
+        E.SearchSettings.from_kwargs(dict(eval_mirror=p)).apply(eng)
         eng.reset((a.warmup + a.steps + 2) * G)
         obs, pri, val = eng.alloc_io()
 

@@ -43,7 +43,7 @@ def main():
     ev = FusedNet(net, dev, max_boards=a.slots, precision=a.precision)
     for leg, k in (("plain", 0.0), ("forced", a.k)):
         eng = E.SelfPlayEngine("connect_four", a.slots, n_playouts=a.playouts, max_games=a.games, device=dev, seed=1)
-        eng.set_forced_playouts(k, True)
+        E.SearchSettings.from_kwargs(dict(forced_playouts=(k, True))).apply(eng)
         rows = []
         for run in range(a.runs + 1):  # (the first one is untimed: library load, kernel first use, graph capture)
             torch.cuda.synchronize()

@@ -38,7 +38,8 @@ def main():
     from alphazero_openspiel_amd import engine as E
     from alphazero_openspiel_amd.fusednet import FusedNet
     from alphazero_openspiel_amd.network import Net
-    fpu = E.fpu_pair(tuple(float(x) for x in a.fpu.split(":")))
+    settings = E.SearchSettings.from_kwargs(dict(fpu=tuple(float(x) for x in a.fpu.split(":"))))
+    fpu = settings.fpu
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     net = Net([3, 6, 7], 7, n_blocks=a.blocks, n_filters=a.filters).eval()
@@ -49,7 +50,7 @@ def main():
     for leg in a.legs.split(","):
         eng = E.SelfPlayEngine("connect_four", a.slots, n_playouts=a.playouts, max_games=a.games, device=dev, seed=1)
         if leg == "fpu":
-            eng.set_fpu(*fpu)
+            settings.apply(eng)
         rows = []
         for run in range(a.runs + 1):  # (the first one is untimed: library load, kernel first use, graph capture)
             torch.cuda.synchronize()

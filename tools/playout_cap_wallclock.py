@@ -45,7 +45,7 @@ def main():
     for leg, cap in (("no_cap", None), ("cap", (n_fast, p_full))):
         eng = E.SelfPlayEngine("connect_four", a.slots, n_playouts=a.playouts, max_games=a.games, device=dev, seed=1)
         if cap is not None:
-            eng.set_playout_cap(*cap)
+            eng.set_playout_cap(*E.SearchSettings.from_kwargs(dict(playout_cap=cap)).check(n_playouts=a.playouts).playout_cap)
         rows = []
         for run in range(a.runs + 1):  # (the first one is untimed: library load, kernel first use, graph capture)
             torch.cuda.synchronize()

@@ -32,8 +32,7 @@ def parse_settings(text, playouts):
         if key == "solver" and val in ("", "1", "true", "True"):
             out["solver"] = True
         elif key == "fpu" and val:
-            parts = [float(x) for x in val.split(":")]
-            out["fpu"] = (parts[0], parts[1] if len(parts) > 1 else 0.0)
+            out["fpu"] = tuple(float(x) for x in val.split(":")) if ":" in val else float(val)  # (read by SearchSettings)
         elif key == "eval_mirror" and val:
             out["eval_mirror"] = float(val)
         elif key == "n_playouts" and val:

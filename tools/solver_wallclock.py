@@ -75,7 +75,7 @@ def main():
     ev = FusedNet(net, dev, max_boards=a.slots, precision=a.precision)
     for leg, solver in (("plain", False), ("solver", True)):
         eng = E.SelfPlayEngine("connect_four", a.slots, n_playouts=a.playouts, max_games=a.games, device=dev, seed=1)
-        eng.set_solver(solver)
+        E.SearchSettings.from_kwargs(dict(solver=solver)).apply(eng)
         rows, counts = [], []
         for run in range(a.runs + 1):  # (the first one is untimed: library load, kernel first use, graph capture)
             torch.cuda.synchronize()
