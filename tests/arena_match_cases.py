@@ -1,7 +1,7 @@
-"""The model of tests/test_arena_match_host.py and tests/test_arena_match_gpu.py: evaluation games in plain Python (IEEE doubles,
-the original's association) between an AlphaZeroBot outside self-play and a bot, or between two such agents, with the settings of
-az_engine_set_arena_search (include/az_engine.h) and an opening per game (az_engine_set_arena_openings).  The search is the one
-tests/fpu_cases.py states - Node, select and the playout, which carry first-play urgency, the MCTS-Solver and the evaluation
+"""The cases of tests/test_arena_match_host.py and tests/test_arena_match_gpu.py: evaluation games in plain Python between an
+AlphaZeroBot outside self-play and a bot, or between two such agents, with the settings of az_engine_set_arena_search
+(include/az_engine.h) and an opening per game (az_engine_set_arena_openings).  The search and the move step are those of
+tests/search_model.py - playout, proven_counts and choose_move, which carry first-play urgency, the MCTS-Solver and the evaluation
 mirror.  The agent loop restates orc_play_arena_game / orc_play_duel_game and orc_bot_step of oracle/az_oracle.c: the agent of
 game i plays player (i & 1) ^ flip, its tree is kept across both players' moves, update_root runs only with >= 2 moves played
 (alphazerobot.py:60-64), the move is the first maximum of the tempered visit fractions or - use_probabilistic_actions - a sample
@@ -11,16 +11,15 @@ tests/test_arena_match_host.py pins.  No test lives here."""
 import numpy as np
 
 import eval_mirror_cases as EM
-import forced_playouts_cases as FC
-import fpu_cases as FP
+import search_model as SM
 import solver_cases as SC
 from alphazero_openspiel_amd import games
 from mirror_cases import action_mirror_table
 from oracle import binding as orc
 from oracle import fakepolicy
-from test_playout_cap_host import cap_uniform
+from philox_cases import cap_uniform
+from search_model import DRAW, LOSS, UNKNOWN, WIN   # (the tests read them here)
 
-UNKNOWN, WIN, DRAW, LOSS = SC.UNKNOWN, SC.WIN, SC.DRAW, SC.LOSS
 C4, B66 = "connect_four", "breakthrough(rows=6,columns=6)"
 FPU = (0.3, 0.1)
 # the single settings and all three together, as the parity tests run every game
@@ -38,109 +37,48 @@ class Agent:
 
     def __init__(self, game, salt, seed, game_id, n_playouts, c_puct=2.5, temperature=1.0, keep_search_tree=True, use_puct=True,
                  use_probabilistic_actions=False, num_probabilistic_actions=1000, fpu=None, solver=False, eval_mirror=0.0):
-        self.game, self.salt, self.seed, self.gid = game, salt, seed, game_id
-        self.S, self.c_puct, self.temperature, self.keep, self.use_puct = n_playouts, c_puct, temperature, keep_search_tree, use_puct
+        self.salt, self.seed, self.gid = salt, seed, game_id
+        self.S, self.temperature, self.keep, self.use_puct = n_playouts, temperature, keep_search_tree, use_puct
         self.n_prob = (int(num_probabilistic_actions) if int(num_probabilistic_actions) > 0 else 0) if use_probabilistic_actions else 0
-        self.fpu, self.solver, self.p_mirror = fpu, bool(solver), float(eval_mirror or 0.0)
+        self.settings = SM.Settings(c_puct, 0.0, bool(solver), fpu)
+        self.p_mirror = float(eval_mirror or 0.0)
         self.table = action_mirror_table(games.load_game(game)) if self.p_mirror > 0.0 else None
-        self.root = FP.Node(None, 0.0, True)                            # MCTS.__init__ builds a PUCT root (mcts.py:122)
+        self.root = SM.Node(None, 0.0, True)                            # MCTS.__init__ builds a PUCT root (mcts.py:122)
         self.steps = []                                                 # one dict per move of the agent
         self.mirrored = [0, 0]                                          # requests evaluated as they are / mirrored
         self.fpu_differs = 0                                            # selections the FPU rule made differently
-        self.cur = {"ply": 0, "ran": 0}
-
-    def update_root(self, action):                                      # mcts.py:192-203
-        if not self.root.children:
-            self.root = FP.Node(None, 0.0, self.use_puct)
-        else:
-            self.root = self.root.children[self.root.actions.index(action)]
-            self.root.parent = None
-
-    def evaluate(self, s, A):
-        board = np.asarray(s.board())
-        flip = self.p_mirror > 0.0 and bool(EM.coin(self.seed, self.gid, self.cur["ply"], EM.PH_WAIT_LEAF, self.cur["ran"], self.p_mirror))
-        pri, val = fakepolicy.fake_eval(board[..., ::-1] if flip else board, A, self.salt)
-        if flip:
-            pri = pri[np.asarray(self.table)]
-        self.mirrored[int(flip)] += 1
-        return [float(x) for x in pri], float(val)
-
-    def playout(self, s, A):                                            # mcts.py:126-153 with the rules of fpu_cases.play_game
-        root, solver = self.root, self.solver
-        node, depth, mover = root, 0, s.current_player()
-        while node.children and not s.is_terminal() and not (solver and node is not root and node.status != UNKNOWN):
-            mover = s.current_player()
-            f = None if self.fpu is None else (self.fpu[1] if node is root else self.fpu[0])
-            i, plain = FP.select(node, self.c_puct, 0.0, solver, f)
-            if f is not None:
-                self.fpu_differs += i != FP.select(node, self.c_puct, 0.0, solver, None)[0]
-            s.apply_action(node.actions[i])
-            node = node.children[i]
-            depth += 1
-        if s.is_terminal() or (solver and node is not root and node.status != UNKNOWN):
-            if solver and node.status != UNKNOWN:                       # rule 4
-                node.update_recursive(SC.VALUE[node.status])
-            else:
-                x = -(-s.player_return(mover))
-                node.update_recursive(x)
-                if solver:                                              # rules 1 and 2
-                    node.status = SC.status_of(x)
-                    SC.propagate(node, [None] * (depth + 1), None)
-        else:
-            priors, leaf_value = self.evaluate(s, A)
-            node.expand(priors, s.legal_actions())
-            node.update_recursive(-leaf_value)
+        self.counters = dict.fromkeys(SM.COUNTERS, 0)
 
     def step(self, state, hist):
         """AlphaZeroBot.step (alphazerobot.py:42-93) in `state`, reached by the moves `hist` from the initial position."""
-        A = int(state.num_actions)
+        A, solver = int(state.num_actions), self.settings.solver
         if self.keep:
             if len(hist) >= 2:                                          # alphazerobot.py:60-64
-                self.update_root(hist[-2])
-                self.update_root(hist[-1])
+                self.root = SM.update_root(SM.update_root(self.root, hist[-2], self.use_puct), hist[-1], self.use_puct)
         else:
-            self.root = FP.Node(None, 0.0, True)
+            self.root = SM.Node(None, 0.0, True)
         root = self.root
         kept_status = root.status
-        self.cur["ply"], ran = len(hist), 0
+        ran = 0
+
+        def evaluate(s):
+            flip = self.p_mirror > 0.0 and bool(EM.coin(self.seed, self.gid, len(hist), EM.PH_WAIT_LEAF, ran, self.p_mirror))
+            self.mirrored[int(flip)] += 1
+            return SM.evaluate(lambda b: fakepolicy.fake_eval(b, A, self.salt), s, flip, self.table)
+
         for _ in range(self.S):
-            if self.solver and root.status != UNKNOWN:                  # rule 5: also a kept subtree that is already proven
+            if solver and root.status != UNKNOWN:                       # rule 5: also a kept subtree that is already proven
                 break
-            self.cur["ran"] = ran
-            self.playout(state.clone(), A)
+            self.fpu_differs += len(SM.playout(root, state.clone(), self.settings, evaluate, self.counters).fpu_differs)
             ran += 1
-        legal = state.legal_actions()
         raw = [c.N for c in root.children]
-        counts = list(raw)
-        if self.solver and root.status != UNKNOWN:                      # rule 6, before the move is drawn
-            if root.status == LOSS:                                     # won for the player to move
-                counts = [n if c.status == WIN else 0 for n, c in zip(raw, root.children)]
-            elif root.status == DRAW:
-                counts = [0 if c.status == LOSS else n for n, c in zip(raw, root.children)]
-        tot = sum(counts)                                               # mcts.py:155-162 + alphazerobot.py:7-18
-        nv = np.zeros(A, dtype=np.float64)
-        for a, n in zip(root.actions, counts):
-            nv[a] = float(n) / float(tot)
-        nv = orc.remove_illegal_actions(nv, legal)
-        e, tot = 1.0 / self.temperature, 0
-        ap = [FC.np_pow(float(x), e) for x in nv]
-        for x in ap:
-            tot = tot + x
-        ap = [x / tot for x in ap]
-        if len(hist) < self.n_prob:                                     # np.random.choice on the engine's move stream
-            u = cap_uniform(self.seed, self.gid, len(hist), purpose=1, idx=0)
-            acc, cdf = 0.0, []
-            for x in ap:
-                acc += x
-                cdf.append(acc)
-            cdf = [x / cdf[-1] for x in cdf]
-            move = next((i for i, x in enumerate(cdf) if x > u), A - 1)
-        else:
-            move = max(range(A), key=lambda a: (ap[a], -a))             # np.argmax: the first maximum
+        counts = SM.proven_counts(root, raw) if solver else list(raw)   # rule 6, before the move is drawn
+        u = cap_uniform(self.seed, self.gid, len(hist), purpose=1, idx=0) if len(hist) < self.n_prob else None   # the move stream
+        move, _ = SM.choose_move(root, counts, state.legal_actions(), A, self.temperature, u)
         rec = dict(ply=len(hist), status=root.status, kept_status=kept_status, raw=raw, counts=counts, actions=list(root.actions),
                    child_status=[c.status for c in root.children], ran=ran, move=move)
         if root.status != UNKNOWN:
-            rec["statuses"] = SC.tree_statuses(root)[0]                 # the order of SelfPlayEngine.read_proofs
+            rec["statuses"] = SM.tree_statuses(root)[0]                 # the order of SelfPlayEngine.read_proofs
         self.steps.append(rec)
         return move
 

@@ -5,7 +5,7 @@ evaluator that mirrors the chosen rows itself.  No test lives here.
 The coin: every network request is mirrored iff u < p_mirror, u = the first philox_u01 of the Philox stream
   leaf request (phase 4):  (seed, game id, absolute ply of the slot's root, purpose 4, index = sims_done of the waiting slot)
   root request (phase 3):  (seed, game id, root ply, purpose 5, index 0)
-restated with the Philox model of tests/test_playout_cap_host.py.
+restated with the Philox model of tests/philox_cases.py.
 
 The wrapper: for each row whose coin is set it evaluates obs.flip(-1) and writes the priors permuted by
 mirror_cases.action_mirror_table(game), so that the plain engine, which reads priors[row][a], finds net(flip(obs))[mirror(a)]
@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from mirror_cases import action_mirror_table
-from test_playout_cap_host import cap_uniform
+from philox_cases import cap_uniform
 
 C4, B66 = "connect_four", "breakthrough(rows=6,columns=6)"
 S, G, N = 24, 4, 8

@@ -1,12 +1,12 @@
 """Shared pieces of the production-RNG tests (tests/test_production_rng_gpu.py, tests/test_production_rng_host.py); no GPU here.
 
 Production mode (AZ_RNG_PHILOX) draws two things on the device: the move uniform - the first philox_u01 of the stream (seed,
-game id, ply, purpose 1, index 0), which the Python Philox of tests/test_playout_cap_host.py models bit for bit - and the root
+game id, ply, purpose 1, index 0), which the Python Philox of tests/philox_cases.py models bit for bit - and the root
 noise, gamma draws behind the stream (seed, game id, ply, purpose 0, index = child) made with hardware approximations, which no
 host model reproduces.  So the noise is READ BACK (SelfPlayEngine.read_root_noise) and everything downstream of it is exact."""
 import numpy as np
 
-from test_playout_cap_host import cap_uniform   # the one Python Philox of the suite
+from philox_cases import cap_uniform   # the one Python Philox of the suite
 
 from oracle import fakepolicy
 

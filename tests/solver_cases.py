@@ -1,300 +1,23 @@
-"""The model of tests/test_solver_host.py and tests/test_solver_gpu.py: play_game of tests/forced_playouts_cases.py (self-play,
-game_utils.py:148-206, in plain Python with IEEE doubles and the original's association) restated with the seven rules of
-az_engine_set_solver (include/az_engine.h): proof status on the nodes, propagation after a terminal's backup, no selection of a
-child proven lost, a playout that stops at a proven node, a search that ends at a proven root, the move and the targets at a proven
-root, and a status that travels with a kept subtree.  With solver=False it is play_game itself, which tests/test_solver_host.py
-pins against the C oracle.  Also here: a brute-force negamax for small positions, the shared cases, and (at the end) the cases of
-tests/test_solver_scale_host.py and tests/test_solver_scale_gpu.py: sequences and games at 400-1600 playouts and deep lines.  No
-test lives here."""
-import math
+"""The cases of tests/test_solver_host.py and tests/test_solver_gpu.py: self-play under the seven rules of az_engine_set_solver
+(include/az_engine.h) as tests/search_model.py states them: proof status on the nodes, propagation after a terminal's backup, no
+selection of a child proven lost, a playout that stops at a proven node, a search that ends at a proven root, the move and the
+targets at a proven root, and a status that travels with a kept subtree.  With solver=False the model is play_game_self itself,
+which tests/test_solver_host.py pins against the C oracle.  Also here: a brute-force negamax for small positions, the shared cases,
+and (at the end) the cases of tests/test_solver_scale_host.py and tests/test_solver_scale_gpu.py: sequences and games at 400-1600
+playouts and deep lines.  No test lives here."""
+import functools
 
 import numpy as np
 
 import deep_line_cases as DL
 import forced_playouts_cases as FC
 import product_scale_cases as PS
+import search_model as SM
 from oracle import binding as orc
-from oracle import fakepolicy
+from search_model import COUNTERS, DRAW, LOSS, UNKNOWN, VALUE, WIN, event_stats, tree_statuses   # (the tests read them here)
+from search_model import SOLVER_EFFECTS as EFFECTS
 
-INF = float("inf")
-UNKNOWN, WIN, DRAW, LOSS = 0, 1, 2, 3             # seen by the player who moved INTO the node, as its Q
-VALUE = {WIN: 1.0, DRAW: 0.0, LOSS: -1.0}
-COUNTERS = FC.COUNTERS
-PH_WAIT_ROOT, PH_WAIT_LEAF = 3, 4                 # the phases of a slot with a request outstanding (include/az_engine.h)
-EFFECTS = ("levels2", "loss_skipped", "stopped_nonterminal", "early_won_root", "early_lost_root", "draw_root", "kept_proven_root",
-           "counts_zeroed")
-
-
-def status_of(x):
-    return WIN if x > 0.0 else (LOSS if x < 0.0 else DRAW)
-
-
-class Node(FC.Node):
-    __slots__ = ("status",)
-
-    def __init__(self, parent, prior, use_puct):
-        FC.Node.__init__(self, parent, prior, use_puct)
-        self.status = UNKNOWN
-
-    def expand(self, priors, legal):                  # mcts.py:54-66; a re-expansion rewrites P alone (rule 7)
-        for a in legal:
-            if a in self.actions:
-                self.children[self.actions.index(a)].P = priors[a]
-            else:
-                self.actions.append(a)
-                self.children.append(Node(self, priors[a], self.use_puct))
-
-
-def select(node, c_puct, solver):
-    """The first maximal child (mcts.py:38-52); rule 3: a LOSS child counts as -infinity.  -> (index, index without the rule)."""
-    best, bv, plain, pv = 0, None, 0, None
-    for i, c in enumerate(node.children):
-        v0 = c.value(c_puct)
-        v = -INF if solver and c.status == LOSS else v0
-        if bv is None or v > bv:
-            best, bv = i, v
-        if pv is None or v0 > pv:
-            plain, pv = i, v0
-    return best, plain
-
-
-def propagate(node, path_states, audit):
-    """Rule 2, from the node that has just become proven upward -> levels climbed.  path_states[d]: the state at depth d."""
-    levels, d = 0, len(path_states) - 1
-    while node.parent is not None:
-        par = node.parent
-        if node.status == WIN:
-            new = LOSS
-        elif any(c.status == UNKNOWN for c in par.children):
-            break
-        else:
-            new = 4 - min(c.status for c in par.children)   # minus the best child value: the codes ascend from WIN to LOSS
-        assert par.status == UNKNOWN                  # the descent never passes through a proven node
-        par.status = new
-        d -= 1
-        if audit is not None:
-            audit(path_states[d], new, 1 - path_states[d].current_player())
-        levels += 1
-        node = par
-    return levels
-
-
-def play_game(game, salt, etas, us, solver=True, schedule=None, n_playouts=100, c_puct=2.5, temperature=1.0, dirichlet_ratio=0.25,
-              use_dirichlet=True, keep_search_tree=True, backup="on-policy", num_probabilistic_actions=1000, start=(), audit=None,
-              trees=None, mirror=None, policy=None, max_searches=None, dumps=False):
-    """One game of self-play from the position after `start`.  etas[i][j]: the Dirichlet draw of the j-th legal action at the i-th
-    ply played, us[i]: the uniform behind that move.  schedule: per ply played (playouts, is_full) - a playout cap.
-    audit(state, status, mover): called with a clone of the position of every node that takes a status, the status, and the player
-    who moved into the node (whose view the status is).
-    trees: a list that takes the root Node after every search.
-    mirror: (coin, table) - az_engine_set_eval_mirror: coin(absolute ply of the root, phase of the waiting slot (3: the root request,
-    4: a leaf), playouts of this search already run) says whether the request is evaluated left-right mirrored; the net then sees
-    the board with its columns reversed and the search reads the prior of action a at table[a].  The value is left alone.
-    policy: board -> (priors, value) in place of fakepolicy.fake_eval(board, A, salt).
-    max_searches: stop after that many searches (the last move is still chosen and recorded, but not played; ret0 is None then).
-    dumps: every ply also carries tree = tree_dump(root) after its search and kept = the dump of the subtree the re-rooting kept,
-    before it is searched (None at the first ply and where the search starts on a fresh root).
-    -> dict(plies=[dict(raw, recorded, actions, move, pi, value, ran, status, counters (so far), nodes (in the tree after the
-    search), kept_nodes, kept_proven (nodes / proven nodes in the tree the search started on))], actions, ret0, counters, effects,
-    mirrored, events=[(ply played, depth of the terminal node that became proven, levels its proof climbed)])."""
-    state = orc.State(game)
-    for a in start:
-        state.apply_action(a)
-    A = int(state.num_actions)
-    cnt = dict.fromkeys(COUNTERS, 0)
-    eff = dict.fromkeys(EFFECTS, 0)
-    events = []
-    net = policy if policy is not None else (lambda b: fakepolicy.fake_eval(b, A, salt))
-
-    cur = {"ply": len(start), "ran": 0}                                # the search under way: its root's absolute ply, playouts run
-    mirrored = [0, 0]                                                   # requests evaluated as they are / mirrored
-
-    def evaluate(s, phase=PH_WAIT_LEAF):
-        board = np.asarray(s.board())
-        flip = mirror is not None and bool(mirror[0](cur["ply"], phase, cur["ran"] if phase == PH_WAIT_LEAF else 0))
-        pri, val = net(board[..., ::-1] if flip else board)
-        if flip:
-            pri = pri[np.asarray(mirror[1])]
-        mirrored[int(flip)] += 1
-        cnt["evals"] += 1
-        return [float(x) for x in pri], float(val)
-
-    def playout(root, s):
-        node, depth, mover = root, 0, s.current_player()
-        states = [s.clone()] if audit is not None else [None]
-        while node.children and not s.is_terminal() and not (solver and node is not root and node.status != UNKNOWN):
-            mover = s.current_player()                                  # mcts.py:126-153
-            cnt["sum_children"] += len(node.children)
-            i, plain = select(node, c_puct, solver)
-            if i != plain:
-                eff["loss_skipped"] += 1
-            s.apply_action(node.actions[i])
-            node = node.children[i]
-            depth += 1
-            states.append(s.clone() if audit is not None else None)
-        if s.is_terminal() or (solver and node is not root and node.status != UNKNOWN):
-            if solver and node.status != UNKNOWN:                       # rule 4: the proven value, as a terminal's
-                x = VALUE[node.status]
-                if not s.is_terminal():
-                    eff["stopped_nonterminal"] += 1
-                node.update_recursive(x)
-            else:
-                x = -(-s.player_return(mover))                          # leaf_value = -player_return(mover); update(-leaf_value)
-                node.update_recursive(x)
-                if solver:                                              # rules 1 and 2
-                    node.status = status_of(x)
-                    if audit is not None:
-                        audit(states[-1], node.status, mover)
-                    levels = propagate(node, states, audit)
-                    events.append((len(plies), depth, levels))
-                    if levels >= 2:
-                        eff["levels2"] += 1
-            cnt["terminal_hits"] += 1
-        else:
-            priors, leaf_value = evaluate(s)
-            node.expand(priors, s.legal_actions())
-            node.update_recursive(-leaf_value)
-        cnt["sims"] += 1
-        cnt["sum_depth"] += depth
-
-    root, plies, hist = Node(None, 0.0, True), [], []
-    n_prob = int(num_probabilistic_actions) if int(num_probabilistic_actions) > 0 else 0
-    while not state.is_terminal():
-        ply = len(hist)
-        playouts, full = schedule[ply] if schedule is not None else (n_playouts, True)
-        if keep_search_tree:                                            # alphazerobot.py:44-58 (plain self-play: PUCT throughout)
-            if hist:
-                if not root.children:
-                    root = Node(None, 0.0, True)
-                else:
-                    root = root.children[root.actions.index(hist[-1])]
-                    root.parent = None
-        else:
-            root = Node(None, 0.0, True)
-        legal = state.legal_actions()
-        kept_nodes, kept_proven = tree_size(root)
-        kept = tree_dump(root) if dumps and hist and keep_search_tree else None
-        if solver and root.status != UNKNOWN:
-            eff["kept_proven_root"] += 1
-        cur["ply"], cur["ran"] = len(start) + ply, 0
-        if use_dirichlet:                                               # mcts.py:182-190; made at a proven root as well (rule 5)
-            priors, _ = evaluate(state, PH_WAIT_ROOT)
-            priors = [(1.0 - dirichlet_ratio) * p for p in priors]
-            for i, a in enumerate(legal):
-                priors[a] = priors[a] + 0.25 * etas[ply][i]
-            root.expand(priors, legal)
-        ran = 0
-        for _ in range(playouts):
-            if solver and root.status != UNKNOWN:                       # rule 5
-                break
-            cur["ran"] = ran
-            playout(root, state.clone())
-            ran += 1
-        raw = [c.N for c in root.children]
-        counts = list(raw)
-        if solver and root.status != UNKNOWN:                           # rule 6
-            if ran < playouts:
-                eff["early_won_root" if root.status == LOSS else ("early_lost_root" if root.status == WIN else "draw_root")] += 1
-            if root.status == LOSS:                                     # won for the player to move
-                counts = [n if c.status == WIN else 0 for n, c in zip(raw, root.children)]
-            elif root.status == DRAW:
-                counts = [0 if c.status == LOSS else n for n, c in zip(raw, root.children)]
-            if counts != raw:
-                eff["counts_zeroed"] += 1
-        rec = dict(raw=raw, recorded=counts, actions=list(root.actions), ran=ran, status=root.status, full=bool(full),
-                   counters=dict(cnt), nodes=tree_size(root)[0], kept_nodes=kept_nodes, kept_proven=kept_proven)
-        if dumps:
-            rec["tree"], rec["kept"] = tree_dump(root), kept
-        if trees is not None:
-            trees.append(root)
-
-        tot = sum(counts)                                               # mcts.py:155-162 + alphazerobot.py:7-18
-        nv = np.zeros(A, dtype=np.float64)
-        for a, n in zip(root.actions, counts):
-            nv[a] = float(n) / float(tot)
-        nv = orc.remove_illegal_actions(nv, legal)
-        e, tot = 1.0 / temperature, 0
-        ap = [FC.np_pow(float(x), e) for x in nv]
-        for x in ap:
-            tot = tot + x
-        ap = [x / tot for x in ap]
-        if ply + len(start) < n_prob:                                   # np.random.choice with its one uniform
-            acc, cdf = 0.0, []
-            for x in ap:
-                acc += x
-                cdf.append(acc)
-            cdf = [x / cdf[-1] for x in cdf]
-            move = next((i for i, x in enumerate(cdf) if x > us[ply]), A - 1)
-        else:
-            move = max(range(A), key=lambda a: (ap[a], -a))             # np.argmax: the first maximum
-        rec["pi"] = nv.tolist()
-        if backup == "on-policy":
-            rec["value"] = 0.0
-        elif solver and root.status != UNKNOWN:                         # the proven value for the player to move
-            rec["value"] = -VALUE[root.status]
-        elif backup == "soft-Z":                                        # game_utils.py:172-194
-            rec["value"] = -root.Q
-        elif backup == "A0C":
-            rec["value"] = max(c.Q if c.N > 0 else -99.0 for c in root.children)
-        else:
-            rec["value"] = FC.a0gb_value(root)
-        rec["move"] = move
-        plies.append(rec)
-        if max_searches is not None and len(plies) >= max_searches:
-            break
-        state.apply_action(move)
-        hist.append(move)
-    ret0 = state.player_return(0) if state.is_terminal() else None
-    if backup == "on-policy" and ret0 is not None:                                           # game_utils.py:200-204
-        reward = ret0 if len(start) % 2 == 0 else -ret0                 # (seen by the player to move at the first recorded ply)
-        for rec in plies:
-            rec["value"] = reward
-            reward *= -1
-    return {"plies": plies, "actions": hist, "ret0": ret0, "counters": cnt, "effects": eff, "mirrored": mirrored, "events": events}
-
-
-def tree_statuses(root, full=False):
-    """The statuses of a tree in the breadth-first order of SelfPlayEngine.read_tree / read_proofs, with the visit counts.
-    full: -> (statuses, counts, parent rows, actions, Q, P) - every column of az_engine_read_tree; the root's row has parent -1
-    and action -1."""
-    order, parent, action, i = [root], [-1], [-1], 0
-    while i < len(order):
-        n = order[i]
-        order.extend(n.children)
-        parent.extend([i] * len(n.children))
-        action.extend(n.actions)
-        i += 1
-    if not full:
-        return [n.status for n in order], [n.N for n in order]
-    return [n.status for n in order], [n.N for n in order], parent, action, [n.Q for n in order], [n.P for n in order]
-
-
-def tree_dump(root):
-    """tree_statuses(full=True) as the arrays of SelfPlayEngine.read_tree (parent, action, N, Q, P) plus status as read_proofs'."""
-    st, n, parent, action, q, p = tree_statuses(root, full=True)
-    return {"parent": np.asarray(parent, dtype=np.int32), "action": np.asarray(action, dtype=np.int32),
-            "N": np.asarray(n, dtype=np.int64), "Q": np.asarray(q, dtype=np.float64), "P": np.asarray(p, dtype=np.float64),
-            "status": np.asarray(st, dtype=np.int8)}
-
-
-def tree_size(root):
-    """-> (nodes, proven nodes) of a tree."""
-    stack, nodes, proven = [root], 0, 0
-    while stack:
-        n = stack.pop()
-        nodes += 1
-        proven += n.status != UNKNOWN
-        stack.extend(n.children)
-    return nodes, proven
-
-
-def event_stats(events):
-    """What the proof events of a game reach -> dict(events, max_levels, max_depth, cross64, cross128: events whose walk up the
-    path goes from depth 64 (128) to depth 63 (127), i.e. depth - levels <= 63 (127) < depth)."""
-    return dict(events=len(events), max_levels=max((lv for _, _, lv in events), default=0),
-                max_depth=max((d for _, d, _ in events), default=0),
-                cross64=sum(1 for _, d, lv in events if d - lv <= 63 < d),
-                cross128=sum(1 for _, d, lv in events if d - lv <= 127 < d))
+play_game = functools.partial(SM.play_game, solver=True)
 
 
 # ------------------------------------------------------------------------------------------------ brute force

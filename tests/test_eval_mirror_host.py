@@ -13,7 +13,7 @@ import torch
 import eval_mirror_cases as EM
 from conftest import ROOT
 from alphazero_openspiel_amd import _lib, games
-from test_playout_cap_host import cap_uniform
+from philox_cases import cap_uniform
 
 
 # ------------------------------------------------------------------------------------------------ 1. ABI surface

@@ -17,7 +17,7 @@ from alphazero_openspiel_amd import games
 from net_cases import drifted_net
 from oracle import fakepolicy
 from playout_cap_cases import check_store as _check, expect as _expect, same_game as _same_game
-from test_playout_cap_host import schedule
+from philox_cases import schedule
 
 pytestmark = pytest.mark.gpu
 

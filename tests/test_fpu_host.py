@@ -1,6 +1,6 @@
-"""First-play urgency without a GPU: the Python model of tests/fpu_cases.py against the older models with the setting off (which
-the older host tests pin to the C oracle), the butterfly sum against a restatement of wave_sum_d and against the left-to-right sum,
-the effects the rule must show on the inputs of tests/test_fpu_gpu.py, the ABI surface and the facade's argument validation."""
+"""First-play urgency without a GPU: the Python model of tests/search_model.py against the C oracle with the setting off (with
+forcing, pruning or the solver on, where the oracle cannot speak, tests/test_search_model_host.py pins it), the butterfly sum
+against a restatement of wave_sum_d and against the left-to-right sum, the effects the rule must show on the inputs of tests/test_fpu_gpu.py, the ABI surface and the facade's argument validation."""
 import ctypes as C
 import math
 import os
@@ -20,26 +20,7 @@ from oracle import fakepolicy
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _same_plies(got, want, what, keys):
-    assert got["actions"] == want["actions"] and got["ret0"] == want["ret0"] and got["counters"] == want["counters"], what
-    assert not any(got["effects"].values()), what
-    for j, (a, b) in enumerate(zip(got["plies"], want["plies"])):
-        for key in keys:
-            assert a[key] == b[key], (what, j, key)
-
-
-# ------------------------------------------------------------------------------------------------ 1. off is the older models
-@pytest.mark.parametrize("idx", range(len(FC.CASES)))
-def test_without_the_setting_the_model_is_forced_playouts_cases_play_game(idx):
-    """k = 0 (play_game_self itself, pinned to the C oracle by tests/test_forced_playouts_host.py) and k = 2 with pruning."""
-    c = FC.CASES[idx]
-    etas, us = FC.draws(c["seed"], c["game"], c["n_games"])
-    for k in (0.0, FC.K):
-        for i, want in enumerate(FC.model_games(idx, k)):
-            got = F.play_game(c["game"], c["salt"], etas[i], us[i], fpu=None, k=k, prune_targets=True, n_playouts=FC.S, **c["kw"])
-            _same_plies(got, want, (idx, k, i), ("raw", "recorded", "actions", "move", "pi", "value", "full"))
-
-
+# ------------------------------------------------------------------------------------------------ 1. off is the reference
 @pytest.mark.parametrize("idx", [i for i, c in enumerate(SC.CASES) if c["start"] is None])
 def test_without_the_setting_the_model_is_the_c_oracle(idx):
     """Straight against play_game_self of the C oracle, on the cases tests/test_solver_host.py pins to it."""
@@ -51,22 +32,10 @@ def test_without_the_setting_the_model_is_the_c_oracle(idx):
         want = orc.play_game_self(lambda b: fakepolicy.fake_eval(b, A, c["salt"]), c["game"], etas=etas[i], us=us[i],
                                   n_playouts=SC.S, **c["kw"])
         assert got["actions"] == want["actions"] and got["ret0"] == want["ret0"] and got["counters"] == want["counters"], (idx, i)
-        assert not any(got["effects"].values())
+        assert not any(got["fpu_effects"].values())
         for j, ply in enumerate(got["plies"]):
             assert ply["raw"] == ply["recorded"] == want["root_cN"][j], (idx, i, j)
             assert ply["pi"] == want["examples"][j][2] and ply["value"] == want["examples"][j][3], (idx, i, j)
-
-
-@pytest.mark.parametrize("idx", range(len(SC.CASES)))
-def test_without_the_setting_the_model_is_solver_cases_play_game(idx):
-    """With the solver on and off, start prefixes included."""
-    c = SC.CASES[idx]
-    etas, us = FC.draws(c["seed"], c["game"], c["n_games"])
-    for solver in (False, True):
-        for i, want in enumerate(SC.model_games(idx, solver=solver)):
-            got = F.play_game(c["game"], c["salt"], etas[i], us[i], fpu=None, solver=solver, n_playouts=SC.S,
-                              start=SC.case_start(c), **c["kw"])
-            _same_plies(got, want, (idx, solver, i), ("raw", "recorded", "actions", "move", "pi", "value", "ran", "status", "full"))
 
 
 # ------------------------------------------------------------------------------------------------ 2. the butterfly sum
@@ -124,7 +93,7 @@ def test_the_searches_of_the_table_are_what_they_are_chosen_for():
         w, dumps = F.search_model(key)
         off, dumps_off = F.search_model(key, None)
         assert len(dumps) == 1 + c["again"] and w["counters"]["sims"] == (1 + c["again"]) * c["n_playouts"]
-        assert all(w["effects"][k] > 0 for k in F.EFFECTS), (key, w["effects"])
+        assert all(w["fpu_effects"][k] > 0 for k in F.EFFECTS), (key, w["fpu_effects"])
         assert w["plies"][0]["raw"] != off["plies"][0]["raw"] or w["plies"][0]["move"] != off["plies"][0]["move"], key
         assert dumps[-1]["N"].tolist() != dumps_off[-1]["N"].tolist(), key
         widest = max(len(k) for k in _nodes(dumps[-1]).values())
@@ -155,8 +124,8 @@ def test_the_games_of_the_table_differ_from_the_games_without_the_setting(key):
     on, off = F.game_models(key), F.game_models(key, None)
     c = F.GAMES[key]
     for k in F.EFFECTS:
-        assert sum(w["effects"][k] for w in on) > 0, (key, k)
-        assert not any(w["effects"][k] for w in off), (key, k)
+        assert sum(w["fpu_effects"][k] for w in on) > 0, (key, k)
+        assert not any(w["fpu_effects"][k] for w in off), (key, k)
     for i, (a, b) in enumerate(zip(on, off)):
         assert a["actions"] != b["actions"] or [p["recorded"] for p in a["plies"]] != [p["recorded"] for p in b["plies"]], (key, i)
     plies = [p for w in on for p in w["plies"]]
@@ -178,7 +147,7 @@ def test_a_zero_reduction_is_not_the_reference():
               max_searches=1)
     zero = F.play_game(c["game"], c["salt"], None, None, fpu=(0.0, 0.0), **kw)
     none = F.play_game(c["game"], c["salt"], None, None, fpu=None, **kw)
-    assert zero["plies"][0]["raw"] != none["plies"][0]["raw"] and any(zero["effects"].values())
+    assert zero["plies"][0]["raw"] != none["plies"][0]["raw"] and any(zero["fpu_effects"].values())
 
 
 # ------------------------------------------------------------------------------------------------ 4. ABI and facade

@@ -2,7 +2,7 @@
 and their Python facade).
 
 References, all bit for bit (there are no tolerances):
-  * the schedule: the pure-Python Philox restatement of tests/test_playout_cap_host.py;
+  * the schedule: the pure-Python Philox restatement of tests/philox_cases.py;
   * the searches: plain engines (no cap) - with p_full = 1 / 0 the whole generation of a plain engine with n_playouts / n_fast
     playouts; with a mixed schedule and fresh trees, ply by ply, a plain engine whose n_playouts is that ply's count and whose
     game-start table puts game id i at game i's position (a fresh-tree search depends on state, ply, game id, seed and count);
@@ -19,7 +19,7 @@ from alphazero_openspiel_amd import games
 from net_cases import drifted_net
 from playout_cap_cases import check_store as _check, expect as _expect, reference_games as _reference_games
 from playout_cap_cases import same as _same, same_game as _same_game
-from test_playout_cap_host import is_full, schedule
+from philox_cases import is_full, schedule
 
 pytestmark = pytest.mark.gpu
 

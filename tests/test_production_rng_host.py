@@ -10,6 +10,7 @@ import pytest
 
 import production_rng_cases as PC
 from alphazero_openspiel_amd import _lib, games
+from philox_cases import cap_uniform
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NS = sorted({n for _, _, _, n in PC.LAW_POSITIONS})          # every number of legal moves the GPU law test meets
@@ -63,7 +64,6 @@ def test_move_uniform_is_keyed_by_seed_halves_game_ply_and_purpose():
               PC.move_uniform(777, 3, 6), PC.move_uniform(777, 3, 5, purpose=3), PC.move_uniform(777, 3, 5, purpose=0),
               PC.move_uniform(777, 5, 3)]
     assert 0.0 <= base < 1.0 and base not in others and len(set(others)) == len(others)
-    from test_playout_cap_host import cap_uniform
     assert base == cap_uniform(777, 3, 5, purpose=1) != cap_uniform(777, 3, 5)
 
 

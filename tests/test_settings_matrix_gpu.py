@@ -50,7 +50,7 @@ def acted(combo, want):
         idle.append("mirror")
     if solver and not any(ply["status"] != F.UNKNOWN for ply in plies):
         idle.append("solver")
-    if fpu and not sum(sum(w["effects"].values()) for w in want):
+    if fpu and not sum(sum(w["fpu_effects"].values()) for w in want):
         idle.append("fpu")
     return idle
 

@@ -15,6 +15,7 @@ import solver_cases as SC
 from alphazero_openspiel_amd import games
 from net_cases import drifted_net
 from oracle import fakepolicy
+from philox_cases import schedule
 from playout_cap_cases import same_game as _same_game
 
 pytestmark = pytest.mark.gpu
@@ -141,12 +142,11 @@ def test_engine_equals_the_model(idx, solver):
 @pytest.mark.parametrize("idx", [0, 1, 4])
 def test_with_a_playout_cap_and_eval_mirror_the_engine_equals_the_model(idx):
     """Solver + playout cap (6, 0.5) + eval mirror p = 0.5.  The model takes the schedule from the Python Philox model of the cap's
-    draw (tests/test_playout_cap_host.py) and the orientation of every request from the coin model of tests/eval_mirror_cases.py;
+    draw (tests/philox_cases.py) and the orientation of every request from the coin model of tests/eval_mirror_cases.py;
     the coin's index is the count of playouts the search has run, from 0 in a fast search too, and a search that ends early at a
     proven root - a fast one included - ends on that count.  Kept trees (cases 0 and 4), fresh ones (case 1), both games."""
     import eval_mirror_cases as EM
     from mirror_cases import action_mirror_table
-    from test_playout_cap_host import schedule
     case = SC.CASES[idx]
     n, p0 = case["n_games"], len(SC.case_start(case))
     _, mp, _, _ = FC.geometry(case["game"])

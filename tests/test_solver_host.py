@@ -29,7 +29,7 @@ def test_model_without_the_solver_is_play_game_self(idx):
                                   n_playouts=SC.S, **case["kw"])
         assert got["actions"] == want["actions"] and got["ret0"] == want["ret0"], (idx, i)
         assert got["counters"] == want["counters"], (idx, i)
-        assert not any(got["effects"].values())
+        assert not any(got["solver_effects"].values())
         for j, ply in enumerate(got["plies"]):
             assert ply["raw"] == ply["recorded"] == want["root_cN"][j] and ply["status"] == SC.UNKNOWN, (idx, i, j)
             assert ply["pi"] == want["examples"][j][2] and ply["value"] == want["examples"][j][3], (idx, i, j)
@@ -57,7 +57,7 @@ def test_the_rules_bite_on_the_inputs_of_the_gpu_test():
         on, off = SC.model_games(idx, True), SC.model_games(idx, False)
         for a, b in zip(on, off):
             for k in SC.EFFECTS:
-                total[k] += a["effects"][k]
+                total[k] += a["solver_effects"][k]
             moves_differ += a["actions"] != b["actions"]
             assert a["counters"]["sims"] == sum(p["ran"] for p in a["plies"]) <= SC.S * len(a["plies"])
             for ply in a["plies"]:
@@ -70,7 +70,7 @@ def test_the_rules_bite_on_the_inputs_of_the_gpu_test():
     assert all(total[k] > 0 for k in SC.EFFECTS), total
     assert moves_differ > 0
     assert 42 - len(SC.case_start(SC.CASES[4])) <= 4 and 42 - len(SC.case_start(SC.CASES[0])) <= 10
-    draw = [a["effects"]["draw_root"] for a in SC.model_games(4, True)]
+    draw = [a["solver_effects"]["draw_root"] for a in SC.model_games(4, True)]
     assert sum(draw) > 0                                                 # the DRAW root: connect_four, at most 4 empty cells
 
 

@@ -37,7 +37,7 @@ def test_model_without_the_solver_builds_the_oracles_trees(key):
             prev = want[k - 1]
             _same_tree(ply["kept"], PS.sub_bfs(prev["tree"], 1 + prev["root"]["actions"].index(prev["move"])), (key, "kept", k))
             assert ply["kept_nodes"] == len(ply["kept"]["N"])
-    assert not any(got["effects"].values()) and not got["events"]
+    assert not any(got["solver_effects"].values()) and not got["events"]
     print(key, "searches", len(want), "largest tree", max(p["nodes"] for p in got["plies"]))
 
 
@@ -74,8 +74,8 @@ def test_every_status_of_the_late_case_is_the_negamax_value():
 # ------------------------------------------------------------------------------------------------ what the cases reach
 def _summary(w):
     plies = w["plies"]
-    return dict(SC.event_stats(w["events"]), loss_skipped=w["effects"]["loss_skipped"],
-                stopped_nonterminal=w["effects"]["stopped_nonterminal"], ran=[p["ran"] for p in plies],
+    return dict(SC.event_stats(w["events"]), loss_skipped=w["solver_effects"]["loss_skipped"],
+                stopped_nonterminal=w["solver_effects"]["stopped_nonterminal"], ran=[p["ran"] for p in plies],
                 kept_proven=[p["kept_proven"] for p in plies], largest_tree=max(p["nodes"] for p in plies))
 
 
@@ -97,7 +97,7 @@ def test_scale_cases_reach_what_they_are_for(key):
     assert any(p["status"] != SC.UNKNOWN and p["ran"] < c["n_playouts"] for p in plies)
     kept_proven_roots = [p for p in plies[1:] if p["kept"]["status"][0] != SC.UNKNOWN]
     assert len(kept_proven_roots) >= 2 and all(p["ran"] == 0 for p in kept_proven_roots)
-    assert len(kept_proven_roots) == w["effects"]["kept_proven_root"]
+    assert len(kept_proven_roots) == w["solver_effects"]["kept_proven_root"]
     for p in plies[1:]:                                                  # the bookkeeping agrees with the dumps
         assert p["kept_proven"] == int((p["kept"]["status"] != SC.UNKNOWN).sum()) and p["kept_nodes"] == len(p["kept"]["N"])
     # the solver's sequence is not the plain one
@@ -151,10 +151,10 @@ def _terminal_playouts(key):
 def test_the_deep_game_keeps_proven_chains_through_every_re_rooting():
     w = SC.deep_game_model()
     st = SC.event_stats(w["events"])
-    print(len(w["plies"]), st, w["effects"])
+    print(len(w["plies"]), st, w["solver_effects"])
     assert st["cross64"] >= 10 and st["max_depth"] >= 90
     assert all(p["kept_proven"] > 0 for p in w["plies"][1:]) and max(p["kept_proven"] for p in w["plies"]) >= 1000
-    assert w["effects"]["kept_proven_root"] >= 1 and w["ret0"] is not None
+    assert w["solver_effects"]["kept_proven_root"] >= 1 and w["ret0"] is not None
     assert w["actions"] != SC.deep_game_model(solver=False)["actions"] or \
         [p["raw"] for p in w["plies"]] != [p["raw"] for p in SC.deep_game_model(solver=False)["plies"]]
 
@@ -172,6 +172,6 @@ def test_whole_games_and_the_small_pool_fit(key):
     assert compactions >= 1
     assert cap >= need + max(p["kept_nodes"] for w in games for p in w["plies"])
     for w in games:
-        assert w["effects"]["kept_proven_root"] >= 1 and any(0 < p["ran"] < c["n_playouts"] or p["ran"] == 0 for p in w["plies"])
+        assert w["solver_effects"]["kept_proven_root"] >= 1 and any(0 < p["ran"] < c["n_playouts"] or p["ran"] == 0 for p in w["plies"])
         assert any(p["raw"] != p["recorded"] for p in w["plies"])
-    assert sum(w["effects"]["loss_skipped"] for w in games) >= 500
+    assert sum(w["solver_effects"]["loss_skipped"] for w in games) >= 500
