@@ -175,6 +175,8 @@ PROTOTYPES = [
     ("az_replay_append_device_starts", C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp]),
     ("az_replay_append_device_kept", C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp]),
     ("az_replay_dedupe", C.c_int, [_vp, _vp]),
+    ("az_replay_dedupe_positions", C.c_int, [_vp, C.c_int32, _vp]),
+    ("az_replay_unique_counts_device", C.c_int, [_vp, _vp, C.c_int64, _vp]),
     ("az_replay_sample", C.c_int, [_vp, _vp, C.c_int32, C.c_uint64, _vp, _vp, _vp, _vp]),
     ("az_replay_sample_sym", C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_uint64, _vp, _vp, _vp, _vp]),
     ("az_replay_gather_states", C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp]),

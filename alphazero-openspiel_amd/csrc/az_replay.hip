@@ -11,6 +11,11 @@
 // float64 (one rounding per addition, as `[sum(x) for x in zip(acc, item)]` does), divides by the count and
 // writes the average back into the first member (the reference's aliasing side effect, train.py:191-197)
 // -> unique list = first members in ascending buffer order (dict insertion order).
+//
+// az_replay_dedupe_positions (no counterpart in the reference) is the same pass grouped by the position instead of the history:
+// canonical (c0, c1, ply & 1) per example -> three stable sorts on the full key (exact: nothing is hashed) -> the same segment
+// scan and the same averaging body, which reads a member stored in the other orientation than the first through
+// az_mirror_action.  Both passes leave the members' count of every group for az_replay_unique_counts_device.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <string.h>
@@ -39,6 +44,10 @@ struct az_replay {
     int32_t *ply = nullptr;
     double *z = nullptr, *pi = nullptr;
     int64_t *unique = nullptr; // [n_unique] logical indices of the first occurrences, ascending
+    // count[i] = the members of the group whose first occurrence is logical index i, written by the last dedupe of either kind
+    // (the other entries are stale); valid while epoch == count_epoch (az_replay_unique_counts_device)
+    int32_t *count = nullptr;
+    int64_t count_epoch = -1;
     // az_replay_refresh_from_roots: claim[phys] = the lowest slot that refreshes the example in the running call (REFRESH_FREE
     // between calls), sel[slot] = the example a slot refreshes (-1: none), refreshed = the call's count
     unsigned int *claim = nullptr;
@@ -74,6 +83,7 @@ extern "C" int az_replay_destroy(az_replay *r) {
     (void)hipFree(r->z);
     (void)hipFree(r->pi);
     (void)hipFree(r->unique);
+    (void)hipFree(r->count);
     (void)hipFree(r->claim);
     (void)hipFree(r->sel);
     (void)hipFree(r->refreshed);
@@ -125,7 +135,8 @@ extern "C" int az_replay_create(const az_replay_config *cfg, az_replay **out) {
               hipMalloc((void **)&r->bb0, n * 8) == hipSuccess &&
               hipMalloc((void **)&r->bb1, n * 8) == hipSuccess && hipMalloc((void **)&r->ply, n * 4) == hipSuccess &&
               hipMalloc((void **)&r->z, n * 8) == hipSuccess && hipMalloc((void **)&r->pi, n * 8 * (size_t)r->A) == hipSuccess &&
-              hipMalloc((void **)&r->unique, n * 8) == hipSuccess && hipMalloc((void **)&r->claim, n * 4) == hipSuccess &&
+              hipMalloc((void **)&r->unique, n * 8) == hipSuccess && hipMalloc((void **)&r->count, n * 4) == hipSuccess &&
+              hipMalloc((void **)&r->claim, n * 4) == hipSuccess &&
               hipMemset(r->claim, 0xFF, n * 4) == hipSuccess && hipMalloc((void **)&r->refreshed, 8) == hipSuccess;
     if (!ok) {
         g_replay_err = "hipMalloc of the replay store failed";
@@ -600,33 +611,107 @@ __global__ void seg_flags_kernel(const uint64_t *skey, long long n, unsigned cha
     long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j < n) flag[j] = (j == 0 || skey[j] != skey[j - 1]) ? 1 : 0;
 }
-// one wave per segment: members sidx[seg_start[s] .. seg_start[s+1]) are in buffer order (stable sort)
-__global__ void seg_average_kernel(const long long *seg_start, long long n_seg, long long n, const long long *sidx, long long head,
-                                   long long cap, int A, double *pi, double *z, unsigned char *first_flag, const uint64_t *key2,
-                                   const uint64_t *bb0, const uint64_t *bb1, const int32_t *ply, unsigned int *faults) {
+// The position rule (az_replay_dedupe_positions): one thread per stored example writes its canonical triple and its flip bit,
+// by logical index.  mirror: the smaller of (bb0, bb1) and its mirror image as unsigned pairs, bb0 the major word; flip = the
+// mirror image is strictly smaller (a position that is its own mirror image keeps flip = 0).  GAME is a template argument as in
+// replay_sample_sym_kernel: az_mirror_bits differs per game.
+template <int GAME>
+__global__ void canon_keys_kernel(const uint64_t *bb0, const uint64_t *bb1, const int32_t *ply, long long head, long long cap, long long n,
+                                  AzGeom geom, int mirror, uint64_t *c0, uint64_t *c1, uint64_t *par, unsigned char *flip) {
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    long long phys = (head + i) % cap;
+    AzState s;
+    s.bb0 = bb0[phys];
+    s.bb1 = bb1[phys];
+    s.ply = ply[phys];
+    bool f = false;
+    if (mirror) {
+        const AzState m = az_mirror_state<GAME>(s, geom);
+        f = m.bb0 < s.bb0 || (m.bb0 == s.bb0 && m.bb1 < s.bb1);
+        if (f) s = m;
+    }
+    c0[i] = s.bb0;
+    c1[i] = s.bb1;
+    par[i] = (uint64_t)(s.ply & 1);
+    flip[i] = f ? 1 : 0;
+}
+// the next LSD pass's keys: word[] (by logical index) in the order the passes so far have given
+__global__ void gather_word_kernel(const uint64_t *word, const long long *idx, long long n, uint64_t *out) {
+    long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) out[j] = word[idx[j]];
+}
+// a segment starts where any of the three words differs from the previous record's: exact, there is no collision case
+__global__ void seg_flags3_kernel(const uint64_t *c0, const uint64_t *c1, const uint64_t *par, const long long *sidx, long long n,
+                                  unsigned char *flag) {
+    long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    bool start = j == 0;
+    if (!start) {
+        const long long i = sidx[j], p = sidx[j - 1];
+        start = c0[i] != c0[p] || c1[i] != c1[p] || par[i] != par[p];
+    }
+    flag[j] = start ? 1 : 0;
+}
+
+struct SegArgs {
+    const long long *seg_start, *sidx;
+    long long n_seg, n, head, cap;
+    int A;
+    double *pi, *z;
+    unsigned char *first_flag;
+    int32_t *count; // [logical index of a first occurrence] the group's members
+    // the history rule: the exact-key guard
+    const uint64_t *key2, *bb0, *bb1;
+    const int32_t *ply;
+    unsigned int *faults;
+    // the position rule: flip bit by logical index, and the board for az_mirror_action
+    const unsigned char *flip;
+    AzGeom geom;
+};
+#define SEG_RULE_HISTORY -1 // (the position rule's RULE is the game, AZG_*)
+// One wave per segment: members sidx[seg_start[s] .. seg_start[s+1]) are in buffer order (stable sort).  One body for both rules:
+//   RULE == SEG_RULE_HISTORY : every member is checked against the first (the 64-bit key is a hash), action a adds up component a
+//   RULE == the game         : nothing to check (the sort key is the position itself), and a member stored in the other
+//                              orientation than the first adds its component az_mirror_action(a)
+template <int RULE> __global__ void seg_average_kernel(SegArgs g) {
+    constexpr int GAME = RULE == SEG_RULE_HISTORY ? AZG_CONNECT_FOUR : RULE; // (names a function the history rule never calls)
     long long s = (long long)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
     int lane = threadIdx.x & 63;
-    if (s >= n_seg) return;
-    long long j0 = seg_start[s], j1 = s + 1 < n_seg ? seg_start[s + 1] : n;
+    if (s >= g.n_seg) return;
+    const long long head = g.head, cap = g.cap;
+    const long long *sidx = g.sidx;
+    const int A = g.A;
+    double *pi = g.pi, *z = g.z;
+    long long j0 = g.seg_start[s], j1 = s + 1 < g.n_seg ? g.seg_start[s + 1] : g.n;
     long long first = sidx[j0];
-    if (lane == 0) first_flag[first] = 1;
     long long cnt = j1 - j0;
+    if (lane == 0) {
+        g.first_flag[first] = 1;
+        g.count[first] = (int32_t)cnt;
+    }
     if (cnt == 1) return; // x / 1 == x: nothing to write
     long long pf = (head + first) % cap;
-    { // exact-key guard: every member must be the same history as the first (same fingerprint, ply and position)
+    if (RULE == SEG_RULE_HISTORY) { // exact-key guard: every member must be the same history as the first (same fingerprint, ply and position)
         bool bad = false;
         for (long long j = j0 + 1 + lane; j < j1; j += 64) {
             long long pm = (head + sidx[j]) % cap;
-            bad |= key2[pm] != key2[pf] || ply[pm] != ply[pf] || bb0[pm] != bb0[pf] || bb1[pm] != bb1[pf];
+            bad |= g.key2[pm] != g.key2[pf] || g.ply[pm] != g.ply[pf] || g.bb0[pm] != g.bb0[pf] || g.bb1[pm] != g.bb1[pf];
         }
         if (__ballot(bad) != 0) { // (wave-uniform) the segment is left untouched: nothing is averaged across different histories
-            if (lane == 0) atomicOr(faults, AZ_REPLAY_FAULT_KEY_COLLISION);
+            if (lane == 0) atomicOr(g.faults, AZ_REPLAY_FAULT_KEY_COLLISION);
             return;
         }
     }
+    const unsigned char flip_first = RULE == SEG_RULE_HISTORY ? 0 : g.flip[first];
     for (int a = lane; a < A; a += 64) { // flattened_buffer_dict[key][2] = [sum(x) for x in zip(acc, item[2])]
+        const int am = RULE == SEG_RULE_HISTORY ? a : az_mirror_action<GAME>(a, g.geom);
         double acc = pi[(size_t)pf * A + a];
-        for (long long j = j0 + 1; j < j1; j++) acc = acc + pi[(size_t)((head + sidx[j]) % cap) * A + a];
+        for (long long j = j0 + 1; j < j1; j++) {
+            const long long m = sidx[j];
+            const int am_j = RULE == SEG_RULE_HISTORY || g.flip[m] == flip_first ? a : am;
+            acc = acc + pi[(size_t)((head + m) % cap) * A + am_j];
+        }
         pi[(size_t)pf * A + a] = acc / (double)cnt;
     }
     if (lane == 0) { // flattened_buffer_dict[key][3] += item[3]
@@ -641,23 +726,28 @@ __global__ void iota_kernel(long long *p, long long n) {
     if (i < n) p[i] = i;
 }
 
-extern "C" int az_replay_dedupe(az_replay *r, void *stream) {
-    if (!r) return AZ_E_INVALID;
-    hipStream_t st = (hipStream_t)stream;
+// Both dedupe entries.  by_position == false: the reference's rule, grouping by the 64-bit history key (one sort, the exact-key
+// guard).  by_position == true: grouping by the canonical triple (three stable LSD passes, no collision case; the
+// AZ_REPLAY_FAULT_KEY_COLLISION flag is neither raised nor cleared).  Everything after the grouping is one code path.
+static int dedupe_common(az_replay *r, hipStream_t st, bool by_position, int mirror) {
     RCHK(r, hipSetDevice(r->cfg.device));
     long long n = r->n;
     r->n_unique = 0;
     r->epoch++;
     // the collision flag describes THIS pass (an earlier one may have tripped on examples that have since been evicted)
-    hipLaunchKernelGGL(clear_fault_kernel, dim3(1), dim3(1), 0, st, r->faults, AZ_REPLAY_FAULT_KEY_COLLISION);
-    if (n == 0) return AZ_OK;
-    uint64_t *k_in = nullptr, *k_out = nullptr;
+    if (!by_position) hipLaunchKernelGGL(clear_fault_kernel, dim3(1), dim3(1), 0, st, r->faults, AZ_REPLAY_FAULT_KEY_COLLISION);
+    if (n == 0) {
+        r->count_epoch = r->epoch; // (an empty unique list has its counts: none)
+        return AZ_OK;
+    }
+    uint64_t *k_in = nullptr, *k_out = nullptr, *canon = nullptr; // canon: c0 | c1 | parity, n words each, by logical index
     long long *i_in = nullptr, *i_out = nullptr, *seg_start = nullptr, *iota = nullptr, *d_count = nullptr;
-    unsigned char *flag = nullptr, *first_flag = nullptr;
+    unsigned char *flag = nullptr, *first_flag = nullptr, *flip = nullptr;
     void *tmp = nullptr;
     auto cleanup = [&]() {
         (void)hipFree(k_in); (void)hipFree(k_out); (void)hipFree(i_in); (void)hipFree(i_out); (void)hipFree(seg_start);
         (void)hipFree(iota); (void)hipFree(d_count); (void)hipFree(flag); (void)hipFree(first_flag); (void)hipFree(tmp);
+        (void)hipFree(canon); (void)hipFree(flip);
     };
 #define DCHK(call)                                                         \
     do {                                                                   \
@@ -673,12 +763,45 @@ extern "C" int az_replay_dedupe(az_replay *r, void *stream) {
     DCHK(hipMalloc((void **)&seg_start, n * 8)); DCHK(hipMalloc((void **)&iota, n * 8));
     DCHK(hipMalloc((void **)&d_count, 8)); DCHK(hipMalloc((void **)&flag, n)); DCHK(hipMalloc((void **)&first_flag, n));
     unsigned nb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(gather_keys_kernel, dim3(nb), dim3(256), 0, st, r->key, (long long)r->head, (long long)r->cap, n, k_in, i_in);
     size_t tb = 0;
-    DCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k_in, k_out, i_in, i_out, (int)n, 0, 64, st));
-    DCHK(hipMalloc(&tmp, tb));
-    DCHK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, k_in, k_out, i_in, i_out, (int)n, 0, 64, st)); // LSD radix sort: stable
-    hipLaunchKernelGGL(seg_flags_kernel, dim3(nb), dim3(256), 0, st, k_out, n, flag);
+    // (keys, indices) sorted on the keys' bits [0, end_bit): an LSD radix sort, stable.  The scratch buffer grows as asked for.
+    auto sort_pairs = [&](const uint64_t *kin, uint64_t *kout, const long long *iin, long long *iout, int end_bit) -> hipError_t {
+        size_t need = 0;
+        hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, need, kin, kout, iin, iout, (int)n, 0, end_bit, st);
+        if (e != hipSuccess) return e;
+        if (need > tb) {
+            (void)hipFree(tmp);
+            tmp = nullptr;
+            tb = 0;
+            if ((e = hipMalloc(&tmp, need)) != hipSuccess) return e;
+            tb = need;
+        }
+        return hipcub::DeviceRadixSort::SortPairs(tmp, need, kin, kout, iin, iout, (int)n, 0, end_bit, st);
+    };
+    if (!by_position) {
+        hipLaunchKernelGGL(gather_keys_kernel, dim3(nb), dim3(256), 0, st, r->key, (long long)r->head, (long long)r->cap, n, k_in, i_in);
+        DCHK(sort_pairs(k_in, k_out, i_in, i_out, 64));
+        hipLaunchKernelGGL(seg_flags_kernel, dim3(nb), dim3(256), 0, st, k_out, n, flag);
+    } else {
+        DCHK(hipMalloc((void **)&canon, n * 24));
+        DCHK(hipMalloc((void **)&flip, n));
+        uint64_t *c0 = canon, *c1 = canon + n, *par = canon + 2 * n;
+        if (r->cfg.game == AZG_CONNECT_FOUR)
+            hipLaunchKernelGGL(canon_keys_kernel<AZG_CONNECT_FOUR>, dim3(nb), dim3(256), 0, st, r->bb0, r->bb1, r->ply, (long long)r->head,
+                               (long long)r->cap, n, r->geom, mirror, c0, c1, par, flip);
+        else
+            hipLaunchKernelGGL(canon_keys_kernel<AZG_BREAKTHROUGH>, dim3(nb), dim3(256), 0, st, r->bb0, r->bb1, r->ply, (long long)r->head,
+                               (long long)r->cap, n, r->geom, mirror, c0, c1, par, flip);
+        // three stable passes, the minor word first: parity, then c1, then c0.  Each pass's keys are gathered in the order the
+        // passes before it gave; the indices ping-pong between i_in and i_out and end in i_out.
+        hipLaunchKernelGGL(iota_kernel, dim3(nb), dim3(256), 0, st, i_in, n);
+        DCHK(sort_pairs(par, k_out, i_in, i_out, 1));
+        hipLaunchKernelGGL(gather_word_kernel, dim3(nb), dim3(256), 0, st, c1, i_out, n, k_in);
+        DCHK(sort_pairs(k_in, k_out, i_out, i_in, 64));
+        hipLaunchKernelGGL(gather_word_kernel, dim3(nb), dim3(256), 0, st, c0, i_in, n, k_in);
+        DCHK(sort_pairs(k_in, k_out, i_in, i_out, 64));
+        hipLaunchKernelGGL(seg_flags3_kernel, dim3(nb), dim3(256), 0, st, c0, c1, par, i_out, n, flag);
+    }
     hipLaunchKernelGGL(iota_kernel, dim3(nb), dim3(256), 0, st, iota, n);
     size_t tb2 = 0;
     DCHK(hipcub::DeviceSelect::Flagged(nullptr, tb2, iota, flag, seg_start, d_count, (int)n, st));
@@ -693,8 +816,29 @@ extern "C" int az_replay_dedupe(az_replay *r, void *stream) {
     DCHK(hipMemcpyAsync(&n_seg, d_count, 8, hipMemcpyDeviceToHost, st));
     DCHK(hipStreamSynchronize(st));
     DCHK(hipMemsetAsync(first_flag, 0, n, st));
-    hipLaunchKernelGGL(seg_average_kernel, dim3((unsigned)((n_seg + 3) / 4)), dim3(256), 0, st, seg_start, n_seg, n, i_out,
-                       (long long)r->head, (long long)r->cap, r->A, r->pi, r->z, first_flag, r->key2, r->bb0, r->bb1, r->ply, r->faults);
+    SegArgs sa;
+    sa.seg_start = seg_start;
+    sa.sidx = i_out;
+    sa.n_seg = n_seg;
+    sa.n = n;
+    sa.head = r->head;
+    sa.cap = r->cap;
+    sa.A = r->A;
+    sa.pi = r->pi;
+    sa.z = r->z;
+    sa.first_flag = first_flag;
+    sa.count = r->count;
+    sa.key2 = r->key2;
+    sa.bb0 = r->bb0;
+    sa.bb1 = r->bb1;
+    sa.ply = r->ply;
+    sa.faults = r->faults;
+    sa.flip = flip;
+    sa.geom = r->geom;
+    const dim3 seg_grid((unsigned)((n_seg + 3) / 4)), seg_block(256);
+    if (!by_position) hipLaunchKernelGGL(seg_average_kernel<SEG_RULE_HISTORY>, seg_grid, seg_block, 0, st, sa);
+    else if (r->cfg.game == AZG_CONNECT_FOUR) hipLaunchKernelGGL(seg_average_kernel<AZG_CONNECT_FOUR>, seg_grid, seg_block, 0, st, sa);
+    else hipLaunchKernelGGL(seg_average_kernel<AZG_BREAKTHROUGH>, seg_grid, seg_block, 0, st, sa);
     DCHK(hipcub::DeviceSelect::Flagged(nullptr, tb2, iota, first_flag, (long long *)r->unique, d_count, (int)n, st));
     if (tb2 > tb) {
         (void)hipFree(tmp);
@@ -714,11 +858,52 @@ extern "C" int az_replay_dedupe(az_replay *r, void *stream) {
         r->err = "internal: unique count mismatch";
         return AZ_E_DEVICE;
     }
-    if (faults & AZ_REPLAY_FAULT_KEY_COLLISION) {
+    if (!by_position && (faults & AZ_REPLAY_FAULT_KEY_COLLISION)) {
         r->err = "remove_duplicates: two different histories share a 64-bit key (they would have been averaged); not deduplicated";
         return AZ_E_DEVICE;
     }
     r->n_unique = n_unique;
+    r->count_epoch = r->epoch;
+    return AZ_OK;
+}
+
+extern "C" int az_replay_dedupe(az_replay *r, void *stream) {
+    if (!r) return AZ_E_INVALID;
+    return dedupe_common(r, (hipStream_t)stream, false, 0);
+}
+
+extern "C" int az_replay_dedupe_positions(az_replay *r, int32_t mirror, void *stream) {
+    if (!r) return AZ_E_INVALID;
+    if (mirror != 0 && mirror != 1) {
+        r->err = "az_replay_dedupe_positions: mirror must be 0 or 1, not " + std::to_string(mirror);
+        return AZ_E_INVALID;
+    }
+    return dedupe_common(r, (hipStream_t)stream, true, mirror);
+}
+
+__global__ void unique_counts_kernel(const int64_t *unique, const int32_t *count, long long n, int32_t *out) {
+    long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u < n) out[u] = count[unique[u]];
+}
+
+extern "C" int az_replay_unique_counts_device(az_replay *r, int32_t *counts_out_dev, int64_t n, void *stream) {
+    if (!r) return AZ_E_INVALID;
+    if (r->count_epoch != r->epoch) {
+        r->err = r->count_epoch < 0 ? "az_replay_unique_counts_device before any dedupe"
+                                    : "az_replay_unique_counts_device: the store has changed (append or capacity) since the last dedupe, or "
+                                      "that dedupe failed";
+        return AZ_E_STATE;
+    }
+    if (n != r->n_unique || (n > 0 && !counts_out_dev)) {
+        r->err = "az_replay_unique_counts_device: n = " + std::to_string(n) + " is not n_unique = " + std::to_string(r->n_unique) +
+                 " (or counts_out_dev is null)";
+        return AZ_E_INVALID;
+    }
+    if (n == 0) return AZ_OK;
+    RCHK(r, hipSetDevice(r->cfg.device));
+    hipLaunchKernelGGL(unique_counts_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, r->unique, r->count,
+                       (long long)n, counts_out_dev);
+    RCHK(r, hipGetLastError());
     return AZ_OK;
 }
 

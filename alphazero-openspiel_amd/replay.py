@@ -14,6 +14,19 @@ from . import _lib
 from .games import Game
 
 
+def dedupe_mode(by="history", mirror=False):
+    """The arguments of DeviceReplay.dedupe -> None for the history rule (az_replay_dedupe), else the `mirror` argument of
+    az_replay_dedupe_positions (0 or 1).  ValueError for an unknown rule, and for mirror=True with by="history": a history has
+    no mirror key."""
+    if by not in ("history", "position"):
+        raise ValueError("dedupe: by must be 'history' or 'position', not %r" % (by,))
+    if by == "history":
+        if mirror:
+            raise ValueError("dedupe: mirror=True needs by='position' - a history has no mirror key")
+        return None
+    return 1 if mirror else 0
+
+
 class DeviceReplay:
     def __init__(self, game_name, max_games, device=0, max_examples=None):
         self.lib = _lib.load()
@@ -120,10 +133,28 @@ class DeviceReplay:
             rc = self.lib.az_replay_append_device(*head, int(start_ply), self._stream())
         self._check(rc)
 
-    def dedupe(self):
-        """Trainer.remove_duplicates over the flattened buffer; returns the number of unique examples."""
-        self._check(self.lib.az_replay_dedupe(self._h, self._stream()))
+    def dedupe(self, by="history", mirror=False):
+        """Trainer.remove_duplicates over the flattened buffer; returns the number of unique examples.
+        by="history" (the reference's rule): examples merge when their action histories are equal.
+        by="position": examples merge when their positions (bb0, bb1, ply & 1) are equal, whatever the move order that led
+        there; with mirror=True a position and its left-right mirror image merge too, the mirrored member's policy mapped
+        through the action mirror (az_replay_dedupe_positions, include/az_replay.h).  The average goes into the first occurrence
+        in its own orientation; sample(), gather_states(), gather_forks() and the refreshes read that record as always."""
+        mode = dedupe_mode(by, mirror)
+        if mode is None:
+            self._check(self.lib.az_replay_dedupe(self._h, self._stream()))
+        else:
+            self._check(self.lib.az_replay_dedupe_positions(self._h, mode, self._stream()))
         return self.stats()["n_unique"]
+
+    def unique_counts(self):
+        """-> int32 device tensor [n_unique]: how many stored examples went into each entry of the de-duplicated list (the last
+        dedupe() of either kind).  RuntimeError (AZ_E_STATE) before a dedupe and after an append or a capacity change."""
+        # n_unique from a read-back of no rows: stats() would report - and clear - fault flags that are not this call's
+        n = int(self._check(self.lib.az_replay_read_unique(self._h, 0, None, None, None, None, None, None)))
+        out = torch.empty((n,), dtype=torch.int32, device=self.device)
+        self._check(self.lib.az_replay_unique_counts_device(self._h, C.c_void_p(out.data_ptr()) if n else None, n, self._stream()))
+        return out
 
     def stats(self):
         s = _lib.AzReplayStats()

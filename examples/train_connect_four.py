@@ -68,7 +68,12 @@ def main():
                     help="first-play urgency reduction, as Lc0 and KataGo select: an unvisited child is valued at its parent's value "
                          "minus R * sqrt(explored prior mass) (R_ROOT at the root, default 0) in place of the reference's 0, in "
                          "self-play and in the searches of --reanalyse and --fork (e.g. 0.3)")
+    ap.add_argument("--merge-positions", default="off", choices=["off", "plain", "mirror"],
+                    help="what the dedupe before training merges: off = examples with equal action histories, as the reference; "
+                         "plain = examples of one position (bitboards and side to move) whatever the move order that led there; "
+                         "mirror = also a position and its left-right mirror image, the policy mapped with the board")
     a = ap.parse_args()
+    dedupe = {"off": dict(), "plain": dict(by="position"), "mirror": dict(by="position", mirror=True)}[a.merge_positions]
     if a.playout_cap and a.continuous:
         ap.error("--playout-cap is not available with --continuous (the mask of full-search moves does not travel with a take)")
     try:  # one parser and one set of rules for the five settings (alphazero_openspiel_amd/search_settings.py)
@@ -116,7 +121,7 @@ def main():
         if gen % 2 == 0 and n_buffer < n_buffer_max:                       # Trainer.update_buffer_size
             n_buffer += a.games
         store.set_capacity(n_buffer)
-        n_unique = store.dedupe()
+        n_unique = store.dedupe(**dedupe)
         if a.fork:                                                         # store -> engine -> store, on the device
             t_fk = time.perf_counter()
             if forker is None:
@@ -125,7 +130,7 @@ def main():
             else:
                 forker.set_net(net)
             forker.fork(n=a.fork, seed=gen)
-            n_before, n_unique = n_unique, store.dedupe()
+            n_before, n_unique = n_unique, store.dedupe(**dedupe)
             print("gen %d: forked %d games from %d unique positions in %.2f s -> %d unique" %
                   (gen, a.fork, n_before, time.perf_counter() - t_fk, n_unique), flush=True)
         t_re = time.perf_counter()
@@ -152,10 +157,10 @@ def main():
         torch.cuda.synchronize()
         t_train = time.perf_counter() - t1
         st = store.stats()
-        print("gen %d: %d games (%.0f plies avg, %.2f M sims) in %.2f s | buffer %d games / %d examples -> %d unique | "
+        print("gen %d: %d games (%.0f plies avg, %.2f M sims) in %.2f s | buffer %d games / %d examples -> %d unique (merge-positions %s) | "
               "%d batches in %.2f s, loss_p %.4f loss_v %.4f" %
               (gen, a.games, prog["moves"] / a.games, prog["sims"] / 1e6, t_play, st["n_games"], st["n_examples"], n_unique,
-               a.batches, t_train, lp, lv), flush=True)
+               a.merge_positions, a.batches, t_train, lp, lv), flush=True)
         if a.eval_every and gen % a.eval_every == 0:                        # Trainer.test_agent (train.py:238-270)
             net.eval()
             t2 = time.perf_counter()

@@ -44,7 +44,7 @@ typedef struct az_replay_config {
 
 typedef struct az_replay_stats {
     int64_t n_games, n_examples; /* currently stored */
-    int64_t n_unique;            /* after the last az_replay_dedupe (0 before) */
+    int64_t n_unique;            /* after the last az_replay_dedupe / az_replay_dedupe_positions (0 before) */
     int64_t games_dropped;       /* total FIFO evictions */
     int64_t fault_flags;         /* AZ_REPLAY_FAULT_* raised on the device since the last az_replay_stats_get (reading clears them) */
 } az_replay_stats;
@@ -147,6 +147,58 @@ int az_replay_append_device_kept(az_replay *r, const void *dev_buf, int64_t n_ga
  * 64-bit hash of the history, the ply and the position): a mismatch - two different histories under one key, which the
  * reference, keying on the exact information-state string (train.py:177), would keep apart - returns AZ_E_DEVICE. */
 int az_replay_dedupe(az_replay *r, void *stream);
+
+/*
+ * Merging transpositions and mirror images (replaces nothing in the reference: Trainer.remove_duplicates keys on the history
+ * alone).  The net sees (bb0, bb1, ply & 1) only, both games transpose and both are left-right symmetric, so examples of one
+ * position reached along different histories - or of a position and its mirror image - are labels of one input.
+ *
+ * az_replay_dedupe_positions is az_replay_dedupe with another equivalence:
+ *
+ * GROUP.  Two stored examples are the same iff their canonical triples (c0, c1, ply & 1) are equal.
+ *   - With mirror == 0, (c0, c1) = (bb0, bb1) as stored.
+ *   - With mirror != 0, let m = az_mirror_state(s).  flip = 1 iff (m.bb0, m.bb1) < (s.bb0, s.bb1), compared as unsigned pairs
+ *     with bb0 the major word.  (c0, c1) is the smaller pair.
+ *   - A position that is its own mirror image has flip = 0.
+ *   - mirror is 0 or 1.  Anything else returns AZ_E_INVALID (and the store, its epoch included, is as it was).
+ *
+ * GROUPING IS EXACT, NOT HASHED.  The records are sorted on the full triple with three stable LSD passes - parity, then c1,
+ * then c0 - and a segment starts where any of the three words differs from the previous record's.  This pass has no collision
+ * case: it neither raises nor clears AZ_REPLAY_FAULT_KEY_COLLISION.
+ *
+ * ORDER.  Members of a group are in buffer order (the sort is stable).  The unique list is in first-occurrence order, as
+ * az_replay_dedupe's.
+ *
+ * AVERAGE.  All arithmetic is float64, one rounding per operation, in the reference's order:
+ *   - acc = pi_first[a];
+ *   - for every later member j in buffer order: acc = acc + pi_j[a'];
+ *   - a' = a when flip_j == flip_first, else a' = az_mirror_action(a);
+ *   - then pi_first[a] = acc / (double)cnt.  z is treated likewise, with no mapping.
+ *   - A group of one is not written.
+ *   - The average is written into the FIRST OCCURRENCE IN ITS OWN STORED ORIENTATION, as the history pass writes back
+ *     (train.py:191-197).  Later members are left alone.
+ *   - Deliberately not done: a self-symmetric position is not averaged with its own mirrored policy.
+ *
+ * BOOKKEEPING is exactly az_replay_dedupe's: the epoch advances, n_unique is set, unique[] points at first occurrences, the
+ * call synchronises `stream`, and an empty store returns AZ_OK with n_unique = 0.
+ *
+ * EVERY READER OF THE UNIQUE LIST STAYS UNCHANGED: az_replay_sample, _sample_sym, _gather_states, _gather_forks, the two
+ * refresh entries and az_replay_read_unique read the first occurrence's own state, ply and history key pair.  A fork from a
+ * merged entry carries the first occurrence's history.
+ *
+ * MIXING THE TWO RULES.  A later az_replay_dedupe regroups by history over whatever the buffer then holds, as it always did.
+ *
+ * Limits: ply & 1, not ply, is part of the key; self-symmetric positions are not symmetrised; a second position dedupe
+ * averages the written-back first occurrence with its members again, as a second az_replay_dedupe does (the reference's
+ * aliasing).
+ *
+ * az_replay_unique_counts_device writes the member count of every unique entry of the last dedupe, of either kind, to a device
+ * i32 [n] in the order of the unique list.  n must equal n_unique, else AZ_E_INVALID.  AZ_E_STATE before any dedupe, and once
+ * an append or a capacity change has moved the epoch (the state is looked at first).  Asynchronous on `stream`.  Both dedupe
+ * entries fill the counts, in a store-owned array sized like the unique list.
+ */
+int az_replay_dedupe_positions(az_replay *r, int32_t mirror, void *stream);
+int az_replay_unique_counts_device(az_replay *r, int32_t *counts_out_dev, int64_t n, void *stream);
 
 /* The sampling of net_step (train.py:108-120): gather `batch` examples of the de-duplicated list into
  * x [batch][4][H][W] float32, pi [batch][A] float32, z [batch] float32 (all device).  `indices` (device int64
