@@ -2,6 +2,7 @@
 // (az_tower_f16.hip, az_tower_x3.hip, az_head.hip).  Internal; NOT part of the C ABI.
 #pragma once
 #include "az_net_common.h"
+#include "az_x3d_layout.h"
 
 struct HeadParams {
     int HW, A, n_ot, ksteps, n_boards;
@@ -24,8 +25,6 @@ hipError_t az_launch_tower_x3(int device, int nt, bool rp1, int r3, const TowerP
 hipError_t az_launch_tower_x3b(int device, const TowerParams &tp, int grid, hipStream_t st); // row-pair boards, <= 50 filters
 // packed column tiles (az_tower_x3d.h); variant: 0 = 8 boards in 18 tiles (6x6), 1 = 4 boards in 16 tiles (8x8), 2 = 8 boards in 21 tiles (6x7)
 hipError_t az_launch_tower_x3d(int device, int variant, const TowerParams &tp, int grid, hipStream_t st);
-struct X3DVariant { int pc, tiles, rs, R; }; // cells per plane, column tiles per workgroup, row stride, cells per board region
-constexpr int AZ_X3D_VARIANTS = 3;
-constexpr X3DVariant az_x3d_variant(int v) { return v == 0 ? X3DVariant{480, 18, 8, 58} : v == 1 ? X3DVariant{416, 16, 9, 84} : X3DVariant{480, 21, 8, 57}; }
+// (X3DVariant, az_x3d_variant: az_x3d_layout.h - the host side of the variants, plain C++)
 hipError_t az_launch_tower_x3c(int device, int bpw, const TowerParams &tp, int n_boards, hipStream_t st); // the same, a board per four waves, bpw boards per workgroup
 hipError_t az_launch_head(int device, bool x3, const HeadParams &hp, int n_boards, int lds_head, float *logits, hipStream_t st);

@@ -342,55 +342,11 @@ static bool build_x3_stream(const X3Stream &L, const uint16_t *hi_abi, const uin
     return true;
 }
 
-// Column layout of az_tower_x3d_kernel (az_tower_x3d.h) for an H x W board: boards per workgroup, row stride, cells per board
-// region, and the tables - which (board, position) is column 16 k + l15 of tile k, and for every column and tap plane the column
-// that takes its tile-X term.  Board b's cells: b R + (y + 1) rs + x + 1.  R > H rs + W keeps every tap of every position inside
-// the board or on a halo cell; (R, rs) - constants of the kernel variant - make the nb H W cells fall into the 16 residues mod 16
-// equally often; tile k takes the k-th position (in board, position order) of every residue, lane l15 the one of residue l15.
-struct X3DLayout {
-    int variant = -1, nb = 0, R = 0, rs = 0;
-    std::vector<uint16_t> pos, sdst;
-};
-static X3DLayout x3d_layout(int H, int W) {
-    X3DLayout out;
-    const int HW = H * W;
-    for (int v = 0; v < AZ_X3D_VARIANTS && out.variant < 0; v++) {
-        const X3DVariant V = az_x3d_variant(v);
-        const int ncol = 16 * V.tiles;
-        if (ncol % HW) continue;
-        const int nb = ncol / HW;
-        // (rs, R) are compile-time constants of the kernel variant: check that they suit THIS board - every tap of every position
-        // inside the board or on a halo cell, the planes large enough, the residues flat
-        const int rs = V.rs, R = V.R;
-        if (rs < W + 1 || R < H * rs + W + 1 || (nb - 1) * R + (H + 1) * rs + W + 2 > V.pc) continue;
-        int hist[16] = {0};
-        for (int b = 0; b < nb; b++)
-            for (int pp = 0; pp < HW; pp++) hist[(b * R + (pp / W + 1) * rs + pp % W + 1) & 15]++;
-        bool flat = true;
-        for (int r = 0; r < 16; r++) flat = flat && hist[r] == V.tiles;
-        if (flat) out.variant = v, out.nb = nb, out.R = R, out.rs = rs;
-    }
-    if (out.variant < 0) return out;
-    const X3DVariant V = az_x3d_variant(out.variant);
-    const int ncol = 16 * V.tiles;
-    out.pos.assign(ncol, 0);
-    std::vector<int> col_of((size_t)out.nb * HW, -1), seen(16, 0);
-    for (int b = 0; b < out.nb; b++)
-        for (int pp = 0; pp < HW; pp++) {
-            const int r = (b * out.R + (pp / W + 1) * out.rs + pp % W + 1) & 15, k = seen[r]++;
-            out.pos[k * 16 + r] = (uint16_t)(b << 8 | pp);
-            col_of[(size_t)b * HW + pp] = k * 16 + r;
-        }
-    out.sdst.assign((size_t)ncol * 8, 0xFFFF);
-    for (int col = 0; col < ncol; col++) {
-        const int b = out.pos[col] >> 8, pp = out.pos[col] & 255, y = pp / W, x = pp % W;
-        for (int t = 0; t < 8; t++) { // plane t = tap tap_of_plane(t) with d = (dy, dx): this column's value is a term of out[position - d]
-            const int tap = X3D::tap_of_plane(t), dy = tap / 3 - 1, dx = tap % 3 - 1, yd = y - dy, xd = x - dx;
-            if (yd >= 0 && yd < H && xd >= 0 && xd < W) out.sdst[(size_t)col * 8 + t] = (uint16_t)col_of[(size_t)b * HW + yd * W + xd];
-        }
-    }
-    return out;
-}
+// Column layout of az_tower_x3d_kernel (az_tower_x3d.h): x3d_layout, az_x3d_layout.h (plain C++, also built on the host by
+// tests/test_x3d_layout_host.py).
+static_assert(az_x3d_tap_of_plane(0) == X3D::tap_of_plane(0) && az_x3d_tap_of_plane(3) == X3D::tap_of_plane(3) && az_x3d_tap_of_plane(4) == X3D::tap_of_plane(4) &&
+                  az_x3d_tap_of_plane(7) == X3D::tap_of_plane(7),
+              "az_x3d_layout.h and az_net_common.h number the tap planes alike");
 
 // fc1 of the ABI layout (AZ_NET_XOUT_C channels per cell) -> xc channels per cell: [ot][k-step][lane][8], k = 32 ks + 8 (lane >> 4) + e,
 // row lane & 15
@@ -935,7 +891,9 @@ extern "C" int az_net_issued_mfma_per_board(const az_net *n, int32_t n_boards, d
     case TowerKind::X3C_FUSED_HEAD: // the fused head runs its eight chains once per board or pair of boards
         *out = 3.0 * per_tile + 3.0 * (head * 16.0 / p.per_wg);
         break;
-    case TowerKind::X3D: // the workgroup's tiles over its boards
+    case TowerKind::X3D: // the workgroup's tiles over its boards.  The count of the SCHEME: the connect_four variant issues fewer -
+        // its pure tiles sit out the k-steps of their halo row, (skip_top + skip_bot) x 36 MFMAs per workgroup and later conv
+        // (X3BK::n_mfma_pure; 27 per board) - but tests/golden/net_dispatch.json pins this figure as it is
         *out = az_x3d_variant(p.xd_variant).tiles * per_tile / p.per_wg + 3.0 * head;
         break;
     case TowerKind::WIDE:

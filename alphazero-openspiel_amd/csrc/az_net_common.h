@@ -209,7 +209,22 @@ template <bool IS_FIRST, int NT> struct X3BK {
     static constexpr int n_mfma(int ks) { return 9 + (has_t(ks) ? 2 : 0) + (has_x(ks) ? 3 : 0); } // three per product of tiles 0..2, T x (B_hi, B_lo), X
     static constexpr int n_a(int ks) { return 6 + (has_t(ks) ? 1 : 0) + (has_x(ks) ? 2 : 0); } // ah 0..2, al 0..2, T, X hi, X lo
     static constexpr int n_b(int ks) { return is_gather(ks) ? 8 * NT : 2 * NT; }
+    // -1 / +1: every k-group 4 ks + q of the k-step is a tap of the row above (taps 0-2, groups 0..17: k-steps 0-3) / below (taps 6-8,
+    // groups 36..53: k-steps 9-12) - a column tile wholly on board row 0 / row H - 1 multiplies only the zero halo row there, and
+    // az_tower_x3d_kernel leaves those tile-k-steps out; 0: mixed (conv 0 packs its taps differently; k-step 13 holds the zero-weight groups)
+    static constexpr int halo_dy(int ks) {
+        if (IS_FIRST || is_gather(ks) || 4 * ks + 3 >= 54) return 0;
+        return (4 * ks + 3) / 6 / 3 == 0 ? -1 : 4 * ks / 6 / 3 == 2 ? 1 : 0;
+    }
+    static constexpr int n_mfma_pure(int dy) { // MFMAs of a conv for a column tile whose row dy away is the halo
+        int n = 0;
+        for (int ks = 0; ks < NKSC; ks++) n += halo_dy(ks) == dy ? 0 : n_mfma(ks);
+        return n;
+    }
 };
+static_assert(X3BK<false, 1>::halo_dy(3) == -1 && X3BK<false, 1>::halo_dy(4) == 0 && X3BK<false, 1>::halo_dy(8) == 0 && X3BK<false, 1>::halo_dy(9) == 1 &&
+                  X3BK<false, 1>::halo_dy(12) == 1 && X3BK<false, 1>::halo_dy(13) == 0 && X3BK<false, 1>::n_mfma_pure(-1) == 147 - 36 && X3BK<false, 1>::n_mfma_pure(1) == 147 - 36,
+              "k-steps 0-3 are the taps with dy = -1, k-steps 9-12 those with dy = +1: 36 MFMAs each");
 static_assert(X3B::LDS <= 160 * 1024, "x3b LDS budget");
 static_assert(X3B::C0_B <= X3B::CHUNK_S, "conv 0 must fit a chunk buffer");
 

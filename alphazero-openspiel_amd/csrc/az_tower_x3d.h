@@ -20,7 +20,8 @@
 //     disease: pin_acc, az_net_common.h.)  A wave owns two or three tiles whole (three output-channel tiles + T and X); a tile left
 //     over is split by output-channel tile over four waves - mt 0, 1, 2 and T + X, each a role compiled on its own (selecting the A
 //     fragments by a run-time branch cost 45 spilled registers).  connect_four: waves 0-3 three tiles, waves 4-7 two and a share
-//     of tile 20; 6x6: every wave two and a share of tile 16 or 17; 8x8: two tiles a wave.  What made the three-tile role fit
+//     of tile 17 (which tiles: X3DV<2>::own_tile - waves 0-2 hold the tiles that lie wholly on an edge row of the board and sit out
+//     the k-steps of its halo: X3DS::tile_on); 6x6: every wave two and a share of tile 16 or 17; 8x8: two tiles a wave.  What made the three-tile role fit
 //     was the single accumulator (a third of the accumulator registers: az_net_common.h, split_pair_planes).
 //   * the waves share the planes, so a conv has two more rendezvous than x3b's: the barrier of its last k-step also separates the
 //     last plane reads from the epilogue stores, and one barrier follows the epilogue.  The shifted sum of tile X goes through
@@ -39,6 +40,7 @@
 #pragma once
 #include "az_net_common.h"
 #include "az_tower_x3b_parts.h"
+#include "az_x3d_layout.h"
 
 template <bool IS_FIRST> struct X3DK : X3BK<IS_FIRST, 1> { // (the k-steps of tiles T and X are the scheme's: az_net_common.h)
     using X3BK<IS_FIRST, 1>::has_t, X3BK<IS_FIRST, 1>::has_x, X3BK<IS_FIRST, 1>::is_gather;
@@ -55,14 +57,52 @@ template <bool IS_FIRST> struct X3DK : X3BK<IS_FIRST, 1> { // (the k-steps of ti
 // first MFMA, or behind the k-step's last MFMA if tile j + 1 has none.  wait_n(n, j): reads issued AFTER the B fragments of tile j for
 // k-step n, up to the wait in front of that tile's MFMAs - a LOWER bound (further LDS operations in between only make
 // s_waitcnt lgkmcnt(wait_n) stricter; a larger number would let the wait pass before the fragments have landed).
-template <bool IS_FIRST, int NTW, bool EXM, bool EXT> struct X3DS {
+//
+// tile_on(ks, nt): whether the wave's tile nt has MFMAs in k-step ks.  PURE (two bits per own tile: 1 = wholly on board row 0, 2 = wholly
+// on row H - 1; the host's layout provides such tiles, az_x3d_layout.h) turns a tile OFF in the k-steps whose every k-group is a tap
+// of the halo row above / below it (X3BK::halo_dy: k-steps 0-3 / 9-12 of a later conv): its B fragments there are all zeros, so the
+// MFMAs, the B-fragment reads and - for a wave with no tile on - the A-fragment reads are left out.  Everything below works on
+// the k-step's ON tiles in order: "tile j" of the sequence is tile_at(ks, j), and the counts follow from the same predicate.
+// (Leaving out an MFMA that adds exact zeros keeps every bit but one case: an accumulator that is exactly -0 stays -0 where the
+// add would have made it +0.  Accumulators start from +0 or the scaled bias, so that takes a bias of -0.0.)
+template <bool IS_FIRST, int NTW, bool EXM, bool EXT, int PURE = 0> struct X3DS {
     using K = X3DK<IS_FIRST>;
     static constexpr int NKSC = IS_FIRST ? AZ_NET_K0STEPS : X3D::NKS;
-    static constexpr int ntb(int ks) { return NTW + ((EXM || (EXT && K::has_t(ks))) ? 1 : 0); }
+    static constexpr int NTA = NTW + ((EXM || EXT) ? 1 : 0);
+    static constexpr int pure(int nt) { return nt < NTW ? (PURE >> (2 * nt)) & 3 : 0; }
+    static constexpr bool tile_on(int ks, int nt) {
+        if (nt >= NTW) return EXM || (EXT && K::has_t(ks)); // the split tile: its output-channel tiles always, its T and X where tile T is on
+        return !(pure(nt) == 1 && K::halo_dy(ks) == -1) && !(pure(nt) == 2 && K::halo_dy(ks) == 1);
+    }
+    static constexpr int idx_of(int ks, int nt) { // ON tiles in front of tile nt
+        int n = 0;
+        for (int t = 0; t < nt; t++) n += tile_on(ks, t) ? 1 : 0;
+        return n;
+    }
+    static constexpr int ntb(int ks) { return idx_of(ks, NTA); }
+    static constexpr int tile_at(int ks, int j) { // the j-th ON tile
+        for (int t = 0; t < NTA; t++)
+            if (tile_on(ks, t) && idx_of(ks, t) == j) return t;
+        return 0;
+    }
+    static constexpr int n_a(int ks) { return ntb(ks) ? K::n_a(ks) : 0; } // a k-step without tiles fetches no weights either
+    // The fetch of B(ks + 1, j) rides behind the first MFMA of ON tile j + 1 of k-step ks into the registers of tile tile_at(ks + 1, j):
+    // that tile's own MFMAs of k-step ks must be behind it, so a tile's place in the sequence may never move forward from one
+    // k-step to the next (a pure tile comes last among a wave's own tiles, and no output-channel share of a split tile follows a
+    // bottom tile).  The chunk DMA and the A fetches ride in the slots of the first ON tile: an own tile.
+    static constexpr bool order_ok() {
+        for (int ks = 0; ks < NKSC; ks++) {
+            if (ntb(ks) && tile_at(ks, 0) >= NTW) return false;
+            for (int t = 0; t < NTA && ks + 1 < NKSC; t++)
+                if (tile_on(ks, t) && tile_on(ks + 1, t) && idx_of(ks, t) > idx_of(ks + 1, t)) return false;
+        }
+        return true;
+    }
+    static_assert(order_ok(), "x3d: a pure tile in front of a tile that stays on");
     static constexpr int wait_n(int n, int j) {
         int cnt = (ntb(n) - 1 - j) * K::n_b(n); // the rest of the k-step before
         if (j >= 1 && n + 1 < NKSC) {
-            cnt += K::n_a(n + 1); // this k-step, tile 0
+            cnt += n_a(n + 1); // this k-step, tile 0
             const int upto = j - 1 < ntb(n + 1) ? j - 1 : ntb(n + 1);
             cnt += upto * K::n_b(n + 1); // B(n + 1, 0 .. j - 2)
         }
@@ -81,20 +121,36 @@ template <bool IS_FIRST, int NTW, bool EXM, bool EXT> struct X3DS {
 template <int V> struct X3DV;
 template <> struct X3DV<0> { // breakthrough 6x6-sized: 8 boards of 36 positions in 18 tiles
     static constexpr int NTILES = 18, PC = 480, RS = 8, R = 58;
-    __device__ static constexpr int first(int w) { return 2 * w; }
+    static constexpr int N_TOP = 0, N_BOT = 0; // (pure tiles whose halo k-steps the roles leave out: none here)
+    __device__ static constexpr int own_tile(int w, int nt) { return 2 * w + nt; }
     __device__ static constexpr int split_tile(int w) { return 16 + (w >> 2); }
     __device__ static constexpr int split_unit(int w) { return w & 3; }
 };
 template <> struct X3DV<1> { // 8x8: 4 boards of 64 positions in 16 tiles
     static constexpr int NTILES = 16, PC = 416, RS = 9, R = 84;
-    __device__ static constexpr int first(int w) { return 2 * w; }
+    static constexpr int N_TOP = 0, N_BOT = 0;
+    __device__ static constexpr int own_tile(int w, int nt) { return 2 * w + nt; }
     __device__ static constexpr int split_tile(int) { return -1; }
     __device__ static constexpr int split_unit(int) { return 0; }
 };
-template <> struct X3DV<2> { // connect_four-sized: 8 boards of 42 positions in 21 tiles - waves 0-3 three tiles, waves 4-7 two and a quarter of tile 20
+template <> struct X3DV<2> { // connect_four-sized: 8 boards of 42 positions in 21 tiles - waves 0-3 three tiles, waves 4-7 two and a quarter of a split tile
     static constexpr int NTILES = 21, PC = 480, RS = 8, R = 57;
-    __device__ static constexpr int first(int w) { return w < 4 ? 3 * w : 12 + 2 * (w - 4); }
-    __device__ static constexpr int split_tile(int w) { return w < 4 ? -1 : 20; }
+    // Tiles 0, 1, 2 lie wholly on board row 0 and tiles 18, 19, 20 wholly on row 5 (az_x3d_layout.h): X3DS::tile_on leaves out their
+    // k-steps of the halo row.  DEAL: which waves own them (wave w runs on SIMD w & 3; PURE of a role: X3DS) -
+    //   1  spread:       waves 0, 1, 2: (3, 0, 18), (4, 1, 19), (5, 2, 20) - one role; wave 3: (6, 7, 8); MFMAs per SIMD and later conv
+    //                    708, 708, 708, 747 (780, 780, 780, 747 without the skip)
+    //   2  concentrated: wave 0: (0, 1, 2), wave 1: (18, 19, 20) - those two waves also skip the A fragments of the k-steps they
+    //                    sit out; 672, 672, 780, 747
+    //   0  no tile is treated as pure (the kernel of before)
+    // Waves 4-7 hold two tiles of 9..16 and a share of tile 17 in every dealing.
+    static constexpr int DEAL = AZ_X3D_DEAL, N_TOP = DEAL ? 3 : 0, N_BOT = DEAL ? 3 : 0;
+    __device__ static constexpr int own_tile(int w, int nt) {
+        if (w >= 4) return (DEAL ? 9 : 12) + 2 * (w - 4) + nt;
+        if (DEAL == 1) return w < 3 ? (nt == 0 ? 3 + w : nt == 1 ? w : 18 + w) : 6 + nt;
+        if (DEAL == 2) return w == 0 ? nt : w == 1 ? 18 + nt : 3 * (w - 1) + nt;
+        return 3 * w + nt;
+    }
+    __device__ static constexpr int split_tile(int w) { return w < 4 ? -1 : DEAL ? 17 : 20; }
 };
 template <int V> struct X3DG {
     static constexpr int PC = X3DV<V>::PC, NCOL = 16 * X3DV<V>::NTILES;
@@ -170,8 +226,9 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
                                          (__attribute__((address_space(3))) void *)(lds + X3D::OFF_EPI), 16, 0, 0);
 
     // NTW: tiles the wave owns whole; EX: its share of a split tile - 0 none, 1 an output-channel tile (mt = emt), 2 tiles T and X
-    auto body = [&](auto ntw_c, auto ex_c, auto emt_c) {
-        constexpr int NTW = decltype(ntw_c)::value, EX = decltype(ex_c)::value;
+    // PURE: which of its own tiles lie wholly on board row 0 / row H - 1 (X3DS: two bits per tile)
+    auto body = [&](auto ntw_c, auto ex_c, auto emt_c, auto pure_c) {
+        constexpr int NTW = decltype(ntw_c)::value, EX = decltype(ex_c)::value, PURE = decltype(pure_c)::value;
         constexpr bool EXM = EX == 1, EXT = EX == 2;
         constexpr int NTA = NTW + (EX ? 1 : 0);  // tiles whose B fragments the wave reads
         constexpr int NTT = NTW + (EXT ? 1 : 0); // tiles whose T and X this wave holds
@@ -183,7 +240,7 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
         int grow[NTA];       // (prologue only) global board * HW + position of the lane's column, -1 = a board past the batch
 #pragma unroll
         for (int nt = 0; nt < NTA; nt++) {
-            tile[nt] = nt < NTW ? VV::first(wave) + nt : VV::split_tile(wave);
+            tile[nt] = nt < NTW ? VV::own_tile(wave, nt) : VV::split_tile(wave);
             const int e = p.xd_pos[tile[nt] * 16 + l15], b = e >> 8, pos = e & 255;
             const int y = pos / p.W, x = pos - y * p.W;
             const int cell = b * VV::R + (y + 1) * VV::RS + x + 1;
@@ -264,7 +321,7 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
             half8 at, axh, axl;       // ... of tiles T and X
             half8 bh[NTA], bl[NTA];                          // B fragments (activations) of the CURRENT k-step, per tile
             f32x2 s49[NTT];                                  // (lanes q == 0) sum over the nine tap planes at this lane's column: channels 48, 49
-            using SCH = X3DS<IS_FIRST, NTW, EXM, EXT>;
+            using SCH = X3DS<IS_FIRST, NTW, EXM, EXT, PURE>;
             unsigned gh[NTA][4], gl[NTA][4]; // the gather k-step's B fragments, dword by dword (assembled at the MFMA, behind the wait)
             auto read_a = [&](unsigned wb, auto ks_c, auto r_c) { // fragment r of k-step ks into ring slot ks & 1: ah 0..2, al 0..2, T, X hi, X lo
                 constexpr int ks = decltype(ks_c)::value, r = decltype(r_c)::value, buf = ks & 1;
@@ -303,9 +360,9 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
             asm volatile("" ::: "memory"); // (the epilogue's LDS stores stay above these untracked reads)
             { // k-step 0: nothing of it can be fetched before the barrier behind the epilogue that wrote the planes
                 const unsigned wb0 = lds_base + (chunk & 1) * CHUNK_S + lane * 16;
-                static_for<K::n_a(0)>([&](auto r_c) { read_a(wb0, std::integral_constant<int, 0>{}, r_c); });
+                static_for<SCH::n_a(0)>([&](auto r_c) { read_a(wb0, std::integral_constant<int, 0>{}, r_c); });
                 set_k(std::integral_constant<int, 0>{});
-                static_for<SCH::ntb(0)>([&](auto nt_c) { read_b(std::integral_constant<int, 0>{}, nt_c); });
+                static_for<SCH::ntb(0)>([&](auto j_c) { read_b(std::integral_constant<int, 0>{}, std::integral_constant<int, SCH::tile_at(0, decltype(j_c)::value)>{}); });
             }
             static_for<NKSC>([&](auto ks_c) {
                 constexpr int ks = decltype(ks_c)::value;
@@ -314,20 +371,27 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
                 constexpr bool last_of_conv = ks == NKSC - 1;
                 constexpr int cur = ks & 1;
                 constexpr bool T_ON = K::has_t(ks), X_ON = K::has_x(ks);
-                constexpr int NTB = SCH::ntb(ks), NTBN = last_of_conv ? 0 : SCH::ntb(ks + 1), N_ANEXT = last_of_conv ? 0 : K::n_a(ks + 1);
+                constexpr int NTB = SCH::ntb(ks), NTBN = last_of_conv ? 0 : SCH::ntb(ks + 1), N_ANEXT = last_of_conv ? 0 : SCH::n_a(ks + 1);
                 constexpr bool GATHER = K::is_gather(ks);
                 const unsigned wb_cur = lds_base + (chunk & 1) * CHUNK_S + lane * 16, wb_oth = lds_base + ((chunk + 1) & 1) * CHUNK_S + lane * 16;
                 const unsigned wb_next = last_of_chunk ? wb_oth : wb_cur; // where the next k-step's fragments live
                 // the A fragments and tile 0's B fragments of this k-step; at the conv's last k-step every plane read (the epilogue
                 // stores follow its barrier), and around the scratch path everything (its LDS operations are not in the count)
                 constexpr bool S_STORE = !IS_FIRST && ks == 8, S_SUM = !IS_FIRST && ks == 11;
-                wait_lgkm((last_of_conv || S_STORE || S_SUM || K::late_tx(ks)) ? 0 : SCH::wait_n(ks, 0));
+                wait_lgkm((last_of_conv || S_STORE || S_SUM || K::late_tx(ks) || NTB == 0) ? 0 : SCH::wait_n(ks, 0));
                 if constexpr (last_of_chunk) { // the chunk's fragments are in registers: its buffer is free, and the next chunk must be visible
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     __builtin_amdgcn_s_barrier();
                     if (!IS_FIRST && part == 0 && wave == 0) // this conv's epilogue parameters ride the same DMA path into a 2-slot ring
                         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((const unsigned char *)p.epi + (size_t)conv * 1024 + lane * 16),
                                                          (__attribute__((address_space(3))) void *)(lds + X3D::OFF_EPI + (conv & 1) * 1024), 16, 0, 0);
+                    if constexpr (NTB == 0 && !IS_FIRST) { // no MFMA slot to ride behind: the wave's pieces of chunk + 2 right here
+                        constexpr int part2 = (part + 2) % PARTS, dconv = (part + 2) / PARTS;
+                        static_for<NPW>([&](auto i_c) {
+                            issue_piece(chunk & 1, (size_t)X3D::C0_B + (size_t)(conv - 1 + dconv) * X3D::CONV_B + X3D::part_off(part2),
+                                        std::integral_constant<int, X3D::part_bytes(part2) / 1024>{}, decltype(i_c)::value);
+                        });
+                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 // channels 48, 49 (az_tower_x3b.h): tile X and the centre-tap rows of tile T are final after k-step 7.  k-step 8: every
@@ -359,13 +423,13 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
                         s49[nt] = x3b_sum_planes(pl[nt]);
                     });
                 }
-                static_for<NTB>([&](auto nt_c) {
-                    constexpr int nt = decltype(nt_c)::value;
+                static_for<NTB>([&](auto i_c) {
+                    constexpr int i = decltype(i_c)::value, nt = SCH::tile_at(ks, i); // the i-th tile with MFMAs in this k-step
                     constexpr bool OWN = nt < NTW;
                     constexpr int n_main = OWN ? 9 : (EXM ? 3 : 0), n_t = (T_ON && nt < NTT) ? 2 : 0, n_x = (X_ON && nt < NTT) ? 3 : 0;
                     constexpr int NMT = n_main + n_t + n_x;
-                    constexpr int slot0 = nt < NTW ? nt * (9 + (T_ON ? 2 : 0) + (X_ON ? 3 : 0)) : NTW * (9 + (T_ON ? 2 : 0) + (X_ON ? 3 : 0)); // k-step-wide index of the tile's first MFMA
-                    if constexpr (nt > 0) wait_lgkm(SCH::wait_n(ks, nt));
+                    constexpr int slot0 = i * (9 + (T_ON ? 2 : 0) + (X_ON ? 3 : 0)); // k-step-wide index of the tile's first MFMA (the tiles in front are own tiles)
+                    if constexpr (i > 0) wait_lgkm(SCH::wait_n(ks, i));
                     half8 b_hi, b_lo; // this tile's B fragments (every read of them has landed: pin the registers behind the wait)
                     if constexpr (GATHER) {
                         static_for<4>([&](auto i_c) {
@@ -380,12 +444,13 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
                         b_hi = bh[nt];
                         b_lo = bl[nt];
                     }
-                    if constexpr (nt == 0 && !last_of_conv) set_k(std::integral_constant<int, ks + 1>{}); // (tile 0's own fragments are in b_hi / b_lo by now)
+                    if constexpr (i == 0 && !last_of_conv) set_k(std::integral_constant<int, ks + 1>{}); // (tile 0's own fragments are in b_hi / b_lo by now)
                     static_for<NMT>([&](auto j_c) {
                         constexpr int j = decltype(j_c)::value, gslot = slot0 + j;
                         // fetches for the next k-step: its A fragments one per slot of tile 0 (at most nine: tile 0 has at least nine slots), the B fragments of tile nt - 1 behind tile nt's first MFMA
-                        if constexpr (nt == 0 && j < N_ANEXT) read_a(wb_next, std::integral_constant<int, ks + 1>{}, std::integral_constant<int, j>{});
-                        if constexpr (nt >= 1 && j == 1 && nt - 1 < NTBN) read_b(std::integral_constant<int, ks + 1>{}, std::integral_constant<int, (nt >= 1 ? nt - 1 : 0)>{});
+                        if constexpr (i == 0 && j < N_ANEXT) read_a(wb_next, std::integral_constant<int, ks + 1>{}, std::integral_constant<int, j>{});
+                        if constexpr (i >= 1 && j == 1 && i - 1 < NTBN)
+                            read_b(std::integral_constant<int, ks + 1>{}, std::integral_constant<int, SCH::tile_at(last_of_conv ? ks : ks + 1, i >= 1 ? i - 1 : 0)>{});
                         if constexpr (last_of_chunk && gslot >= 2 && (gslot - 2) % 3 == 0 && (gslot - 2) / 3 < NPW) { // buffer chunk & 1 is free: fetch chunk + 2
                             if constexpr (IS_FIRST) // conv 0's part -> the same part of conv 1
                                 issue_piece(chunk & 1, (size_t)X3D::C0_B + X3D::part_off(part), std::integral_constant<int, X3D::part_bytes(part) / 1024>{}, (gslot - 2) / 3);
@@ -408,9 +473,13 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
                 });
                 // the B fragments of the next k-step that had no later tile to ride behind; its T and X fragments where this k-step used their registers
                 if constexpr (!last_of_conv) {
-                    static_for<NTBN>([&](auto nt_c) {
-                        constexpr int nt = decltype(nt_c)::value;
-                        if constexpr (nt + 1 >= NTB) read_b(std::integral_constant<int, ks + 1>{}, nt_c);
+                    if constexpr (NTB == 0) { // a k-step the wave sits out: everything of the next one is fetched here
+                        set_k(std::integral_constant<int, ks + 1>{});
+                        static_for<N_ANEXT>([&](auto r_c) { read_a(wb_next, std::integral_constant<int, ks + 1>{}, r_c); });
+                    }
+                    static_for<NTBN>([&](auto j_c) {
+                        constexpr int j = decltype(j_c)::value;
+                        if constexpr (j + 1 >= NTB) read_b(std::integral_constant<int, ks + 1>{}, std::integral_constant<int, SCH::tile_at(ks + 1, j)>{});
                     });
                     if constexpr (K::late_tx(ks + 1) && NTT > 0)
                         static_for<K::n_tx(ks + 1)>([&](auto r_c) { read_a(wb_next, std::integral_constant<int, ks + 1>{}, std::integral_constant<int, 6 + decltype(r_c)::value>{}); });
@@ -516,18 +585,27 @@ __global__ __launch_bounds__(512, 2) void az_tower_x3d_kernel(TowerParams p) {
     constexpr auto I2 = std::integral_constant<int, 2>{};
     constexpr auto I3 = std::integral_constant<int, 3>{};
     (void)I3;
+    constexpr int TOP = 1, BOT = 2; // X3DS::pure, tile nt at bits 2 nt
     if constexpr (V == 0) {
-        if ((wave & 3) == 0) body(I2, I1, I0);
-        else if ((wave & 3) == 1) body(I2, I1, I1);
-        else if ((wave & 3) == 2) body(I2, I1, I2);
-        else body(I2, I2, I0);
+        if ((wave & 3) == 0) body(I2, I1, I0, I0);
+        else if ((wave & 3) == 1) body(I2, I1, I1, I0);
+        else if ((wave & 3) == 2) body(I2, I1, I2, I0);
+        else body(I2, I2, I0, I0);
     } else if constexpr (V == 2) {
-        if (wave < 4) body(I3, I0, I0);
-        else if (wave == 4) body(I2, I1, I0);
-        else if (wave == 5) body(I2, I1, I1);
-        else if (wave == 6) body(I2, I1, I2);
-        else body(I2, I2, I0);
-    } else body(I2, I0, I0);
+        if (wave < 4) { // three tiles; the roles with pure tiles are compiled on their own (VV::own_tile names the tiles)
+            if constexpr (VV::DEAL == 1) {
+                if (wave < 3) body(I3, I0, I0, std::integral_constant<int, TOP << 2 | BOT << 4>{});
+                else body(I3, I0, I0, I0);
+            } else if constexpr (VV::DEAL == 2) {
+                if (wave == 0) body(I3, I0, I0, std::integral_constant<int, TOP | TOP << 2 | TOP << 4>{});
+                else if (wave == 1) body(I3, I0, I0, std::integral_constant<int, BOT | BOT << 2 | BOT << 4>{});
+                else body(I3, I0, I0, I0);
+            } else body(I3, I0, I0, I0);
+        } else if (wave == 4) body(I2, I1, I0, I0);
+        else if (wave == 5) body(I2, I1, I1, I0);
+        else if (wave == 6) body(I2, I1, I2, I0);
+        else body(I2, I2, I0, I0);
+    } else body(I2, I0, I0, I0);
     // ---- copy-out (behind the barrier that ends the last conv): the image -> the workgroup's rows of xout and xout_lo, 16 bytes per
     // lane, consecutive lanes on consecutive addresses; the rows of boards past the batch are not written
     {

@@ -4,7 +4,8 @@
 
 template <int V> static hipError_t launch_x3d(int device, const TowerParams &tp, int grid, hipStream_t st) {
     static bool attr_set[AZ_MAX_DEVICES] = {false};
-    static_assert(X3DV<V>::NTILES == az_x3d_variant(V).tiles && X3DV<V>::PC == az_x3d_variant(V).pc && X3DV<V>::RS == az_x3d_variant(V).rs && X3DV<V>::R == az_x3d_variant(V).R,
+    static_assert(X3DV<V>::NTILES == az_x3d_variant(V).tiles && X3DV<V>::PC == az_x3d_variant(V).pc && X3DV<V>::RS == az_x3d_variant(V).rs && X3DV<V>::R == az_x3d_variant(V).R &&
+                      X3DV<V>::N_TOP == az_x3d_variant(V).skip_top && X3DV<V>::N_BOT == az_x3d_variant(V).skip_bot,
                   "host table (az_head_params.h) and kernel variants agree");
     if (device < 0 || device >= AZ_MAX_DEVICES || !attr_set[device]) {
         hipError_t s = hipFuncSetAttribute((const void *)az_tower_x3d_kernel<V>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
