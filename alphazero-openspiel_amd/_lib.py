@@ -121,6 +121,8 @@ PROTOTYPES = [
     ("az_engine_set_forced_playouts", C.c_int, [_vp, C.c_double, C.c_int32]),
     ("az_engine_set_eval_mirror", C.c_int, [_vp, C.c_double]),
     ("az_engine_read_request_mirror", C.c_int, [_vp, C.c_int32]),
+    ("az_engine_set_resign", C.c_int, [_vp, C.c_int32, C.c_double, C.c_double, C.c_int32]),
+    ("az_engine_resign_info_device", C.c_int, [_vp, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp]),
     ("az_engine_set_solver", C.c_int, [_vp, C.c_int32]),
     ("az_engine_set_fpu", C.c_int, [_vp, C.c_int32, C.c_double, C.c_double]),
     ("az_engine_set_arena_search", C.c_int, [_vp, C.POINTER(AzArenaSearch)]),

@@ -34,7 +34,7 @@ SEARCH_KW = ARENA_KEYS  # SelfPlayEngine.set_arena_search: the settings an arena
 
 def _apply_search(engine, settings, openings):
     """set_arena_search / set_arena_openings for what `settings` (a dict) and `openings` name; nothing named, nothing called."""
-    SearchSettings.from_kwargs({k: settings.get(k) for k in SEARCH_KW}).apply_arena(engine)
+    SearchSettings.from_kwargs({k: settings.get(k) for k in SEARCH_KW + ("resign",)}).apply_arena(engine)  # (resign: refused there)
     if openings is not None:
         engine.set_arena_openings(openings)
 

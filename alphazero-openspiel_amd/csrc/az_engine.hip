@@ -76,7 +76,8 @@ __device__ __forceinline__ uint64_t lanes_below(int lane) { return lane ? (~0ull
 
 // ------------------------------------------------------------------------------------------------
 // Philox4x32-10 counter RNG: stream = (seed, game id), counter = (ply, purpose, index, draw)
-// Purposes: 0 root noise, 1 move choice, 2 arena opponent, 3 playout cap schedule, 4 / 5 orientation of a leaf / root request
+// Purposes: 0 root noise, 1 move choice, 2 arena opponent, 3 playout cap schedule, 4 / 5 orientation of a leaf / root request,
+// 6 play-through coin of a game (self-play resignation; ply 0, index 0)
 struct Philox {
     uint32_t k0, k1, c0, c1, c2, c3;
     uint32_t out[4];
@@ -666,6 +667,42 @@ __device__ __forceinline__ int arm_search(const Params &p, int g, int gid, int p
     c->sims_base[g] = base;
     return base;
 }
+// Self-play resignation (include/az_engine.h: az_engine_set_resign) - the side information of the record row that game `gid` takes:
+// no resign ply, no flag, no criterion seen.  Called by ONE thread when a slot takes the id (az_reset_kernel, take_next_game).
+__device__ __forceinline__ void resign_clear_row(const Params &p, size_t row) {
+    const ResDev *r = p.resdev;
+    r->resign_ply[row] = -1;
+    r->flags[row] = 0;
+    r->low[row * 2] = r->low[row * 2 + 1] = INFINITY;
+}
+// ... and the rule itself, after the move of ply `ply` is recorded and az_apply has NOT ended the game.  crit = max(-root.Q, the
+// best visited child's Q), wave-uniform, from move_step's registers.  A qualifying ply (min_ply plies from the game's own start,
+// and a full search under a playout cap - the schedule's byte, arm_search's rule) lowers the mover's `low`; the first one with
+// crit < -v is the game's resign ply, and there the game's coin is drawn: u < p_playthrough, u the first uniform of the Philox
+// stream (seed, gid, ply 0, purpose 6, index 0), whatever rng_mode is - a game's fate is a function of (seed, game id, net).
+// Returns true (in every lane) when the game ends here.  Lane 0 does the work: a handful of dependent accesses on the cold path.
+__device__ __forceinline__ bool resign_step(const Params &p, int gid, int ply, double crit, int lane) {
+    const ResDev *r = p.resdev;
+    int end = 0;
+    if (lane == 0) {
+        const int start = p.starts ? p.starts[gid].ply : p.start.ply; // (as finish_game_take_next reads it)
+        const bool full = !p.capdev || p.capdev->sched[(size_t)gid * p.max_plies + ply] != 0;
+        if (full && ply - start >= r->min_ply) {
+            const size_t row = rec_row(p, gid);
+            double *low = r->low + row * 2 + (ply & 1);
+            if (crit < *low) *low = crit;
+            if (crit < -r->v && r->resign_ply[row] < 0) {
+                Philox x;
+                philox_init(x, p.seed, (uint32_t)gid, 0u, 6u, 0u);
+                const bool through = philox_u01(x) < r->p_playthrough;
+                r->resign_ply[row] = ply;
+                r->flags[row] = through ? 2 : 1;
+                end = through ? 0 : 1;
+            }
+        }
+    }
+    return rfl(__shfl(end, 0)) != 0;
+}
 // The next game id for a slot (lane 0's result, broadcast); false when none may be handed out.  A closed generation counts
 // next_game up to n_games (overshooting is harmless: nothing reads the counter's excess).  A stream takes an id only while it
 // is below *hand_limit, by compare-and-swap: no id is skipped when the limit rises later, none is handed out twice.
@@ -688,6 +725,7 @@ __device__ __forceinline__ bool take_next_game(const Params &p, int lane, SlotRe
             if ((long long)nxt >= p.n_games) nxt = ~0ull;
         }
     }
+    if (p.resdev && lane == 0 && nxt != ~0ull) resign_clear_row(p, rec_row(p, (int)nxt)); // (stream mode: the row's last game was taken)
     nxt = ((unsigned long long)rflu((uint32_t)(nxt >> 32)) << 32) | rflu((uint32_t)nxt);
     if (nxt == ~0ull) return false;
     sr.gid = (int)nxt;
@@ -956,9 +994,17 @@ __device__ __forceinline__ void move_step(const Params &p, const int g, const in
             }
         }
         st_moves++;
+        // self-play resignation: the criterion of this search, from the registers above (the soft-Z and the A0C expressions)
+        double crit = 0.0;
+        if (p.resdev) crit = fmax(-t.nd[sr.root].Q, wave_max(lane < nc ? (cn > 0 ? cq : -99.0) : -INFINITY));
+        const int ply_moved = sr.rs.ply;
         float ret0 = 0.f;
         int term = az_apply<GAME>(sr.rs, geom, action, &ret0); // game_utils.py:197
         sr.sims = 0;
+        if (!term && p.resdev && resign_step(p, sr.gid, ply_moved, crit, lane)) { // the game ends here: a loss for the player who moved
+            term = 1;
+            ret0 = (ply_moved & 1) ? 1.f : -1.f;
+        }
         if (term) {
             if (!finish_game_take_next(p, g, lane, sr, ret0, st_moves)) {
                 release_rsv();
@@ -1649,6 +1695,8 @@ __global__ void az_cap_schedule_kernel(uint64_t seed, double p_full, long long n
 
 __global__ void az_reset_kernel(Params p) {
     int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p.resdev) // self-play resignation: every row's side information starts clear (the rows of ids 0..G-1 are taken right here)
+        for (long long r = g; r < p.max_games; r += (long long)gridDim.x * blockDim.x) resign_clear_row(p, (size_t)r);
     if (g >= p.G) return;
     bool active = (long long)g < p.n_games;
     const AzState s0 = (p.starts && active) ? p.starts[g] : p.start; // game id g: its own start when a table is set
@@ -2158,8 +2206,8 @@ extern "C" int az_engine_full_moves_device(az_engine *e, uint8_t *full_out_dev, 
 }
 
 // ---- search settings: one record, one table of who may carry what, one install path ("Search settings") -------------
-// What the six public setters of include/az_engine.h put in force, as they take it: install_search normalises when it stores.
-// Params and the cap's CapDev ARE the storage (Params is the kernel argument and does not move); this is what a setter reads out
+// What the seven public setters of include/az_engine.h put in force, as they take it: install_search normalises when it stores.
+// Params, the cap's CapDev and the resignation's ResDev ARE the storage (Params is the kernel argument and does not move); this is what a setter reads out
 // of them, edits and hands back.
 struct SearchState {
     int32_t n_fast; // az_engine_set_playout_cap: 0 = no cap
@@ -2170,16 +2218,20 @@ struct SearchState {
     int32_t fpu_on; // az_engine_set_fpu
     double fpu_reduction, fpu_reduction_root;
     double p_mirror; // az_engine_set_eval_mirror: 0 = none
+    int32_t resign_on; // az_engine_set_resign
+    double resign_v, resign_p;
+    int32_t resign_min_ply;
 };
 
 // An engine is of exactly one of the first five kinds; KIND_UCT (select_rule = AZ_SELECT_UCT) is asked after that one.
 enum { KIND_SELF_CLOSED, KIND_SELF_STREAM, KIND_MANUAL, KIND_ARENA_ZERO, KIND_ARENA_NET, KIND_UCT, N_KINDS };
-enum { SET_CAP, SET_FORCED, SET_SOLVER, SET_FPU, SET_MIRROR, SET_ARENA, N_SETTERS };
+enum { SET_CAP, SET_FORCED, SET_SOLVER, SET_FPU, SET_MIRROR, SET_RESIGN, SET_ARENA, N_SETTERS };
 
 #define ARENA_REF "an arena engine (an evaluation game measures the reference's search)"
 #define ARENA_CAP "an arena engine (every agent move of an evaluation game is a full search)"
 #define ARENA_FORCED "an arena engine (an evaluation game records no policy target)"
 #define ARENA_MIRROR "an arena engine (an evaluation game measures the network as it is, in the one orientation its opponent's games are played in)"
+#define ARENA_RESIGN "an arena engine (an evaluation game is played to its end: its result is what is measured)"
 #define SELF_OWN "a self-play engine (az_engine_set_fpu / _set_solver / _set_eval_mirror are its entries)"
 // Settings against engine kinds: null = the kind may carry the setting, else why not (az_last_error: "<name> is for <who>: refused
 // for <why>").  fpu_: how the entry's own record spells the three FPU fields in its messages.
@@ -2198,6 +2250,8 @@ static const struct SearchEntry {
     {"az_engine_set_fpu", "PUCT self-play and manual_moves engines", "",
      {nullptr, nullptr, nullptr, ARENA_REF, ARENA_REF, "select_rule = AZ_SELECT_UCT (that rule already values an unvisited child at +infinity)"}},
     {"az_engine_set_eval_mirror", "self-play and manual_moves engines", "", {nullptr, nullptr, nullptr, ARENA_MIRROR, ARENA_MIRROR, nullptr}},
+    {"az_engine_set_resign", "plain self-play engines", "",
+     {nullptr, nullptr, "a manual_moves engine (its caller plays the moves and ends the games)", ARENA_RESIGN, ARENA_RESIGN, nullptr}},
     {"az_engine_set_arena_search", "AZ_ARENA_ZERO agents under the PUCT rule", "fpu_",
      {SELF_OWN, SELF_OWN, "a manual_moves engine (az_engine_set_fpu / _set_solver / _set_eval_mirror are its entries)", nullptr,
       "an AZ_ARENA_NET agent (it searches nothing: one evaluation, the argmax of the priors)",
@@ -2207,6 +2261,7 @@ static const struct SearchEntry {
 #undef ARENA_CAP
 #undef ARENA_FORCED
 #undef ARENA_MIRROR
+#undef ARENA_RESIGN
 #undef SELF_OWN
 
 static int engine_kind(const az_engine *e) {
@@ -2231,7 +2286,8 @@ static int install_search(az_engine *e, int which, Edit edit) {
         return AZ_E_INVALID;
     }
     SearchState s = {e->cap.n_fast,   e->cap.p_full,         e->p.forced_k,           e->p.forced_prune, e->p.solver,
-                     e->p.fpu_on,     e->p.fpu_reduction,    e->p.fpu_reduction_root, e->p.p_mirror};
+                     e->p.fpu_on,     e->p.fpu_reduction,    e->p.fpu_reduction_root, e->p.p_mirror,
+                     e->p.resdev ? 1 : 0, e->res.v,              e->res.p_playthrough,    e->res.min_ply};
     const int rc = edit(s);
     if (rc != AZ_OK) return rc;
     if (s.solver && s.forced_k > 0.0) { // the one exclusion: each entry names the other as the setting in force
@@ -2264,6 +2320,10 @@ static int install_search(az_engine *e, int which, Edit edit) {
         e->err = name + ": p_mirror must be finite and in [0, 1] (0 clears the setting)";
         return AZ_E_INVALID;
     }
+    if (s.resign_on && (!(s.resign_v > 0.0 && s.resign_v <= 1.0) || !(s.resign_p >= 0.0 && s.resign_p <= 1.0) || s.resign_min_ply < 0)) {
+        e->err = name + ": v must be in (0, 1], p_playthrough in [0, 1] and min_ply >= 0 (on = 0 clears the setting)";
+        return AZ_E_INVALID;
+    }
     // the commit
     HIPCHK(e, hipSetDevice(e->cfg.device));
     HIPCHK(e, hipDeviceSynchronize()); // a generation that still plays was launched under the old settings and may be reading the cap
@@ -2286,6 +2346,30 @@ static int install_search(az_engine *e, int which, Edit edit) {
         e->cap.rec_full = (uint8_t *)blk + off_full;
         e->d_cap = (CapDev *)((char *)blk + off_rec);
     }
+    if (s.resign_on && !e->d_res) { // the first call: the device record and the three arrays beside the records, ONE block as above
+        const size_t M = (size_t)e->cfg.max_games;
+        const size_t off_ply = M * 2 * sizeof(double), off_flags = (off_ply + M * sizeof(int) + 15) & ~(size_t)15,
+                     off_rec = (off_flags + M + 15) & ~(size_t)15;
+        void *blk = nullptr;
+        hipError_t hs = hipMalloc(&blk, off_rec + sizeof(ResDev));
+        if (hs == hipSuccess) hs = hipMemset(blk, 0, off_rec + sizeof(ResDev));
+        if (hs != hipSuccess) {
+            if (blk) (void)hipFree(blk);
+            e->err = name + ": " + hipGetErrorString(hs);
+            return hs == hipErrorOutOfMemory ? AZ_E_NOMEM : AZ_E_HIP;
+        }
+        e->dev_allocs.push_back(blk);
+        e->sizes.device_bytes += (int64_t)(off_rec + sizeof(ResDev));
+        e->res.low = (double *)blk;
+        e->res.resign_ply = (int *)((char *)blk + off_ply);
+        e->res.flags = (uint8_t *)blk + off_flags;
+        e->d_res = (ResDev *)((char *)blk + off_rec);
+    }
+    e->res.v = s.resign_on ? s.resign_v : 0.0;
+    e->res.p_playthrough = s.resign_on ? s.resign_p : 0.0;
+    e->res.min_ply = s.resign_on ? s.resign_min_ply : 0;
+    if (e->d_res) HIPCHK(e, hipMemcpy(e->d_res, &e->res, sizeof(ResDev), hipMemcpyHostToDevice));
+    e->p.resdev = s.resign_on ? e->d_res : nullptr;
     e->cap.n_fast = s.n_fast;
     e->cap.p_full = s.n_fast ? s.p_full : 0.0;
     if (e->d_cap) HIPCHK(e, hipMemcpy(e->d_cap, &e->cap, sizeof(CapDev), hipMemcpyHostToDevice));
@@ -2320,6 +2404,55 @@ extern "C" int az_engine_set_fpu(az_engine *e, int32_t on, double reduction, dou
 
 extern "C" int az_engine_set_eval_mirror(az_engine *e, double p_mirror) {
     return install_search(e, SET_MIRROR, [&](SearchState &s) { s.p_mirror = p_mirror; return AZ_OK; });
+}
+
+extern "C" int az_engine_set_resign(az_engine *e, int32_t on, double v, double p_playthrough, int32_t min_ply) {
+    return install_search(e, SET_RESIGN, [&](SearchState &s) {
+        s.resign_on = on ? 1 : 0; s.resign_v = v; s.resign_p = p_playthrough; s.resign_min_ply = min_ply;
+        return AZ_OK;
+    });
+}
+
+// one thread per game: the side information of game first + j, from the row that holds it
+__global__ void az_resign_info_kernel(Params p, long long first, int n, int32_t *ply_out, uint8_t *flags_out, double *low_out) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const ResDev *r = p.resdev;
+    const size_t row = (size_t)((unsigned long long)(first + j) % (unsigned long long)p.max_games); // (closed generation: the id itself)
+    ply_out[j] = r->resign_ply[row];
+    flags_out[j] = r->flags[row];
+    low_out[2 * j] = r->low[row * 2];
+    low_out[2 * j + 1] = r->low[row * 2 + 1];
+}
+
+extern "C" int az_engine_resign_info_device(az_engine *e, int64_t first_game, int64_t n_games, int32_t *ply_out_dev, uint8_t *flags_out_dev,
+                                            double *low_out_dev, void *stream) {
+    if (!e) return AZ_E_INVALID;
+    if (!e->p.resdev) {
+        e->err = "az_engine_resign_info_device: no resignation setting is in force (az_engine_set_resign)";
+        return AZ_E_STATE;
+    }
+    if (!e->reset_done) {
+        e->err = "az_engine_resign_info_device before az_engine_reset / az_engine_stream_begin";
+        return AZ_E_STATE;
+    }
+    if (!ply_out_dev || !flags_out_dev || !low_out_dev || n_games < 1) {
+        e->err = "az_engine_resign_info_device: the three outputs non-null and n_games >= 1";
+        return AZ_E_INVALID;
+    }
+    // the window of ids whose rows are theirs: the generation's games, or - a stream - the ring's rows from the first game not yet taken
+    const int64_t lo = e->streaming ? e->read_pos : 0, hi = e->streaming ? e->read_pos + e->cfg.max_games : e->n_games;
+    if (first_game < lo || n_games > hi - first_game) {
+        e->err = "az_engine_resign_info_device: games [" + std::to_string(first_game) + ", " + std::to_string(first_game) + " + " +
+                 std::to_string(n_games) + ") are outside " + (e->streaming ? "the ring's window [" : "the generation's games [") +
+                 std::to_string(lo) + ", " + std::to_string(hi) + ")";
+        return AZ_E_INVALID;
+    }
+    HIPCHK(e, hipSetDevice(e->cfg.device));
+    hipLaunchKernelGGL(az_resign_info_kernel, dim3((unsigned)((n_games + 255) / 256)), dim3(256), 0, (hipStream_t)stream, e->p,
+                       (long long)first_game, (int)n_games, ply_out_dev, flags_out_dev, low_out_dev);
+    HIPCHK(e, hipGetLastError());
+    return AZ_OK;
 }
 
 // The fields are the three setters' own, so tick_kernel picks the instantiation as it does for them; the FPU, SOLVER and MIRROR

@@ -61,6 +61,19 @@ struct CapDev {
     uint8_t *sched, *rec_full;
 };
 
+// Self-play resignation, device side (one record per engine, written by az_engine_set_resign; include/az_engine.h states the
+// rule).  The three arrays are indexed by the row of the rec_* arrays that holds the game (rec_row), beside the records:
+// resign_ply [max_games] the game's first resign ply (-1: none), flags [max_games] bit 0 = the game ended there, bit 1 = it is a
+// play-through game, low [max_games][2] per player the lowest criterion at a qualifying ply (+inf: none).  A row is cleared when a
+// slot takes the game id that maps to it (az_reset_kernel, take_next_game); move_step alone writes it after that.
+struct ResDev {
+    double v, p_playthrough;
+    int min_ply, pad;
+    int *resign_ply;
+    uint8_t *flags;
+    double *low;
+};
+
 struct Params {
     // geometry / config
     AzGeom geom;
@@ -150,8 +163,11 @@ struct Params {
     // two reductions, appended, so no other field moves.
     int fpu_on;
     double fpu_reduction, fpu_reduction_root;
+    // self-play resignation (az_engine_set_resign): null = none.  One pointer, appended, so no other field moves; only the cold
+    // paths (reset, game turnover, move_step after the move is recorded, the read-back) follow it.
+    const ResDev *resdev;
 };
-static_assert(sizeof(Params) == 984, "Params is passed by value to every kernel and baked into captured graphs: its layout does not move");
+static_assert(sizeof(Params) == 992, "Params is passed by value to every kernel and baked into captured graphs: its layout does not move");
 
 // The engine's own record arrays as a view (az_records.h); the tick kernel keeps reading p.rec_* itself.
 static inline AzRecords records_of(const Params &p) {
@@ -194,6 +210,8 @@ struct az_engine {
     StartTable start; // where games start: read through the accessors below, written by csrc/az_starts.hip alone
     CapDev cap = {0, 0, 0.0, nullptr, nullptr, nullptr}; // host copy of the playout cap's record; d_cap: the device record (p.capdev when a cap is in force)
     CapDev *d_cap = nullptr;
+    ResDev res = {0.0, 0.0, 0, 0, nullptr, nullptr, nullptr}; // host copy of the resignation record; d_res: the device record (p.resdev while set)
+    ResDev *d_res = nullptr;
     bool rows_mapped = false; // az_engine_compact_rows has been called since the last reset
     int rows_live = 0;
     bool streaming = false;   // az_engine_stream_begin since the last az_engine_reset

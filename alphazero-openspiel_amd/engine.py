@@ -96,6 +96,7 @@ class SelfPlayEngine:
         self.solver = False          # set_solver: True while the setting is in force
         self.fpu = None              # set_fpu: (reduction, root reduction) while the setting is in force
         self.arena_search = None     # set_arena_search: dict(fpu=, solver=, eval_mirror=) while an arena agent carries a setting
+        self.resign = None           # set_resign: (v, playthrough, min_ply) while the setting is in force
         self.n_games = 0
 
     # ------------------------------------------------------------------ plumbing
@@ -259,6 +260,41 @@ class SelfPlayEngine:
         afterwards."""
         self._check(self.lib.az_engine_set_fpu(self._h, 0, 0.0, 0.0))
         self.fpu = None
+
+    def set_resign(self, v, playthrough=0.1, min_ply=0):
+        """Self-play resignation (az_engine_set_resign): from the next reset() / stream_begin() on, a game ends at its first
+        RESIGN PLY - a qualifying ply (min_ply plies from the game's own start; a full search under a playout cap) whose criterion
+        max(-root.Q, best visited child Q) lies below -v - with a loss for the player who moved there; the records are the plain
+        game's up to and including that ply.  A game plays through all the same iff one Philox draw keyed by (seed, game id) is
+        below `playthrough`; resign_info() tells per game the first resign ply, whether the game resigned or played through, and
+        per player the lowest criterion seen - what resign.calibrate turns into a threshold.  v in (0, 1], playthrough in [0, 1],
+        min_ply >= 0.  Plain self-play engines (EngineError names the reason for an arena or manual_moves engine).
+        clear_resign() clears.  reset() or stream_begin() afterwards."""
+        self._check(self.lib.az_engine_set_resign(self._h, 1, float(v), float(playthrough), int(min_ply)))
+        self.resign = (float(v), float(playthrough), int(min_ply))
+
+    def clear_resign(self):
+        """Every game is played to its end again (az_engine_set_resign with on = 0).  reset() or stream_begin() afterwards."""
+        self._check(self.lib.az_engine_set_resign(self._h, 0, 0.0, 0.0, 0))
+        self.resign = None
+
+    def resign_info_device(self, first=0, n=None):
+        """-> (ply int32 [n], flags uint8 [n], low float64 [n, 2]) device tensors: the resignation side information of games
+        [first, first + n) (az_engine_resign_info_device) - the first resign ply (-1: none), bit 0 = resigned there / bit 1 = a
+        play-through game, and per player the lowest criterion at a qualifying ply (+inf: none).  One kernel on the current
+        stream, no host synchronisation.  n: default the last reset's games from `first` on; in stream mode name it, with ids
+        inside the ring's window - and read BEFORE stream_take() hands the games' rows out again."""
+        n = int(self.n_games - int(first) if n is None else n)
+        ply = torch.empty((max(n, 0),), dtype=torch.int32, device=self.device)
+        flags = torch.empty((max(n, 0),), dtype=torch.uint8, device=self.device)
+        low = torch.empty((max(n, 0), 2), dtype=torch.float64, device=self.device)
+        self._check(self.lib.az_engine_resign_info_device(self._h, int(first), n, C.c_void_p(ply.data_ptr()),
+                                                          C.c_void_p(flags.data_ptr()), C.c_void_p(low.data_ptr()), self._stream()))
+        return ply, flags, low
+
+    def resign_info(self, first=0, n=None):
+        """resign_info_device as numpy arrays: dict(ply int32 [n], resigned bool [n], playthrough bool [n], low float64 [n, 2])."""
+        return unpack_resign_info(*self.resign_info_device(first, n))
 
     def set_arena_search(self, fpu=None, solver=False, eval_mirror=0.0):
         """Search settings of an arena AGENT (az_engine_set_arena_search): from the next reset() on the "zero" agent of an
@@ -532,6 +568,12 @@ class SelfPlayEngine:
         self._check(self.lib.az_engine_export_lines_device(self._h, int(max_depth), C.c_void_p(buf.data_ptr()), int(buf.numel()),
                                                            self._stream()))
         return buf
+
+
+def unpack_resign_info(ply, flags, low):
+    """The three tensors of SelfPlayEngine.resign_info_device -> the dict of SelfPlayEngine.resign_info (host copies)."""
+    flags = flags.cpu().numpy()
+    return {"ply": ply.cpu().numpy(), "resigned": (flags & 1) != 0, "playthrough": (flags & 2) != 0, "low": low.cpu().numpy()}
 
 
 def pack_histories(histories):
@@ -909,15 +951,20 @@ class SelfPlayStream:
     eval_mirror=p: SelfPlayEngine.set_eval_mirror before the stream begins (an engine that already carries the setting streams
     with it as well).
     solver=True / False: SelfPlayEngine.set_solver before the stream begins (None leaves the engine's setting as it is).
-    fpu=r or (r, r_root): SelfPlayEngine.set_fpu before the stream begins (None leaves the engine's setting as it is)."""
+    fpu=r or (r, r_root): SelfPlayEngine.set_fpu before the stream begins (None leaves the engine's setting as it is).
+    resign=v, (v, playthrough) or (v, playthrough, min_ply): SelfPlayEngine.set_resign before the stream begins (None leaves the
+    engine's setting as it is).  While the engine carries the setting, take() reads the resignation side information of the
+    games it takes BEFORE it takes them (their rows are handed out again afterwards) and keeps it on last_resign_info: the
+    device tensors (ply, flags, low) of SelfPlayEngine.resign_info_device, None without the setting."""
 
     def __init__(self, engine, evaluator, seed=None, use_graph=True, ticks_per_graph=16, check_every=32, forced_playouts=None,
-                 eval_mirror=None, solver=None, fpu=None):
+                 eval_mirror=None, solver=None, fpu=None, resign=None):
         self.engine, self.evaluator = engine, evaluator
         self.use_graph, self.check_every = bool(use_graph), max(1, int(check_every))
         self.ticks_per_graph = min(max(1, int(ticks_per_graph)), self.check_every)
-        SearchSettings.from_kwargs(dict(forced_playouts=forced_playouts, eval_mirror=eval_mirror, solver=solver, fpu=fpu),
+        SearchSettings.from_kwargs(dict(forced_playouts=forced_playouts, eval_mirror=eval_mirror, solver=solver, fpu=fpu, resign=resign),
                                    off="clear").apply(engine)  # (None leaves the engine's setting, an off value clears it)
+        self.last_resign_info = None
         engine.stream_begin(seed)
         self.obs, self.pri, self.val = engine.alloc_io()
         self.taken = 0          # games handed over so far = the id of the next one
@@ -966,6 +1013,8 @@ class SelfPlayStream:
         if not ready():  # (games may be waiting already: after a larger capacity filled up, or when taking a few at a time)
             tick_until(self.driver, self.check_every, ready, None if max_ticks is None else start + int(max_ticks),
                        "take(%d) off the self-play stream" % n, e)
+        if getattr(e, "resign", None) is not None:  # (first: the take frees the rows, and the next tick may hand them out)
+            self.last_resign_info = e.resign_info_device(self.taken, n)
         buf, first = e.stream_take(n, out)
         self.taken = first + n
         return buf, first

@@ -12,8 +12,9 @@ import copy
 import numpy as np
 import torch
 
-from .engine import (EngineError, SearchSettings, SelfPlayEngine, SelfPlayStream, check_stream_request, close_all, examples_from_export,
-                     make_evaluator, run_selfplay, run_selfplay_pools, slot_groups, stream_capacity, unpack_device_export)
+from .engine import (EngineError, SearchSettings, SelfPlayEngine, SelfPlayStream, check_stream_request, close_all, device_export_layout,
+                     examples_from_export, make_evaluator, run_selfplay, run_selfplay_pools, slot_groups, stream_capacity,
+                     unpack_device_export, unpack_resign_info)
 from .games import Game
 from . import distributed as azdist
 
@@ -97,6 +98,13 @@ class ExampleGenerator:
             n_playouts=int(kwargs.get("n_playouts", 100)), overlap=self.overlap)  # (100: SelfPlayEngine's default)
         self.playout_cap, self.forced_playouts = self.settings.playout_cap, self.settings.forced_playouts
         self.eval_mirror, self.solver, self.fpu = self.settings.eval_mirror, bool(self.settings.solver), self.settings.fpu
+        # resign=v, (v, playthrough) or (v, playthrough, min_ply): self-play resignation (SelfPlayEngine.set_resign) in every engine
+        # this generator builds (pools, ranks, the stream of continuous=True); the returned games are the shortened ones, in the
+        # reference's format.  resign_stats accumulates over the calls what THIS process's engines played (see _note_resign).
+        self.resign = self.settings.resign
+        self.resign_stats = {"games": 0, "resigned": 0, "playthrough_would_resign": 0, "playthrough_wrong": 0,
+                             "low": np.zeros((0, 2), dtype=np.float64), "ret0": np.zeros((0,), dtype=np.float64),
+                             "weight": np.zeros((0,), dtype=np.float64)}
 
     def _engine_kwargs(self):
         return {k: self.kwargs[k] for k in _ENGINE_KW if k in self.kwargs}
@@ -111,6 +119,32 @@ class ExampleGenerator:
             close_all(engine)
             raise
         return engine
+
+    def _note_resign(self, info, buf, n, dims):
+        """One engine's games into resign_stats.  info: SelfPlayEngine.resign_info_device's tensors for the n games packed in
+        `buf` (the results are read from its game_ret0 array).  games / resigned: counted; playthrough_would_resign: play-through
+        games that have a resign ply; playthrough_wrong: those among them whose resigner - the player to move at that ply - did
+        not go on to lose; low / ret0 / weight: per-player lowest criterion, result and sampling weight of every game that was
+        PLAYED OUT (a play-through game, or one without a resign ply) - the arguments of resign.false_positive_rate /
+        resign.calibrate(..., weights=).  A game with a resign ply is played out with probability playthrough and carries the
+        weight 1 / playthrough, a game without one the weight 1 (resign.played_out_weights): the weighted rate is unbiased for
+        every threshold.  With playthrough = 0 no game with a resign ply is played out and nothing can be said about them."""
+        layout, _ = device_export_layout(n, *dims)
+        off = next(o for name, _, _, o in layout if name == "game_ret0")
+        ret0 = buf[off:off + 4 * n].cpu().numpy().view(np.float32).astype(np.float64)
+        r = unpack_resign_info(*info)
+        st = self.resign_stats
+        through = r["playthrough"] & (r["ply"] >= 0)
+        lost = np.where((r["ply"] & 1) == 0, ret0 < 0.0, ret0 > 0.0)          # did the player to move at the resign ply lose?
+        st["games"] += int(n)
+        st["resigned"] += int(r["resigned"].sum())
+        st["playthrough_would_resign"] += int(through.sum())
+        st["playthrough_wrong"] += int((through & ~lost).sum())
+        out = ~r["resigned"]
+        st["low"] = np.concatenate([st["low"], r["low"][out]])
+        st["ret0"] = np.concatenate([st["ret0"], ret0[out]])
+        weight = np.where(r["ply"][out] >= 0, 1.0 / self.resign[1] if self.resign[1] > 0.0 else 1.0, 1.0)
+        st["weight"] = np.concatenate([st["weight"], weight])
 
     def _pool_device_list(self):
         """Devices of the reference's pools when this one process drives several GPUs, else None (one engine)."""
@@ -148,7 +182,10 @@ class ExampleGenerator:
             for e in engines:
                 with torch.cuda.device(e.device):
                     b = e.export_device()
+                    info = e.resign_info_device() if self.resign is not None else None
                     torch.cuda.current_stream(e.device).synchronize()
+                if info is not None:
+                    self._note_resign(info, b, n_each, (e.max_plies, e.max_children))
                 bufs.append(b.to(self.device))
             dims = (engines[0].max_plies, engines[0].max_children)
         finally:
@@ -182,7 +219,7 @@ class ExampleGenerator:
             evaluator = None
             try:
                 evaluator = make_evaluator(self.net, self.device, self.eval_backend, self.eval_precision, n_slots, self.eval_dtype)
-                self._stream = SelfPlayStream(engine, evaluator, use_graph=self.use_graph)
+                self._stream = SelfPlayStream(engine, evaluator, use_graph=self.use_graph)  # (the engine carries the settings)
             except Exception:
                 close_all(engine, evaluator, drain=True)
                 raise
@@ -201,6 +238,8 @@ class ExampleGenerator:
                 self._stream_net = [t.detach().clone() for t in now]
         engine = self._stream_engine
         buf, _ = self._stream.take(n_local)
+        if self.resign is not None:
+            self._note_resign(self._stream.last_resign_info, buf, n_local, (engine.max_plies, engine.max_children))
         prog = engine.progress()
         prog["ticks"] = self._stream.ticks
         self.last_progress = prog
@@ -254,6 +293,8 @@ class ExampleGenerator:
                 engine.set_playout_cap(*self.playout_cap)
             evaluator = make_evaluator(self.net, self.device, self.eval_backend, self.eval_precision, n_slots, self.eval_dtype)
             self.last_progress = run_selfplay(engine, evaluator, n, use_graph=self.use_graph)
+            if self.resign is not None:
+                self._note_resign(engine.resign_info_device(), engine.export_device(), n, (engine.max_plies, engine.max_children))
             if into is not None:
                 into.append_engine(engine)
                 out = n
@@ -298,6 +339,8 @@ class ExampleGenerator:
                                               use_graph=self.use_graph, overlap=self.overlap)
             buf = engine.export_device()
             dims = (engine.max_plies, engine.max_children)
+            if self.resign is not None:
+                self._note_resign(engine.resign_info_device(), buf, n_local, dims)
             torch.cuda.current_stream(self.device).synchronize()
         finally:
             close_all(engine, *evaluators)

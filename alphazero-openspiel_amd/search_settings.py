@@ -6,8 +6,9 @@ from its keywords and lets it call the engine's setters.  Which engine kinds may
 ("Search settings"); here are the keywords' forms and the rules the facades state before an engine exists."""
 import numpy as np
 
-KEYS = ("playout_cap", "forced_playouts", "eval_mirror", "solver", "fpu")
-ARENA_KEYS = ("fpu", "solver", "eval_mirror")  # SelfPlayEngine.set_arena_search: the settings an arena agent may carry
+KEYS = ("playout_cap", "forced_playouts", "eval_mirror", "solver", "fpu", "resign")
+ARENA_KEYS = ("fpu", "solver", "eval_mirror")  # SelfPlayEngine.set_arena_search: the settings an arena agent may carry (resign is
+#                                                refused: an evaluation game is played to its end)
 
 
 def fpu_pair(fpu):
@@ -51,13 +52,32 @@ def _eval_mirror(p_given):
     return p
 
 
-_PARSE = {"playout_cap": _playout_cap, "forced_playouts": _forced_playouts, "eval_mirror": _eval_mirror, "solver": bool, "fpu": fpu_pair}
+def _resign(given):
+    """resign=v, (v, playthrough) or (v, playthrough, min_ply) -> (v, playthrough, min_ply): v in (0, 1], playthrough in [0, 1]
+    (0.1 when left out), min_ply an int >= 0 (0 when left out)."""
+    tup = tuple(given) if isinstance(given, (tuple, list)) else (given,)
+    try:
+        if not 1 <= len(tup) <= 3 or any(isinstance(x, bool) for x in tup):
+            raise TypeError
+        v, p = float(tup[0]), float(tup[1]) if len(tup) > 1 else 0.1
+        min_ply = tup[2] if len(tup) > 2 else 0
+        if int(min_ply) != min_ply:
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError("resign must be v, (v, playthrough) or (v, playthrough, min_ply), got %r" % (given,))
+    if not (0.0 < v <= 1.0 and 0.0 <= p <= 1.0 and int(min_ply) >= 0):  # (NaN fails the comparisons)
+        raise ValueError("resign needs v in (0, 1], playthrough in [0, 1] and min_ply >= 0, got %r" % (given,))
+    return v, p, int(min_ply)
+
+
+_PARSE = {"playout_cap": _playout_cap, "forced_playouts": _forced_playouts, "eval_mirror": _eval_mirror, "solver": bool, "fpu": fpu_pair,
+          "resign": _resign}
 _OFF = {"forced_playouts": lambda v: v[0] == 0.0, "eval_mirror": lambda v: v == 0.0, "solver": lambda v: not v}
 
 
 class SearchSettings:
-    """playout_cap (n_fast, p_full), forced_playouts (k, prune), eval_mirror p, solver bool and fpu (r, r_root), normalised; None
-    where the keyword was not named or was None.
+    """playout_cap (n_fast, p_full), forced_playouts (k, prune), eval_mirror p, solver bool, fpu (r, r_root) and resign (v,
+    playthrough, min_ply), normalised; None where the keyword was not named or was None.
 
     A field that is None LEAVES the engine's setting alone: apply() does not call its setter.  A named setting may be in its OFF
     form (k = 0, p = 0, solver=False; a cap and fpu have none as keywords), and what that means is the one difference between the
@@ -100,6 +120,9 @@ class SearchSettings:
                 context("playout_cap")
             if overlap > 1:
                 raise ValueError("playout_cap is not supported with overlap > 1: the capped generation is ticked on one stream")
+        if self.resign is not None and is_test:
+            raise ValueError("resign is a self-play setting: it is not supported with is_test=True (evaluation games are played to "
+                             "their end)")
         why_not_test = {"forced_playouts": "record no policy target", "eval_mirror": "show the network every position as it is",
                         "solver": "measure the reference's search", "fpu": "measure the reference's search"}
         why_puct = {"forced_playouts": "the rules are stated for the PUCT value", "solver": "its select rule is stated for the PUCT value",
@@ -118,7 +141,7 @@ class SearchSettings:
 
     def apply(self, engine):
         """The setters of the settings every engine of a facade carries, in the one order (which setter refuses first shows):
-        forced playouts, mirror, solver, fpu.  The cap is a side table of one engine: the path that reads its mask sets it."""
+        forced playouts, mirror, solver, fpu, resignation.  The cap is a side table of one engine: the path that reads its mask sets it."""
         if self.forced_playouts is not None:
             engine.set_forced_playouts(*self.forced_playouts)
         if self.eval_mirror is not None:
@@ -127,8 +150,12 @@ class SearchSettings:
             engine.set_solver(self.solver)
         if self.fpu is not None:
             engine.set_fpu(*self.fpu)
+        if self.resign is not None:
+            engine.set_resign(*self.resign)
 
     def apply_arena(self, engine):
         """The arena counterpart (SelfPlayEngine.set_arena_search): nothing on, nothing called."""
+        if self.resign is not None:
+            raise ValueError("resign is a self-play setting: an arena engine plays every evaluation game to its end")
         if self.fpu is not None or self.solver or self.eval_mirror:
             engine.set_arena_search(fpu=self.fpu, solver=bool(self.solver), eval_mirror=self.eval_mirror or 0.0)

@@ -16,10 +16,11 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from alphazero_openspiel_amd import arena, engine as E, games, replay  # noqa: E402
+from alphazero_openspiel_amd import arena, engine as E, games, replay, resign  # noqa: E402
 from alphazero_openspiel_amd.examplegenerator import ExampleGenerator  # noqa: E402
 from alphazero_openspiel_amd.fusednet import FusedNet  # noqa: E402
 from alphazero_openspiel_amd.network import Net  # noqa: E402
@@ -72,18 +73,34 @@ def main():
                     help="what the dedupe before training merges: off = examples with equal action histories, as the reference; "
                          "plain = examples of one position (bitboards and side to move) whatever the move order that led there; "
                          "mirror = also a position and its left-right mirror image, the policy mapped with the board")
+    ap.add_argument("--resign", default=None, metavar="V[:P[:MIN_PLY]]",
+                    help="self-play resignation, as AlphaGo Zero and KataGo: a game ends with a loss for the side to move once its "
+                         "search values the position below -V (after MIN_PLY plies, default 0); a share P of the games (default 0.1) "
+                         "plays through all the same, which measures the false positives (e.g. 0.9:0.1)")
+    ap.add_argument("--resign-auto", type=float, default=None, metavar="FP",
+                    help="with --resign: between generations, set V to the most eager threshold whose false-positive rate on the "
+                         "played-out games so far stays at or below FP (e.g. 0.05), and print it with the measured rate (not with "
+                         "--continuous: a stream keeps the threshold it began with)")
     a = ap.parse_args()
     dedupe = {"off": dict(), "plain": dict(by="position"), "mirror": dict(by="position", mirror=True)}[a.merge_positions]
     if a.playout_cap and a.continuous:
         ap.error("--playout-cap is not available with --continuous (the mask of full-search moves does not travel with a take)")
-    try:  # one parser and one set of rules for the five settings (alphazero_openspiel_amd/search_settings.py)
+    if a.resign_auto is not None and (a.resign is None or a.continuous):
+        ap.error("--resign-auto needs --resign and is not available with --continuous")
+    if a.resign_auto is not None and ":" in a.resign and float(a.resign.split(":")[1]) <= 0.0:
+        ap.error("--resign-auto needs a play-through share P > 0: without play-through games no false positive is ever seen")
+    try:  # one parser and one set of rules for the six settings (alphazero_openspiel_amd/search_settings.py)
         settings = E.SearchSettings.from_kwargs(dict(
             forced_playouts=a.forced_playouts or None, eval_mirror=a.eval_mirror or None, solver=a.solver,
             fpu=(tuple(float(x) for x in a.fpu.split(":")) if ":" in a.fpu else float(a.fpu)) if a.fpu else None,
-            playout_cap=tuple(a.playout_cap.split(":")) if a.playout_cap else None)).check(n_playouts=a.playouts)
+            playout_cap=tuple(a.playout_cap.split(":")) if a.playout_cap else None,
+            resign=tuple(float(x) if i < 2 else int(x) for i, x in enumerate(a.resign.split(":"))) if a.resign else None,
+        )).check(n_playouts=a.playouts)
     except ValueError as err:
-        ap.error("%s (--fpu takes R or R:R_ROOT, --playout-cap N_FAST:P_FULL)" % err)
+        ap.error("%s (--fpu takes R or R:R_ROOT, --playout-cap N_FAST:P_FULL, --resign V[:P[:MIN_PLY]])" % err)
     fpu, cap = settings.fpu, settings.playout_cap
+    seen_low, seen_ret0, seen_w = np.zeros((0, 2)), np.zeros((0,)), np.zeros((0,))   # --resign: the played-out games so far, each
+    #                                                                        with its sampling weight (resign.played_out_weights)
 
     dev = torch.device("cuda:0")
     game = games.load_game(a.game)
@@ -97,7 +114,7 @@ def main():
         generator = ExampleGenerator(net, a.game, dev, continuous=True, n_slots=min(a.games, 4096), n_playouts=a.playouts,
                                      backup=a.backup, eval_precision=a.precision, seed=1,
                                      forced_playouts=a.forced_playouts or None, eval_mirror=a.eval_mirror or None, solver=a.solver,
-                                     fpu=fpu)
+                                     fpu=fpu, resign=settings.resign)
     for gen in range(1, a.generations + 1):
         t0 = time.perf_counter()
         net.eval()
@@ -117,6 +134,28 @@ def main():
         t_play = time.perf_counter() - t0
         if generator is None:
             store.append_engine(eng)
+            if settings.resign is not None:                                # what the threshold did, and - auto - the next one
+                info = eng.resign_info()
+                ret0 = E.unpack_device_export(eng.export_device().cpu().numpy(), a.games, eng.max_plies, eng.max_children)["game_ret0"]
+                out = ~info["resigned"]
+                seen_low, seen_ret0 = np.concatenate([seen_low, info["low"][out]]), np.concatenate([seen_ret0, ret0[out]])
+                if settings.resign[1] > 0.0:                               # a game with a resign ply is played out with probability P
+                    seen_w = np.concatenate([seen_w, resign.played_out_weights(info["ply"][out] >= 0, settings.resign[1])])
+                else:
+                    seen_w = np.concatenate([seen_w, np.ones(int(out.sum()))])
+                v = settings.resign[0]
+                rate, n_below = resign.false_positive_rate(seen_low, seen_ret0, v, seen_w)
+                print("gen %d: resign v %.3f: %d of %d games resigned | false-positive rate %.3f at that v, over the %d players below it "
+                      "in the %d played-out games so far (play-through games and games without a resign ply, weighted by how often "
+                      "each kind is played out)" % (gen, v, int(info["resigned"].sum()), a.games, rate, n_below, len(seen_ret0)), flush=True)
+                if a.resign_auto is not None:
+                    try:
+                        v = resign.calibrate(seen_low, seen_ret0, target=a.resign_auto, weights=seen_w)
+                        settings.resign = (v,) + settings.resign[1:]
+                        print("gen %d: resign-auto: v -> %.3f (rate %.3f on the same weighted games, target %.3f)"
+                              % (gen, v, resign.false_positive_rate(seen_low, seen_ret0, v, seen_w)[0], a.resign_auto), flush=True)
+                    except ValueError as err:
+                        print("gen %d: resign-auto: %s" % (gen, err), flush=True)
             eng.close()
         if gen % 2 == 0 and n_buffer < n_buffer_max:                       # Trainer.update_buffer_size
             n_buffer += a.games

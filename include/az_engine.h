@@ -364,6 +364,60 @@ int az_engine_set_eval_mirror(az_engine *e, double p_mirror);
 int az_engine_read_request_mirror(az_engine *e, int32_t slot);
 
 /*
+ * Self-play resignation (AlphaGo Zero: Silver et al. 2017, "Methods"; KataGo) for SELF-PLAY: a game whose side to move has been
+ * lost for a while is ended early instead of being searched to its last ply, and a fraction of the games plays through all the
+ * same, so the rate of false positives of any threshold can be measured.  The reference has no counterpart (play_game_self plays
+ * every game out, game_utils.py:156-197); with nothing set every kernel computes what it computed before, bit for bit.
+ *
+ * az_engine_set_resign: plain self-play engines (arena_agent == AZ_ARENA_SELF_PLAY, manual_moves == 0; closed generations and stream
+ *   mode): an arena or a manual_moves engine returns AZ_E_INVALID and az_last_error names the reason.  on != 0: v in (0, 1],
+ *   p_playthrough in [0, 1], min_ply >= 0; on == 0 clears the setting (the other arguments are not read).  Call it before
+ *   az_engine_reset or az_engine_stream_begin (the next call the engine accepts, as after every setter: a generation or a stream
+ *   that was running is over, az_engine_advance refuses until one of the two is called); it may be called between generations with
+ *   another v, holds for every later generation, and composes with a start prefix, a game-start table, a playout cap, forced
+ *   playouts, the mirror, the solver, first-play urgency, both rng_modes, keep_search_tree, az_engine_advance_slots on several
+ *   streams and the dense rows of az_engine_advance_rows.
+ * The criterion: once the search at absolute ply t has ended, the move is chosen and the ply is recorded exactly as without the
+ *   setting (state, move, child actions, child visits, value target), and the move is applied.  A game that this move ends keeps
+ *   its result.  Otherwise crit = max(r, b) in f64, r = -root.Q (the AZ_BACKUP_SOFT_Z target's expression), b = the largest Q of
+ *   a root child with a visit, -99.0 for a child without one (the AZ_BACKUP_A0C target's expression; the counts are those the move
+ *   was drawn from).  Ply t QUALIFIES when t - start_ply >= min_ply, start_ply the game's own start (a start prefix's or its entry
+ *   of the game-start table), and - under a playout cap - its search was a full one.  It is a RESIGN PLY when it qualifies and
+ *   crit < -v.
+ * Play-through: game id g plays through iff u < p_playthrough, u the first philox_u01 of the Philox stream (seed, game id, ply 0,
+ *   purpose 6, index 0) - from Philox whatever rng_mode is, so a game's fate depends on (seed, game id, network) alone, whichever
+ *   slot, slot group, stream, pool or rank plays it.  (Purposes 0..5: root noise, move choice, arena opponent, playout cap, the two
+ *   orientation coins.)  A play-through game is the game without the setting, bit for bit.
+ * Resigning: at the first resign ply of a game that does not play through, the game ends: game_len = t - start_ply + 1 (the resign
+ *   ply is the last recorded one), game_ret0 = -1 when the player to move at t was player 0 and +1 otherwise, and the slot takes
+ *   the next game as after a terminal move.  The records of a resigned game are the first game_len plies of the game without the
+ *   setting; only game_ret0 (and with AZ_BACKUP_ON_POLICY the value fill that follows from it) differs.  The packed export,
+ *   az_example_view, az_engine_stream_take_device and every az_replay_append_* entry read game_len and game_ret0 and do not change.
+ * Side information, per game, beside the records (not in the packed export): resign_ply (int32: the first resign ply, resigned or
+ *   not; -1 = none), flags (u8: bit 0 = the game resigned there, bit 1 = it is a play-through game - written at the first resign
+ *   ply, so a game without one shows 0), low[2] (f64, per player: the lowest crit that player saw at a qualifying ply, +infinity =
+ *   none; from it and game_ret0 the host computes the false-positive rate of ANY threshold from one batch of play-through games).
+ *   A game's information is cleared when a slot takes its id.  In stream mode it therefore stays valid until the id one ring
+ *   length later is handed out: read it BEFORE az_engine_stream_take_device frees the row.
+ *
+ * az_engine_resign_info_device: writes the side information of games [first_game, first_game + n_games) to ply_out_dev (int32
+ *   [n_games]), flags_out_dev (u8 [n_games]) and low_out_dev (f64 [n_games][2]), device memory.  One small kernel, a thread per
+ *   game, asynchronous on `stream`, no host synchronisation: it may be captured in a graph.  Closed generation: ids within
+ *   [0, n_games of the last az_engine_reset).  Stream mode: ids within the ring's window [first game not yet taken, + max_games).
+ *   AZ_E_INVALID outside the window or with a null output, AZ_E_STATE with nothing set or before az_engine_reset /
+ *   az_engine_stream_begin.  A game still in play shows what it has seen so far.  An id of the window that no slot has taken yet
+ *   (az_progress.games_started counts the ids handed out) shows what its row last held: in a closed generation the cleared
+ *   state az_engine_reset left, in a stream after a wrap the information of the game one ring length earlier - the entry runs
+ *   no host synchronisation, so it does not read the hand-out counter: bound first_game + n_games by games_started.
+ *
+ * Limits: one ply below the threshold resigns (a rule of several consecutive plies is another feature); arena and duel engines
+ *   play every game out.
+ */
+int az_engine_set_resign(az_engine *e, int32_t on, double v, double p_playthrough, int32_t min_ply);
+int az_engine_resign_info_device(az_engine *e, int64_t first_game, int64_t n_games, int32_t *ply_out_dev, uint8_t *flags_out_dev,
+                                 double *low_out_dev, void *stream);
+
+/*
  * MCTS-Solver (Winands, Bjornsson, Saito 2008; "certainty propagation"): the search proves wins, losses and draws inside its tree
  * and acts on them.  The reference scores a terminal node again on every visit (mcts.py:148-152) and knows no proof; with nothing
  * set every kernel computes what it computed before, bit for bit.
